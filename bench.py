@@ -2,7 +2,7 @@
 """Benchmarks of the hot path on synthetic 1080p clips (BASELINE.json configs[1..4]); the default is the headline:
 frames/sec of Real-ESRGAN x4 (RRDBNet-x4plus, 23 blocks), 1920x1080 -> 7680x4320.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config sr|rife|tap|chain]
+  python bench.py [--gpus N --steps K --warmup W] [--config sr|rife|tap|chain] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -16,10 +16,17 @@ it).  Rank 0 prints ONE JSON line.
                      average locally (sharding.sharded_tap_denoise_device)
   chain  configs[4]  temporal denoise -> Real-ESRGAN x4 -> RIFE x2 per block of frames, device-resident hand-off
 
-Extra objects on the line: `roofline` (measured live with HIP events on the launch stream; MFMA-bound convs for sr / chain, HBM
-byte model of the engine's own dataflow for tap / rife), `cpu_baseline` (the fp32 CPU oracle on a bounded crop, rank 0 at N=1),
-`parity` (the engine against that same oracle output: max-abs on the [0,1] float image before quantisation, PSNR on uint8),
-and for sr at N=1 `host_to_host` (pinned host frame in, host frame out through the 3-stream pipeline: PCIe-inclusive).
+A plain run sets up, warms up, times the steps and prints the line.  With `--full` the line also carries: `roofline` (measured
+live with HIP events on the launch stream; MFMA-bound convs for sr / chain, HBM byte model of the engine's own dataflow for
+tap / rife), `energy` (rocm-smi sampled by a child process during the timed region), `cpu_baseline` (the fp32 CPU oracle on a
+bounded crop, rank 0 at N=1), `parity` (the engine against that same oracle output: max-abs on the [0,1] float image before
+quantisation, PSNR on uint8), and for sr at N=1 `host_to_host` (pinned host frame in, host frame out through the 3-stream
+pipeline: PCIe-inclusive).
+
+`--dump-outputs DIR` writes what the last timed step handed back (rank 0) as DIR/<name>.npy in float32: sr_out (the upscaled
+frame), rife_mid, tap_denoised, chain_upscaled + chain_mid.  An output larger than its share of DUMP_BYTES is written as a
+fixed sample of its elements (flat indices drawn from PCG64 with seed 0, sorted): the same elements on every run with the
+same arguments, whose inputs are seeded too.
 """
 from __future__ import annotations
 
@@ -54,6 +61,10 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-crop", type=int, default=192, help="side of the square crop timed on the CPU oracle (also the parity crop)")
     ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, energy, cpu_baseline + parity and host_to_host (runs of their own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most DUMP_BYTES in all)")
     return ap.parse_args()
 
 
@@ -86,6 +97,26 @@ def psnr_u8(a, b):
     import numpy as np
     mse = float(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2))
     return 99.0 if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)
+
+
+DUMP_BYTES = 48_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays` (name -> device tensor) as out_dir/<name>.npy in float32: whole when it fits its share of DUMP_BYTES, else the
+    elements at a fixed, seeded, sorted set of flat indices (1-D)."""
+    import numpy as np
+    import torch
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        if t.numel() <= share:
+            a = t.float().cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=share))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def lib_digest():
@@ -273,9 +304,12 @@ def main():
         return full
 
     def run_pass(k):
+        """-> what this rank's last frame of the pass handed back: {name: device tensor} (empty when the rank had no frame)."""
+        last = lambda d: d[max(d)] if d else None
         if cfg == "sr":
             for i in range(k):
                 sr.upscale_device(frame_of(i), out=out_sr)
+            got = {"sr_out": out_sr}
         elif cfg == "rife":
             # k pairs = k + 1 frames of which this rank owns k; the halo (the next rank's first frame) crosses the link once
             frames = global_list([frame_of(i) for i in range(k)])
@@ -283,26 +317,30 @@ def main():
                 frames.append(frame_of(k))
             else:
                 frames.append(frame_of(k) if rank == world - 1 else None)
-            S.sharded_interpolate_device(ifn, frames, halo_device=halo_dev)
+            got = {"rife_mid": last(S.sharded_interpolate_device(ifn, frames, halo_device=halo_dev))}
         elif cfg == "tap":
-            S.sharded_tap_denoise_device(tap, global_list([frame_of(i) for i in range(k)]), halo_device=halo_dev)
+            got = {"tap_denoised": last(S.sharded_tap_denoise_device(tap, global_list([frame_of(i) for i in range(k)]), halo_device=halo_dev))}
         else:
             den = S.sharded_tap_denoise_device(tap, global_list([frame_of(i) for i in range(k)]), halo_device=halo_dev)
             ups = [None] * (world * k)
             for i, t in den.items():
                 ups[i] = sr.upscale_device(t)
-            S.sharded_pairs(ups, lambda a, b: ifn.interpolate_device(a.to(dev), b.to(dev), 0.5), device=halo_dev)
+            mids = S.sharded_pairs(ups, lambda a, b: ifn.interpolate_device(a.to(dev), b.to(dev), 0.5), device=halo_dev)
+            got = {"chain_upscaled": ups[max(den)] if den else None, "chain_mid": last(mids)}
+        return {n: t for n, t in got.items() if t is not None}
 
     chunk = {"sr": steps, "rife": steps, "tap": min(steps, 20), "chain": min(steps, 4)}[cfg]   # frames resident per pass
 
     def run_steps(n):
-        done = 0
+        done, got = 0, {}
         while done < n:
             k = min(chunk, n - done)
             if cfg in ("tap", "chain") and world > 1 and n - done - k == 1:
                 k += 1            # never leave a one-frame block behind
-            run_pass(k)
+            got = {}              # the previous pass's outputs go back to the allocator before this pass, as when they were dropped
+            got = run_pass(k)
             done += k
+        return got
 
     warm = max(1, args.warmup)
     if cfg in ("tap", "chain") and world > 1:
@@ -317,10 +355,10 @@ def main():
     barrier()
     torch.cuda.synchronize()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    sampler = PowerSampler(dev_ord) if rank == 0 else None       # rocm-smi in a child process, twice a second: joules per step
+    sampler = PowerSampler(dev_ord) if rank == 0 and args.full else None   # rocm-smi in a child process, twice a second: joules per step
     t0 = time.perf_counter()
     ev0.record()
-    run_steps(steps)
+    outputs = run_steps(steps)
     ev1.record()
     torch.cuda.synchronize()
     barrier()
@@ -332,10 +370,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t.item())
     dev_ms = ev0.elapsed_time(ev1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)      # before the --full legs: the roofline's frames reuse out_sr
+    del outputs
 
     # ---- roofline --------------------------------------------------------------------------------------------------------
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if cfg in ("sr", "chain"):
             # HIP events around every conv launch of the Real-ESRGAN forward, on the launch stream (the MFMA implicit-GEMM
             # kernels are > 99 % of its FLOPs)
@@ -393,12 +434,12 @@ def main():
 
     # ---- parity + CPU baseline: the engine and the fp32 oracle on one crop (outside every timed region) --------------------------
     parity = cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         parity, cpu = parity_and_cpu(cfg, args, clip, sr, ifn, naf, sd_sr, sd_if, sd_naf, num_block, scale, H * W)
 
     # ---- PCIe-inclusive rate (sr, one GPU): pinned host frames through the 3-stream pipeline -----------------------------------
     host = None
-    if rank == 0 and world == 1 and cfg == "sr" and not args.no_host_path:
+    if args.full and rank == 0 and world == 1 and cfg == "sr" and not args.no_host_path:
         n_h = min(steps, 30)
         for _ in sr.upscale_stream([clip[i % n_distinct] for i in range(3)], depth=2):   # pins the staging slots (tens of ms, once)
             pass

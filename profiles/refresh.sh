@@ -29,10 +29,10 @@ python3 tools/make_traffic_path.py "$o/pmc_tap" profiles/${R}_traffic_tap.json 4
 python3 tools/make_traffic_path.py "$o/pmc_restormer" profiles/${R}_traffic_restormer.json 3 f16 > /dev/null
 python3 tools/make_traffic_path.py "$o/pmc_rife" profiles/${R}_traffic_rife.json 5 f16 > /dev/null
 cp profiles/${R}_traffic_tap.json profiles/${R}_traffic_restormer.json profiles/${R}_traffic_rife.json "$o/"
-python3 bench.py > "$o/bench_sr.json" 2> "$o/bench_sr.err"
-python3 bench.py --config rife > "$o/bench_rife.json" 2> "$o/bench_rife.err"
-python3 bench.py --config tap > "$o/bench_tap.json" 2> "$o/bench_tap.err"
-python3 bench.py --config chain > "$o/bench_chain.json" 2> "$o/bench_chain.err"
+python3 bench.py --full > "$o/bench_sr.json" 2> "$o/bench_sr.err"
+python3 bench.py --full --config rife > "$o/bench_rife.json" 2> "$o/bench_rife.err"
+python3 bench.py --full --config tap > "$o/bench_tap.json" 2> "$o/bench_tap.err"
+python3 bench.py --full --config chain > "$o/bench_chain.json" 2> "$o/bench_chain.err"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$o/stats_sr" -- python3 "$root/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-host-path > "$o/stats_sr.log" 2>&1
 cd "$root"

@@ -75,3 +75,36 @@ def test_power_sampler_never_takes_the_bench_down(tmp_path, monkeypatch):
         time.sleep(0.1)
     r = s.stop()
     assert r is not None and r["power_w"] == 1399.0 and r["sclk_mhz"] == 1750 and r["samples"] >= 3
+
+
+def test_full_and_dump_outputs_are_opt_in(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs the headline only: the legs of their own (roofline, energy, parity +
+    cpu_baseline, host_to_host) wait for --full, and nothing is written without --dump-outputs."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse_args()
+    assert a.full is False and a.dump_outputs is None and (a.gpus, a.steps, a.warmup) == (1, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse_args()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: an output within its share of DUMP_BYTES is written whole, in its shape; a larger one as the elements at a
+    seeded, sorted set of flat indices - the same on every run - and the files stay within the budget."""
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_BYTES", 4000)            # 500 float32 elements per output when there are two
+    small = torch.arange(18, dtype=torch.uint8).reshape(2, 3, 3)
+    big = torch.randint(0, 256, (40, 50, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(5))
+    for d in ("a", "b"):
+        b.dump_outputs(tmp_path / d, {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 3) and np.array_equal(s, small.numpy())
+    g = np.load(tmp_path / "a" / "big.npy")
+    assert g.dtype == np.float32 and g.ndim == 1 and 400 < g.size <= 500
+    idx = np.unique(np.random.default_rng(0).integers(0, big.numel(), size=500))
+    assert np.array_equal(g, big.numpy().reshape(-1)[idx].astype(np.float32))
+    assert np.array_equal(g, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(4 * np.load(f).size for f in (tmp_path / "a").iterdir()) <= 4000

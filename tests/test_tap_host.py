@@ -57,10 +57,15 @@ def test_oracle_truncates_like_the_reference():
     assert out[0, 0, 0] == 254 and out[0, 1, 0] == 127 and out[1, 0, 0] == 0 and out[1, 1, 0] == 255
 
 
-def test_unaccelerated_models_are_reported_unavailable():
+def test_unaccelerated_models_are_reported_unavailable(hip_lib):
     assert T.TAPDenoiseConfig().model is T.TAPModel.RESTORMER          # the reference's default (tap_denoise.py:110)
-    d = T.TAPDenoiser(T.TAPDenoiseConfig(model=T.TAPModel.TAP))
-    assert d.is_available() is False
+    # every TAPModel has an engine (TAP runs on the Restormer backbone, the reference's fallback): available exactly when a device is
+    has_gpu = hip_lib.fw_device_count() > 0
+    for m in T.TAPModel:
+        assert T.TAPDenoiser(T.TAPDenoiseConfig(model=m)).is_available() is has_gpu, m
+    cfg = T.TAPDenoiseConfig()
+    cfg.model = "basicvsr"                                              # a model outside the accelerated set: never available
+    assert T.TAPDenoiser(cfg).is_available() is False
 
 
 # ---- pinned on outputs of the reference's own code (tests/golden/tap_reference.*, oracle/gen_golden.py tap_logic) ----

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/r03/box_$1
 mkdir -p $o
-python3 bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-host-path > $o/bench.json 2> $o/bench.err
+python3 bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-host-path > $o/bench.json 2> $o/bench.err
 bash tools/power_trace.sh $o/power.log
 python3 - <<PY
 import json, re, statistics as st
