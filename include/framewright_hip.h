@@ -56,8 +56,8 @@ typedef struct fw_nafnet fw_nafnet;
 /* Message of the last failing call on this thread ("" if none).  Never NULL. */
 const char* fw_last_error(void);
 
-/* ABI version of this header: 3.  Bumped whenever entry points are added or changed (1 -> 2 and 2 -> 3 were additive: a binder of
- * version 1 or 2 keeps working against this library). */
+/* ABI version of this header: 4.  Bumped whenever entry points are added or changed (1 -> 2, 2 -> 3 and 3 -> 4 were additive: a
+ * binder of version 1, 2 or 3 keeps working against this library). */
 int fw_abi_version(void);
 
 /* Number of visible HIP devices (0 when there is no GPU; never fails). */
@@ -187,6 +187,34 @@ size_t fw_pack_conv_up2x_phase(int dtype, const float* weight, uint16_t* dst);
 int fw_conv_up2x_phase_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int height, int width,
                             const void* packed_weight, const float* bias, int act_lrelu, void* out, int out_cstride,
                             long out_plane_stride, void* stream);
+
+/* conv5 of a residual dense block on the split trunk (64 output channels; the trunk is held as operand-typed hi planes plus lo planes
+ * that keep the rounding error of the hi values):
+ *   y = s1 * (conv3x3(x) + bias + in_id_scale * x[0:64] + sum_{c < n_id} id_scale[c] * plane_c);  y = lrelu(y, 0.2) if post_act
+ *   out = T(y), out_lo = T(y - T(y)) (out_lo may be NULL: hi only)
+ * x, the padding and strides as in fw_conv3x3_nhwc; residual plane c (32 channels) is read at byte offset chunk_off[c] from x with
+ * pixel stride in_cstride and feeds output channels [32 (c & 1), 32 (c & 1) + 32).  in_id_scale and id_scale[c] must be exactly
+ * representable in the operand type.  The two 32-channel halves of out / out_lo are out_plane_stride elements apart (0 = 32).
+ * winograd = 0: the direct kernel, packed_weight = fw_pack_conv3x3(cout 64, cin, 2, cin_chunks).
+ * winograd = 1: the row-wise Winograd F(2, 3) kernel (f16 only; no post_act), packed_weight = fw_pack_conv3x3_wino(...).
+ * fw_pack_conv3x3_wino packs a torch-layout weight [cout][cin][3][3] (host fp32, cout <= 64, cin <= 32*cin_chunks) into the
+ * Winograd kernel's fragments: per tap row (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2), summed in fp32 and rounded to f16
+ * once.  f16 only (any other dtype returns 0); returns the number of uint16, dst = NULL to size the buffer.
+ * fw_conv3x3_wino_nhwc: act(conv3x3(x) + bias) (act_lrelu 0 or 1), 64 output channels, with the Winograd kernel (conv_hr's form). */
+size_t fw_pack_conv3x3_wino(int dtype, const float* weight, int cout, int cin, int cin_chunks, uint16_t* dst);
+int fw_conv3x3_split_nhwc(int dtype, int winograd, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int height,
+                          int width, const void* packed_weight, const float* bias, float s1, float in_id_scale, int n_id,
+                          const long* chunk_off, const float* id_scale, int post_act, void* out, void* out_lo, int out_cstride,
+                          long out_plane_stride, int out_coff, void* stream);
+int fw_conv3x3_wino_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int height, int width,
+                         const void* packed_weight, const float* bias, int act_lrelu, void* out, int out_cstride,
+                         long out_plane_stride, int out_coff, void* stream);
+/* Self-check of the Winograd launchers' argument checks (host only, no device call, nothing launched): for each of the fields
+ * the Winograd kernels do not implement (post_act, chan_scale, res1, res2, out_f32, n_groups > 1, act in the split form, in_id_scale /
+ * id_scale not exact in f16; out_f32, n_groups, chan_scale, post_act, res1, PReLU and out_lo in the STORE form), one otherwise valid
+ * problem with that field set is checked and its status (FW_ERR_INVALID when rejected, FW_OK when not) written to codes[i], i < n.
+ * Returns the number of cases, or -1 when one of the unmodified valid problems is rejected (message in fw_last_error). */
+int fw_conv3x3_wino_check_fields(int* codes, int n);
 
 /* -------------------------------------------------------------------------------------------------
  * TAP temporal denoise: NAFNet

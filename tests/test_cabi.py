@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol(hip_lib):
 
 
 def test_abi_version_and_error_string(hip_lib):
-    assert hip_lib.fw_abi_version() >= 1
+    assert hip_lib.fw_abi_version() == 4
     assert isinstance(hip_lib.fw_last_error(), bytes)
 
 

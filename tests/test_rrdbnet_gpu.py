@@ -577,3 +577,139 @@ def test_winograd_conv5_vs_oracle_and_vs_the_direct_kernel(hip_lib, monkeypatch,
     assert err < 1e-3 and np.abs(rgb - rgb_d).max() < 1e-3
     want_u8 = (np.clip(want, 0, 1) * 255.0).round().astype(np.uint8)[:, :, ::-1]
     assert _psnr_u8(u8, want_u8) >= 60.0 and np.abs(u8.astype(int) - want_u8.astype(int)).max() <= 1
+
+
+def _c5_outputs(monkeypatch, sd, frame, num_block, scale, modes, hr_wino="0"):
+    outs = {}
+    monkeypatch.setenv("FW_RRDB_HR_WINO", hr_wino)
+    for mode in modes:
+        monkeypatch.setenv("FW_RRDB_C5_WINO", mode)
+        eng = R.RRDBNetEngine(num_block, scale, "f16")
+        eng.load_state_dict(sd)
+        outs[mode] = _gpu_rgb_f32(eng, frame)
+        eng.close()
+    return outs
+
+
+@pytest.mark.parametrize("wino", ["1", "2"])
+@pytest.mark.parametrize("num_block,scale,H,W", [(6, 4, 33, 47), (23, 2, 41, 57)])
+def test_winograd_conv_hr_vs_oracle_and_vs_the_direct_kernel(hip_lib, monkeypatch, num_block, scale, H, W, wino):
+    """conv_hr at the output resolution as the Winograd STORE form (FW_RRDB_HR_WINO=1) on top of conv5 in that form: the bar of
+    test_winograd_conv5_vs_oracle_and_vs_the_direct_kernel against the fp32 oracle, and within rounding of the direct path."""
+    sd = synthetic_rrdbnet_state(num_block, scale, seed=4321)
+    frame = synthetic_frames(1, H, W, seed=H + W)[0]
+    (rgb, u8), = _c5_outputs(monkeypatch, sd, frame, num_block, scale, [wino], hr_wino="1").values()
+    (rgb_c5, _), = _c5_outputs(monkeypatch, sd, frame, num_block, scale, [wino]).values()
+    (rgb_d, _), = _c5_outputs(monkeypatch, sd, frame, num_block, scale, ["0"]).values()
+    want = _oracle_rgb_f32(sd, frame, num_block, scale)
+    err = np.abs(rgb - want).max()
+    print(f"hr_wino nb={num_block} x{scale} {H}x{W} c5_wino={wino}: vs oracle {err:.2e}, vs direct {np.abs(rgb - rgb_d).max():.2e}")
+    assert not np.array_equal(rgb, rgb_c5)                  # the knob took effect
+    assert err < 1e-3 and np.abs(rgb - rgb_d).max() < 1e-3
+    want_u8 = (np.clip(want, 0, 1) * 255.0).round().astype(np.uint8)[:, :, ::-1]
+    assert _psnr_u8(u8, want_u8) >= 60.0 and np.abs(u8.astype(int) - want_u8.astype(int)).max() <= 1
+
+
+@pytest.mark.parametrize("c5_wino", ["0", "1"])
+def test_golden_trunk_and_tail_both_conv5_forms(hip_lib, golden_dir, monkeypatch, c5_wino):
+    """test_golden_trunk_and_tail (f16) with conv5 pinned explicitly to the direct kernel (0) and to the Winograd form (1)."""
+    monkeypatch.setenv("FW_RRDB_C5_WINO", c5_wino)
+    g = np.load(golden_dir / "rrdb_reference.npz")
+    sd = synthetic_rrdbnet_state(2, 4, seed=int(g["net_seed"]))
+    frame = np.ascontiguousarray((g["net_in"][0].transpose(1, 2, 0)[:, :, ::-1] * 255).round().astype(np.uint8))
+    eng = R.RRDBNetEngine(2, 4, "f16")
+    eng.load_state_dict(sd)
+    rgb, _ = _gpu_rgb_f32(eng, frame)
+    eng.close()
+    want = _oracle_rgb_f32(sd, frame, 2, 4)
+    print(f"golden c5_wino={c5_wino}: max-abs {np.abs(rgb - want).max():.2e}")
+    assert np.abs(rgb - want).max() < 1e-3
+    with torch.no_grad():
+        y = ref.rrdbnet_forward(_sd_t(sd), torch.from_numpy(g["net_in"]), 2, 4).numpy()
+    assert np.abs(y - g["net_out"]).max() < 2e-5
+
+
+def _high_contrast_frame(H, W, seed):
+    """8x8 blocks of black / white / mid-grey with sharp edges, plus a little noise: the widest activations a frame can give."""
+    rng = np.random.default_rng(seed)
+    lv = rng.choice(np.array([0, 128, 255]), size=((H + 7) // 8, (W + 7) // 8, 3))
+    f = np.repeat(np.repeat(lv, 8, 0), 8, 1)[:H, :W].astype(np.float64) + rng.normal(0, 3, (H, W, 3))
+    return np.clip(f, 0, 255).round().astype(np.uint8)
+
+
+@pytest.mark.parametrize("num_block,scale,H,W", [(6, 4, 48, 80), (23, 2, 40, 66)])
+def test_wide_range_conv5_forms_vs_oracle(hip_lib, monkeypatch, num_block, scale, H, W):
+    """conv5 weights without the 0.1 shrink of the synthetic recipe and high-contrast frames: the trunk runs at a wider dynamic
+    range, where the Winograd form's f16 input differences and once-rounded transformed weights would show first.  All three conv5
+    settings (1 = rdb1 / rdb2 Winograd, the default; 0 = direct; 2 = rdb3 too) against the fp32 oracle at the 1e-3 bar."""
+    sd = synthetic_rrdbnet_state(num_block, scale, seed=99, conv5_scale=1.0)
+    frame = _high_contrast_frame(H, W, seed=H * W)
+    outs = _c5_outputs(monkeypatch, sd, frame, num_block, scale, ["1", "0", "2"])
+    want = _oracle_rgb_f32(sd, frame, num_block, scale)
+    want_u8 = (np.clip(want, 0, 1) * 255.0).round().astype(np.uint8)[:, :, ::-1]
+    errs = {m: np.abs(rgb - want).max() for m, (rgb, _) in outs.items()}
+    print(f"wide range nb={num_block} x{scale} {H}x{W}: out range [{want.min():.2f}, {want.max():.2f}] std {want.std():.3f}; "
+          + ", ".join(f"c5_wino={m} {e:.2e}" for m, e in errs.items()))
+    for m, (rgb, u8) in outs.items():
+        assert errs[m] < 1e-3, (m, errs)
+        assert _psnr_u8(u8, want_u8) >= 60.0 and np.abs(u8.astype(int) - want_u8.astype(int)).max() <= 1, m
+
+
+@pytest.mark.parametrize("scale", [4, 2])
+def test_23_block_full_frame_1080p_vs_gpu_oracle(hip_lib, scale):
+    """The 23-block f16 network (every default: fused pairs, split trunk, Winograd conv5 of rdb1 / rdb2) on a whole 1920 x 1080 frame
+    - persistent workgroups walking far more than 256 tiles, the next-tile prefetch, the slide kernel's warm-up tiles, all at full
+    depth - against oracle/rrdbnet_ref.py run by torch in fp32 on the GPU (tf32 off), which is first certified against the CPU oracle
+    on a 48 x 48 crop (max-abs <= 1e-5).  Bars of test_rrdbnet_vs_oracle: max-abs < 1e-3 on the float output, PSNR >= 60 dB and <= 1 LSB on uint8."""
+    H, W = 1080, 1920
+    sd = synthetic_rrdbnet_state(23, scale, seed=1234)
+    frame = synthetic_frames(1, H, W, seed=1080)[0]
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    sd_gpu = {k: torch.from_numpy(v).cuda() for k, v in sd.items()}
+
+    def gpu_oracle(f, band):
+        """oracle/rrdbnet_ref.py's forward from its own building blocks, the tail (nearest x2 + conv twice, conv_hr, conv_last) in bands
+        of `band` feature rows plus a 4-row halo: torch's fp32 conv on the whole 8.5 GB tail tensor of a 1080p frame returned wrong
+        rows (tests/test_conv_split_wino_gpu.py::test_winograd_store_form_at_8k), a band never reaches that size."""
+        x = torch.from_numpy(f[:, :, ::-1].astype(np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0).cuda()
+        if scale == 2 and (x.shape[2] % 2 or x.shape[3] % 2):
+            x = torch.nn.functional.pad(x, (0, x.shape[3] % 2, 0, x.shape[2] % 2), "reflect")
+        up = lambda t: torch.nn.functional.interpolate(t, scale_factor=2, mode="nearest")
+        with torch.no_grad():
+            feat = ref._conv(sd_gpu, "conv_first", torch.nn.functional.pixel_unshuffle(x, 2) if scale == 2 else x)
+            body = feat
+            for i in range(23):
+                body = ref.rrdb_forward(sd_gpu, f"body.{i}", body)
+            feat = feat + ref._conv(sd_gpu, "conv_body", body)
+            rows = []
+            for r0 in range(0, feat.shape[2], band):
+                r1 = min(r0 + band, feat.shape[2])
+                a, b = max(r0 - 4, 0), min(r1 + 4, feat.shape[2])
+                t = ref._lrelu(ref._conv(sd_gpu, "conv_up1", up(feat[:, :, a:b])))
+                t = ref._lrelu(ref._conv(sd_gpu, "conv_up2", up(t)))
+                t = ref._conv(sd_gpu, "conv_last", ref._lrelu(ref._conv(sd_gpu, "conv_hr", t)))
+                rows.append(t[:, :, 4 * (r0 - a):4 * (r1 - a)].cpu())
+            y = torch.cat(rows, 2)[:, :, :f.shape[0] * scale, :f.shape[1] * scale]
+        return y.squeeze(0).permute(1, 2, 0).numpy()
+
+    crop = np.ascontiguousarray(frame[500:548, 900:948])
+    cert = np.abs(gpu_oracle(crop, 5) - _oracle_rgb_f32(sd, crop, 23, scale)).max()   # several bands: the banding is certified too
+    assert cert <= 1e-5, cert
+    t0 = time.time()
+    want = gpu_oracle(frame, 135)
+    t_oracle = time.time() - t0
+    torch.cuda.empty_cache()
+    eng = R.RRDBNetEngine(23, scale, "f16")
+    eng.load_state_dict(sd)
+    rgb, u8 = _gpu_rgb_f32(eng, frame)
+    eng.close()
+    err = np.abs(rgb - want)
+    want_u8 = (np.clip(want, 0, 1) * 255.0).round().astype(np.uint8)[:, :, ::-1]
+    psnr = _psnr_u8(u8, want_u8)
+    lsb = np.abs(u8.astype(int) - want_u8.astype(int)).max()
+    print(f"23 blocks x{scale} 1920x1080: max-abs {err.max():.2e} (mean {err.mean():.2e}), PSNR {psnr:.1f} dB, max {lsb} LSB; "
+          f"GPU oracle certified at {cert:.1e} on a 48x48 crop, {t_oracle:.1f} s for the frame")
+    assert rgb.shape == want.shape == (H * scale, W * scale, 3)
+    assert err.max() < 1e-3
+    assert psnr >= 60.0 and lsb <= 1

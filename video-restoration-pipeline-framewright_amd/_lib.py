@@ -41,6 +41,7 @@ EXPORTS = [
     "fw_layernorm_nhwc", "fw_pack_pointwise", "fw_pointwise_nhwc", "fw_dwconv3x3_nhwc", "fw_attn_workspace_floats",
     "fw_attn_matrix", "fw_attn_apply", "fw_attn_pack", "fw_attn_proj_pack", "fw_pixel_shuffle2_f32", "fw_copy_channels_f32", "fw_f32_to_planar", "fw_tap_post_u8",
     "fw_flow_accumulate_u8", "fw_flow_accumulate_finish_u8", "fw_resize_lanczos4_u8", "fw_resize_linear_u8", "fw_face_paste_u8", "fw_grain_addback_u8", "fw_attn_softmax_rows", "fw_pack_pointwise_transposed", "fw_attn_qk_scratch_elems", "fw_attn_matrix_mfma",
+    "fw_pack_conv3x3_wino", "fw_conv3x3_split_nhwc", "fw_conv3x3_wino_nhwc", "fw_conv3x3_wino_check_fields",
 ]
 
 
@@ -138,6 +139,15 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_pack_conv_up2x_phase.argtypes = [i32, vp, vp]
     lib.fw_conv_up2x_phase_nhwc.restype = i32
     lib.fw_conv_up2x_phase_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, vp, vp, i32, vp, i32, C.c_long, vp]
+    lib.fw_pack_conv3x3_wino.restype = sz
+    lib.fw_pack_conv3x3_wino.argtypes = [i32, vp, i32, i32, i32, vp]
+    lib.fw_conv3x3_split_nhwc.restype = i32
+    lib.fw_conv3x3_split_nhwc.argtypes = [i32, i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, f32, f32, i32, C.POINTER(C.c_long),
+                                          C.POINTER(f32), i32, vp, vp, i32, C.c_long, i32, vp]
+    lib.fw_conv3x3_wino_nhwc.restype = i32
+    lib.fw_conv3x3_wino_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, i32, vp, i32, C.c_long, i32, vp]
+    lib.fw_conv3x3_wino_check_fields.restype = i32
+    lib.fw_conv3x3_wino_check_fields.argtypes = [C.POINTER(i32), i32]
     lib.fw_conv3x3_pair_nhwc.restype = i32
     lib.fw_conv3x3_pair_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.fw_u8_to_rgb_f32.restype = i32

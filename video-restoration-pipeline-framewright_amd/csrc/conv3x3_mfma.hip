@@ -589,6 +589,8 @@ void launch_conv3x3(DType dt, int cout_tiles, ConvEpilogue epi, const ConvParams
         for (int i = 0; i < p.n_id; ++i)
             if (operand_to_f32(dt, f32_to_operand(dt, p.id_scale[i])) != p.id_scale[i])
                 throw Error(1, "conv3x3: identity scale not representable in the operand type");
+        if (operand_to_f32(dt, f32_to_operand(dt, p.in_id_scale)) != p.in_id_scale)
+            throw Error(1, "conv3x3: in_id_scale not representable in the operand type");
     }
     if (dt == DT_BF16)
         launch_typed<__bf16>(cout_tiles, epi, p, stream);

@@ -19,6 +19,12 @@
 // Residuals: the conv's own input chunks 0, 1 (x hi) come from the raw centre fragments while they are in registers, residual planes from
 // HBM as in the direct kernel; a pixel of the pair's first / second column enters frequency 0 with + s I / frequency 3 with - s I
 // (y(2j) takes + m0, y(2j + 1) takes - m3).  The bias sits in m1, which both outputs take with + 1.
+//
+// f16 domain of V: d0 - d2, d1 + d2, d2 - d1 and d1 - d3 are formed in f16, so they overflow where the direct form does not.  The form is
+// finite for every input with |x| <= 32752 (65504 / 2: two such values sum to at most 65504, the largest finite f16; the next f16,
+// 32768, gives 32752 + 32768 = 65520, which rounds to inf).  The trunk of a trained RRDBNet stays orders of magnitude inside it.
+// tests/test_conv_split_wino_gpu.py runs the kernel at that limit and pins it to a float64 emulation of these rounding points
+// (oracle/winograd_ref.py).
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -419,12 +425,43 @@ size_t pack_conv3x3_wino_weights(DType dt, const float* w, int cout, int cin, in
     return n;
 }
 
+// The fields of ConvParams this kernel does not implement are rejected, not ignored: a dispatch that hands it one of them (IFNet's
+// post_act, a per-channel scale, fp32 side buffers, output-channel groups) must fail loudly instead of dropping the term.  f32_native is
+// not among them: it only describes the fp32 side buffers, which are rejected themselves.  Host only (no device call): the launchers run
+// it before they touch the device, and fw_conv3x3_wino_check_fields exercises it field by field.
+void check_conv3x3_wino(const ConvParams& p, bool split) {
+    if (p.H <= 0 || p.W <= 0 || p.cin_chunks <= 0 || p.upsample2x || !p.out || p.in_cstride < 32 || (p.in_cstride & 7) || (p.out_cstride & 7) ||
+        (p.out_coff & 7))
+        throw Error(1, "conv3x3_wino: bad problem");
+    if (p.in_pstride < 32 || (p.in_pstride & 7) || (p.in_pstride == 32 && p.in_cstride < 32 * p.cin_chunks && (long)p.H * p.W > 1))
+        throw Error(1, "conv3x3_wino: bad input channel/plane stride");
+    if (p.out_pstride < 32 || (p.out_pstride & 7)) throw Error(1, "conv3x3_wino: bad output plane stride");
+    if (p.post_act) throw Error(1, "conv3x3_wino: post_act is not implemented");
+    if (p.chan_scale) throw Error(1, "conv3x3_wino: chan_scale is not implemented");
+    if (p.res1 || p.res2) throw Error(1, "conv3x3_wino: fp32 residuals (res1 / res2) are not implemented");
+    if (p.out_f32) throw Error(1, "conv3x3_wino: the fp32 output copy (out_f32) is not implemented");
+    if (p.n_groups > 1) throw Error(1, "conv3x3_wino: output-channel groups (n_groups > 1) are not implemented");
+    if (split) {
+        if (p.act != 0) throw Error(1, "conv3x3_wino: no activation in the split-trunk form");
+        if (p.n_id < 0 || p.n_id > 6 || p.n_id > p.cin_chunks) throw Error(1, "conv3x3_wino: bad number of residual planes (n_id)");
+        // residual planes are addressed with 32-bit byte offsets from their base
+        if (p.n_id > 0 && (long)p.H * p.W * p.in_cstride * 2 > 0xffffffffL) throw Error(1, "conv3x3_wino: residual planes larger than 4 GiB");
+        // the identity terms enter the MFMAs as f16 A fragments: a scale that f16 rounds would silently change the residual
+        if (operand_to_f32(DT_F16, f32_to_operand(DT_F16, p.in_id_scale)) != p.in_id_scale)
+            throw Error(1, "conv3x3_wino: in_id_scale not representable in f16");
+        for (int i = 0; i < p.n_id; ++i)
+            if (operand_to_f32(DT_F16, f32_to_operand(DT_F16, p.id_scale[i])) != p.id_scale[i])
+                throw Error(1, "conv3x3_wino: identity scale not representable in f16");
+    } else {
+        if (p.act < 0 || p.act > 1) throw Error(1, "conv3x3_wino: act must be 0 or 1 (PReLU is not implemented)");
+        if (p.n_id || p.out_lo) throw Error(1, "conv3x3_wino: residual planes / lo planes need the split-trunk form");
+    }
+}
+
 void launch_conv3x3_wino_split(const ConvParams& p_in, hipStream_t stream) {
+    check_conv3x3_wino(p_in, true);
     ConvParams p = p_in;
     p.zeros = conv_zero_page();
-    if (p.H <= 0 || p.W <= 0 || p.cin_chunks <= 0 || p.upsample2x || !p.out || p.n_id < 0 || p.n_id > 6 || p.n_id > p.cin_chunks || p.in_cstride < 32 ||
-        (p.in_cstride & 7) || (p.out_cstride & 7) || (p.out_coff & 7))
-        throw Error(1, "conv3x3_wino: bad problem");
     const int tiles = ((p.W + TILE_W - 1) / TILE_W) * ((p.H + TILE_H - 1) / TILE_H);
     const int cus = conv_num_cus();
     dim3 grid(tiles < cus ? tiles : cus), block(64 * NWAVES);
@@ -437,13 +474,9 @@ void launch_conv3x3_wino_split(const ConvParams& p_in, hipStream_t stream) {
 
 // lrelu(conv3x3 + bias) (act = 1) or conv3x3 + bias, 64 output channels, typed planes out: the ConvParams of launch_conv3x3(dt, 2, EPI_STORE, ...)
 void launch_conv3x3_wino_store(const ConvParams& p_in, hipStream_t stream) {
+    check_conv3x3_wino(p_in, false);
     ConvParams p = p_in;
     p.zeros = conv_zero_page();
-    p.n_id = 0;
-    p.out_lo = nullptr;
-    if (p.H <= 0 || p.W <= 0 || p.cin_chunks <= 0 || p.upsample2x || !p.out || p.in_cstride < 32 || (p.in_cstride & 7) || (p.out_cstride & 7) || (p.out_coff & 7) ||
-        p.out_f32 || p.act > 1)
-        throw Error(1, "conv3x3_wino: bad problem");
     const int tiles = ((p.W + TILE_W - 1) / TILE_W) * ((p.H + TILE_H - 1) / TILE_H);
     const int cus = conv_num_cus();
     dim3 grid(tiles < cus ? tiles : cus), block(64 * NWAVES);

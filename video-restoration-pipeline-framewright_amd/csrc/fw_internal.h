@@ -103,6 +103,8 @@ struct ConvPairParams {
 size_t pack_conv3x3_wino_weights(DType dt, const float* w, int cout, int cin, int cin_chunks, uint16_t* dst);
 void launch_conv3x3_wino_split(const ConvParams& p, hipStream_t stream);
 void launch_conv3x3_wino_store(const ConvParams& p, hipStream_t stream);   // act(conv + bias) -> typed planes (EPI_STORE, 64 channels)
+// throws Error(1, ...) for every ConvParams field the Winograd kernels do not implement (host only; both launchers run it first)
+void check_conv3x3_wino(const ConvParams& p, bool split);
 void launch_conv3x3_pair(DType dt, const ConvPairParams& p, hipStream_t stream);
 const void* conv_zero_page();  // 256 B of zeros on the current device
 

@@ -528,8 +528,9 @@ extern "C" {
 
 const char* fw_last_error(void) { return fw::last_error_ref().c_str(); }
 
-int fw_abi_version(void) { return 3; }  // 2: + upscale_u16, resize_lanczos4, grain_addback, attention (softmax rows, transposed pack, MFMA Gram)
+int fw_abi_version(void) { return 4; }  // 2: + upscale_u16, resize_lanczos4, grain_addback, attention (softmax rows, transposed pack, MFMA Gram)
                                          // 3 (round 2, additive): + fw_ifnet_*, fw_restormer_*, fw_srvgg_*, fw_unsharp_mask_u8, fw_preserve_edges_*, fw_attn_proj_pack
+                                         // 4 (additive): + fw_pack_conv3x3_wino, fw_conv3x3_split_nhwc, fw_conv3x3_wino_nhwc, fw_conv3x3_wino_check_fields
 
 int fw_device_count(void) {
     int n = 0;
@@ -883,6 +884,135 @@ int fw_conv3x3_nhwc_ex(int dtype, const void* x, int in_cstride, long in_plane_s
         p.f32_coff = f32_coff;
         launch_conv3x3((DType)dtype, cout_tiles, res1 ? EPI_RESIDUAL : EPI_STORE, p, (hipStream_t)stream);
     });
+}
+
+size_t fw_pack_conv3x3_wino(int dtype, const float* weight, int cout, int cin, int cin_chunks, uint16_t* dst) {
+    if (dtype != FW_DTYPE_F16) return 0;   // the Winograd kernel is f16 only
+    if (cout < 1 || cin < 1 || cin_chunks < 1 || cout > 64 || cin > 32 * cin_chunks) return 0;
+    if (dst && !weight) return 0;
+    return pack_conv3x3_wino_weights(DT_F16, weight, cout, cin, cin_chunks, dst);
+}
+
+int fw_conv3x3_split_nhwc(int dtype, int winograd, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int H, int W,
+                          const void* packed_weight, const float* bias, float s1, float in_id_scale, int n_id, const long* chunk_off,
+                          const float* id_scale, int post_act, void* out, void* out_lo, int out_cstride, long out_plane_stride,
+                          int out_coff, void* stream) {
+    if (!x || !packed_weight || !bias || !out) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: NULL argument");
+    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: bad dtype");
+    if (winograd != 0 && winograd != 1) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: winograd must be 0 or 1");
+    if (winograd && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: the Winograd form is f16 only");
+    if (n_id < 0 || n_id > 6) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: n_id must be in [0, 6]");
+    if (n_id > 0 && (!chunk_off || !id_scale)) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: residual planes need chunk_off and id_scale");
+    return guarded([&] {
+        ConvParams p{};
+        p.in = x;
+        p.in_cstride = in_cstride;
+        p.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
+        p.cin_chunks = cin_chunks;
+        p.H = H;
+        p.W = W;
+        p.wpk = packed_weight;
+        p.bias = bias;
+        p.s1 = s1;
+        p.s2 = 1.f;
+        p.in_id_scale = in_id_scale;
+        p.n_id = n_id;
+        for (int i = 0; i < n_id; ++i) {
+            p.chunk_off[i] = chunk_off[i];
+            p.id_scale[i] = id_scale[i];
+        }
+        p.post_act = post_act;
+        p.out = out;
+        p.out_lo = out_lo;
+        p.out_cstride = out_cstride;
+        p.out_pstride = out_plane_stride > 0 ? out_plane_stride : 32;
+        p.out_coff = out_coff;
+        if (winograd)
+            launch_conv3x3_wino_split(p, (hipStream_t)stream);
+        else
+            launch_conv3x3((DType)dtype, 2, EPI_RESIDUAL_SPLIT, p, (hipStream_t)stream);
+    });
+}
+
+int fw_conv3x3_wino_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int H, int W,
+                         const void* packed_weight, const float* bias, int act_lrelu, void* out, int out_cstride, long out_plane_stride,
+                         int out_coff, void* stream) {
+    if (!x || !packed_weight || !bias || !out) return fail(FW_ERR_INVALID, "fw_conv3x3_wino_nhwc: NULL argument");
+    if (dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_wino_nhwc: the Winograd form is f16 only");
+    if (act_lrelu != 0 && act_lrelu != 1) return fail(FW_ERR_INVALID, "fw_conv3x3_wino_nhwc: act_lrelu must be 0 or 1");
+    return guarded([&] {
+        ConvParams p{};
+        p.in = x;
+        p.in_cstride = in_cstride;
+        p.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
+        p.cin_chunks = cin_chunks;
+        p.H = H;
+        p.W = W;
+        p.wpk = packed_weight;
+        p.bias = bias;
+        p.act = act_lrelu;
+        p.out = out;
+        p.out_cstride = out_cstride;
+        p.out_pstride = out_plane_stride > 0 ? out_plane_stride : 32;
+        p.out_coff = out_coff;
+        launch_conv3x3_wino_store(p, (hipStream_t)stream);
+    });
+}
+
+int fw_conv3x3_wino_check_fields(int* codes, int n) {
+    // one valid problem per form, then one field at a time set to what the Winograd kernels do not implement (no launch, no device call)
+    static const float one = 1.f;
+    static char dummy[16];
+    ConvParams ok{};
+    ok.H = ok.W = 16;
+    ok.cin_chunks = 2;
+    ok.in_cstride = 32;
+    ok.in_pstride = 16 * 16 * 32;
+    ok.out = dummy;
+    ok.out_cstride = 32;
+    ok.out_pstride = 16 * 16 * 32;
+    ok.s1 = 0.2f;
+    ok.in_id_scale = 5.f;
+    ok.n_id = 2;
+    ok.id_scale[0] = ok.id_scale[1] = 5.f;
+    ok.f32_native = 1;   // set for every conv of the engine; meaningless without fp32 side buffers, accepted
+    struct Case { bool split; void (*set)(ConvParams&); };
+    static const Case cases[] = {
+        {true, [](ConvParams& p) { p.post_act = 1; }},
+        {true, [](ConvParams& p) { p.chan_scale = &one; }},
+        {true, [](ConvParams& p) { p.res1 = &one; }},
+        {true, [](ConvParams& p) { p.res2 = &one; }},
+        {true, [](ConvParams& p) { p.out_f32 = const_cast<float*>(&one); }},
+        {true, [](ConvParams& p) { p.n_groups = 2; }},
+        {true, [](ConvParams& p) { p.act = 1; }},
+        {true, [](ConvParams& p) { p.in_id_scale = 0.1f; }},
+        {true, [](ConvParams& p) { p.id_scale[1] = 0.1f; }},
+        {false, [](ConvParams& p) { p.out_f32 = const_cast<float*>(&one); }},
+        {false, [](ConvParams& p) { p.n_groups = 2; }},
+        {false, [](ConvParams& p) { p.chan_scale = &one; }},
+        {false, [](ConvParams& p) { p.post_act = 1; }},
+        {false, [](ConvParams& p) { p.res1 = &one; }},
+        {false, [](ConvParams& p) { p.act = 2; }},
+        {false, [](ConvParams& p) { p.out_lo = dummy; }},
+    };
+    const int nc = (int)(sizeof(cases) / sizeof(cases[0]));
+    ConvParams st = ok;
+    st.n_id = 0;
+    st.in_id_scale = 0.f;
+    st.act = 1;
+    try {   // the unmodified problems pass
+        check_conv3x3_wino(ok, true);
+        check_conv3x3_wino(st, false);
+    } catch (const fw::Error& e) {
+        fail(FW_ERR_INTERNAL, std::string("fw_conv3x3_wino_check_fields: a valid problem was rejected: ") + e.what());
+        return -1;
+    }
+    for (int i = 0; i < nc && i < n; ++i) {
+        ConvParams p = cases[i].split ? ok : st;
+        cases[i].set(p);
+        codes[i] = guarded([&] { check_conv3x3_wino(p, cases[i].split); });
+    }
+    return nc;
 }
 
 size_t fw_pack_conv_up2x_phase(int dtype, const float* weight, uint16_t* dst) {

@@ -44,17 +44,18 @@ def rrdbnet_conv_shapes(num_block: int, scale: int, num_feat: int = 64, grow: in
 
 
 def synthetic_rrdbnet_state(num_block: int, scale: int, seed: int = 1234, num_feat: int = 64, grow: int = 32,
-                            image_range: bool = True) -> Dict[str, np.ndarray]:
-    """Seeded state-dict (numpy fp32 arrays) with BasicSR key names."""
+                            image_range: bool = True, conv5_scale: float = 0.1) -> Dict[str, np.ndarray]:
+    """Seeded state-dict (numpy fp32 arrays) with BasicSR key names.  conv5_scale: the factor on every dense block's conv5
+    (1.0 = PyTorch's default initialisation unshrunk: a wider dynamic range through the trunk)."""
     rng = np.random.default_rng(seed)
     sd: Dict[str, np.ndarray] = {}
     for key, cout, cin in rrdbnet_conv_shapes(num_block, scale, num_feat, grow):
         bound = 1.0 / np.sqrt(cin * 9)
         w = rng.uniform(-bound, bound, size=(cout, cin, 3, 3)).astype(np.float32)
         b = rng.uniform(-bound, bound, size=(cout,)).astype(np.float32)
-        if key.endswith(".conv5"):
-            w *= np.float32(0.1)
-            b *= np.float32(0.1)
+        if key.endswith(".conv5") and conv5_scale != 1.0:
+            w *= np.float32(conv5_scale)
+            b *= np.float32(conv5_scale)
         if key == "conv_last" and image_range:
             w *= np.float32(0.25)
             b = b * np.float32(0.25) + np.float32(0.5)
