@@ -416,6 +416,33 @@ def test_hipgraph_capture_gives_identical_frames(hip_lib, monkeypatch):
     print(f"48x64 x4, 3 blocks: direct {outs['0'][1]:.3f} ms, graph {outs['1'][1]:.3f} ms")
 
 
+def test_profile_counters_count_launches_and_flops_and_leave_the_frame_alone(hip_lib):
+    """fw_rrdbnet_profile_enable / _read (bench.py --full builds its roofline from them): every conv launch of a forward is timed
+    between two events and its algorithmic FLOPs are added up.  A read returns and resets the counters; the per-launch FLOP counts
+    are integers far below 2^53, so the double sums of two forwards are exactly twice those of one; with profiling off nothing
+    is counted; and the frame does not depend on whether its launches were timed."""
+    sd = synthetic_rrdbnet_state(3, 4, seed=8)
+    frame = synthetic_frames(1, 48, 64, seed=3)[0]
+    eng = R.RRDBNetEngine(3, 4, "f16")
+    eng.load_state_dict(sd)
+    plain = eng.upscale(frame)
+    eng.profile_enable(True)
+    timed = eng.upscale(frame)
+    launches, ms, flops = eng.profile_read()
+    print(f"3 blocks x4 48x64: {launches} timed launches, {ms:.3f} ms, {flops / 1e9:.3f} GFLOP")
+    assert launches > 0 and ms > 0 and flops > 0
+    assert eng.profile_read() == (0, 0.0, 0.0)               # a read resets the counters
+    eng.upscale(frame)
+    eng.upscale(frame)
+    launches2, ms2, flops2 = eng.profile_read()
+    assert launches2 == 2 * launches and flops2 == 2 * flops and ms2 > 0
+    eng.profile_enable(False)
+    off = eng.upscale(frame)
+    assert eng.profile_read() == (0, 0.0, 0.0)
+    assert np.array_equal(timed, plain) and np.array_equal(off, plain)
+    eng.close()
+
+
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_sliding_window_pair_kernel_equals_ring_kernel_at_1080p(hip_lib, monkeypatch, dtype):
     """Three independent implementations of the fused conv pair (conv3x3_pair_slide32.hip, conv3x3_pair_slide.hip - the

@@ -19,22 +19,11 @@
 #include <set>
 #include <string>
 #include <vector>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "engine_common.h"
 
 using namespace fw;
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
 
 struct Conv {
     DevBuf w, b;
@@ -43,18 +32,6 @@ struct Conv {
 struct Attn {
     DevBuf w[3], b[3], gamma;   // query, key, value
     int tiles[3] = {0, 0, 0};
-};
-
-struct Arena {
-    char* base = nullptr;
-    size_t top = 0, peak = 0;
-    bool plan = false;
-    void* take(size_t bytes) {
-        const size_t at = top;
-        top += (bytes + 255) / 256 * 256;
-        if (top > peak) peak = top;
-        return base + at;
-    }
 };
 
 }  // namespace
@@ -76,29 +53,6 @@ struct fw_aesrgan {
 
 namespace {
 
-int fail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
-}
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
-void upload(DevBuf& b, const void* src, size_t bytes) {
-    b.release();
-    FW_HIP_CHECK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    FW_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-}
 void chk(int status) {
     if (status != FW_OK) throw Error(status, fw::last_error_ref());
 }
@@ -351,12 +305,7 @@ int fw_aesrgan_forward_rgb(fw_aesrgan* n, const float* x_rgb, int H, int W, floa
         Arena P;
         P.plan = true;
         forward(n, P, nullptr, H, W, nullptr, nullptr);
-        if (n->ws.bytes < P.peak) {
-            FW_HIP_CHECK(hipDeviceSynchronize());
-            n->ws.release();
-            FW_HIP_CHECK(hipMalloc(&n->ws.p, P.peak));
-            n->ws.bytes = P.peak;
-        }
+        ensure_workspace(n->ws, P.peak);
         Arena A;
         A.base = (char*)n->ws.p;
         StreamOrder::Scope in_order(n->order, (hipStream_t)stream);

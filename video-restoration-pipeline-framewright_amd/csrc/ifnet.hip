@@ -19,8 +19,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "engine_common.h"
 
 using namespace fw;
 
@@ -32,23 +31,6 @@ constexpr int SC[NBLK] = {8, 4, 2, 1};
 constexpr int NRES = 8;
 
 int pad_to(int n, int m) { return (n + m - 1) / m * m; }
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-void upload(DevBuf& b, const void* src, size_t bytes) {
-    b.release();
-    FW_HIP_CHECK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    FW_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-}
 
 // One 3x3 convolution [cout_pad][cin_pad] split into launches of 64 (or a last 32) output channels.
 struct Conv {
@@ -197,36 +179,10 @@ struct fw_ifnet {
     bool narrow_groups = true;  // 32-channel output groups for the conv chains of blocks with few tiles (FW_IFNET_NARROW=0: A/B;
     long narrow_below = 128;    //   FW_IFNET_NARROW_BELOW: below that many 64-channel workgroups per launch)
     bool warmed = false;
-    struct GraphEntry {
-        int H, W;
-        float t;
-        const void *a, *b;
-        void *out, *rgb;
-        hipGraph_t graph;
-        hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> graphs;
+    GraphCache graphs;
 };
 
 namespace {
-
-int fail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
-}
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
 
 size_t esz(DType) { return 2; }
 
@@ -417,14 +373,6 @@ void forward(fw_ifnet* n, const uint8_t* d0, const uint8_t* d1, int H, int W, fl
     FW_HIP_CHECK(hipGetLastError());
 }
 
-void drop_graphs(fw_ifnet* n) {
-    for (auto& g : n->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    n->graphs.clear();
-}
-
 void need(size_t got, size_t want, const std::string& key) {
     if (got != want)
         throw Error(FW_ERR_INVALID, "fw_ifnet_set_tensor: '" + key + "' has " + std::to_string(got) + " elements, expected " + std::to_string(want));
@@ -507,7 +455,7 @@ int fw_ifnet_finalize(fw_ifnet* n) {
             if (n->blk[i].have != BLOCK_ALL)
                 throw Error(FW_ERR_INVALID, "fw_ifnet_finalize: block" + std::to_string(i) + " is missing tensors");
         DevGuard dg(n->device);
-        drop_graphs(n);
+        n->graphs.clear();   // captured forwards hold the addresses of the weights being replaced
         for (int i = 0; i < NBLK; ++i) {
             Block& b = n->blk[i];
             const int c = b.c, cin = b.cin;
@@ -587,13 +535,7 @@ int fw_ifnet_interp_u8(fw_ifnet* n, const uint8_t* frame0, const uint8_t* frame1
         hipStream_t st = (hipStream_t)stream;
         StreamOrder::Scope in_order(n->order, st);
         const Plan pl = make_plan(H, W);
-        if (n->ws.bytes < pl.total) {
-            FW_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(n);
-            n->ws.release();
-            FW_HIP_CHECK(hipMalloc(&n->ws.p, pl.total));
-            n->ws.bytes = pl.total;
-        }
+        ensure_workspace(n->ws, pl.total, &n->graphs);
         char* ws = (char*)n->ws.p;
         const size_t bytes = (size_t)H * W * 3;
         const uint8_t *d0 = frame0, *d1 = frame1;
@@ -610,38 +552,10 @@ int fw_ifnet_interp_u8(fw_ifnet* n, const uint8_t* frame0, const uint8_t* frame1
         if (!graphed) {
             forward(n, d0, d1, H, W, timestep, d_out, out_rgb_f32, st);
         } else {
-            fw_ifnet::GraphEntry* hit = nullptr;
-            for (auto& g : n->graphs)
-                if (g.H == H && g.W == W && g.t == timestep && g.a == d0 && g.b == d1 && g.out == d_out && g.rgb == out_rgb_f32) hit = &g;
-            if (!hit) {
-                if (n->graphs.size() >= 16) drop_graphs(n);
-                (void)conv_zero_page();   // its first use allocates: not inside a capture
-                hipStream_t cs = nullptr;
-                FW_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-                fw_ifnet::GraphEntry e{H, W, timestep, d0, d1, d_out, out_rgb_f32, nullptr, nullptr};
-                hipError_t err = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-                if (err == hipSuccess) {
-                    try {
-                        forward(n, d0, d1, H, W, timestep, d_out, out_rgb_f32, cs);
-                    } catch (...) {
-                        hipGraph_t junk = nullptr;
-                        (void)hipStreamEndCapture(cs, &junk);
-                        if (junk) (void)hipGraphDestroy(junk);
-                        (void)hipStreamDestroy(cs);
-                        throw;
-                    }
-                    err = hipStreamEndCapture(cs, &e.graph);
-                }
-                if (err == hipSuccess) err = hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0);
-                (void)hipStreamDestroy(cs);
-                if (err != hipSuccess) {
-                    if (e.graph) (void)hipGraphDestroy(e.graph);
-                    FW_HIP_CHECK(err);
-                }
-                n->graphs.push_back(e);
-                hit = &n->graphs.back();
-            }
-            FW_HIP_CHECK(hipGraphLaunch(hit->exec, st));
+            uint32_t t_bits;   // the timestep is a kernel argument of the captured launches: keyed by its bits
+            memcpy(&t_bits, &timestep, sizeof t_bits);
+            const GraphCache::Key key = {(uint64_t)H, (uint64_t)W, t_bits, (uint64_t)d0, (uint64_t)d1, (uint64_t)d_out, (uint64_t)out_rgb_f32};
+            n->graphs.launch(key, st, [&](hipStream_t cs) { forward(n, d0, d1, H, W, timestep, d_out, out_rgb_f32, cs); });
         }
         if (out_bgr && out_loc == FW_HOST) {
             FW_HIP_CHECK(hipMemcpyAsync(out_bgr, d_out, bytes, hipMemcpyDeviceToHost, st));
@@ -657,7 +571,7 @@ int fw_ifnet_destroy(fw_ifnet* n) {
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(n->device);
     (void)hipDeviceSynchronize();
-    drop_graphs(n);
+    n->graphs.clear();
     for (auto& b : n->blk) {
         b.conv00.release();
         b.conv01.release();

@@ -13,22 +13,11 @@
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "engine_common.h"
 
 using namespace fw;
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
 
 struct Block {
     int c = 0;
@@ -76,50 +65,10 @@ struct fw_nafnet {
     // sequence bakes in (FW_NAF_GRAPH=1; off by default: a caller that hands over fresh buffers every frame would re-capture every frame)
     int graph_mode = 0;
     bool warmed = false;
-    struct GraphEntry {
-        int H, W;
-        const void* in;
-        void *out, *rgb;
-        hipGraph_t graph;
-        hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> graphs;
+    GraphCache graphs;
 };
 
 namespace {
-
-int fail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
-}
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
-
-void drop_graphs(fw_nafnet* n) {
-    for (auto& g : n->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    n->graphs.clear();
-}
-
-void upload(DevBuf& b, const void* src, size_t bytes) {
-    b.release();
-    FW_HIP_CHECK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    FW_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-}
 
 void upload_pointwise(DType dt, DevBuf& b, const float* w, int cout, int K) {
     std::vector<uint16_t> pk(pack_pointwise_weights(dt, nullptr, cout, K, nullptr));
@@ -435,7 +384,7 @@ int fw_nafnet_set_tensor(fw_nafnet* n, const char* key_c, const float* data, siz
         DevGuard dg(n->device);
         if (!n->graphs.empty()) {   // captured forwards hold the addresses of the weights being replaced
             FW_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(n);
+            n->graphs.clear();
         }
         const std::string key(key_c);
         const int w = n->width;
@@ -531,13 +480,7 @@ int fw_nafnet_denoise_u8(fw_nafnet* n, const uint8_t* in_bgr, int in_loc, int H,
         hipStream_t st = (hipStream_t)stream;
         StreamOrder::Scope in_order(n->order, st);
         const Plan pl = make_plan(n, H, W);
-        if (n->ws.bytes < pl.total) {
-            FW_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(n);
-            n->ws.release();
-            FW_HIP_CHECK(hipMalloc(&n->ws.p, pl.total));
-            n->ws.bytes = pl.total;
-        }
+        ensure_workspace(n->ws, pl.total, &n->graphs);
         const size_t bytes = (size_t)H * W * 3;
         const uint8_t* d_in = in_bgr;
         if (in_loc == FW_HOST) {
@@ -552,38 +495,8 @@ int fw_nafnet_denoise_u8(fw_nafnet* n, const uint8_t* in_bgr, int in_loc, int H,
         if (!graphed) {
             forward(n, d_in, H, W, d_out, out_rgb_f32, st);
         } else {
-            fw_nafnet::GraphEntry* hit = nullptr;
-            for (auto& g : n->graphs)
-                if (g.H == H && g.W == W && g.in == d_in && g.out == d_out && g.rgb == out_rgb_f32) hit = &g;
-            if (!hit) {
-                if (n->graphs.size() >= 16) drop_graphs(n);
-                (void)conv_zero_page();   // its first use allocates: not inside a capture
-                hipStream_t cs = nullptr;
-                FW_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-                fw_nafnet::GraphEntry e{H, W, d_in, d_out, out_rgb_f32, nullptr, nullptr};
-                hipError_t err = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-                if (err == hipSuccess) {
-                    try {
-                        forward(n, d_in, H, W, d_out, out_rgb_f32, cs);
-                    } catch (...) {
-                        hipGraph_t junk = nullptr;
-                        (void)hipStreamEndCapture(cs, &junk);
-                        if (junk) (void)hipGraphDestroy(junk);
-                        (void)hipStreamDestroy(cs);
-                        throw;
-                    }
-                    err = hipStreamEndCapture(cs, &e.graph);
-                }
-                if (err == hipSuccess) err = hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0);
-                (void)hipStreamDestroy(cs);
-                if (err != hipSuccess) {
-                    if (e.graph) (void)hipGraphDestroy(e.graph);
-                    FW_HIP_CHECK(err);
-                }
-                n->graphs.push_back(e);
-                hit = &n->graphs.back();
-            }
-            FW_HIP_CHECK(hipGraphLaunch(hit->exec, st));
+            const GraphCache::Key key = {(uint64_t)H, (uint64_t)W, (uint64_t)d_in, (uint64_t)d_out, (uint64_t)out_rgb_f32};
+            n->graphs.launch(key, st, [&](hipStream_t cs) { forward(n, d_in, H, W, d_out, out_rgb_f32, cs); });
         }
         if (out_bgr && out_loc == FW_HOST) {
             FW_HIP_CHECK(hipMemcpyAsync(out_bgr, d_out, bytes, hipMemcpyDeviceToHost, st));
@@ -697,7 +610,7 @@ int fw_nafnet_destroy(fw_nafnet* n) {
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(n->device);
     (void)hipDeviceSynchronize();
-    drop_graphs(n);
+    n->graphs.clear();
     auto free_block = [](Block& b) {
         for (DevBuf* d : {&b.n1w, &b.n1b, &b.n2w, &b.n2b, &b.beta, &b.gamma, &b.w1, &b.b1, &b.w3, &b.b3, &b.w4, &b.b4, &b.w5, &b.w1g, &b.w3g, &b.w4g, &b.w5g,
                           &b.b5, &b.wdw, &b.bdw, &b.wsca, &b.bsca, &b.front, &b.tail128})

@@ -22,8 +22,7 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "engine_common.h"
 
 using namespace fw;
 
@@ -33,23 +32,6 @@ int pad_to(int n, int m) { return (n + m - 1) / m * m; }
 // channels per pixel of the fp32 stream (and of every typed operand) at c real channels: whole 32-channel contraction chunks - 48 -> 64,
 // 96 / 192 / 384 as they are (round 2 padded to 64: a third more bytes per pixel at 96 channels, where 20 of the 44 blocks run)
 int stream_pad(int c) { return pad_to(c, 32); }
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-void upload(DevBuf& b, const void* src, size_t bytes) {
-    b.release();
-    FW_HIP_CHECK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    FW_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-}
 
 // [cout][k] fp32 -> packed pointwise fragments, cout padded to 32 and k to k_pad; returns the number of 32-channel tiles
 int upload_pointwise(DType dt, DevBuf& b, const float* w, int cout, int k, int k_pad) {
@@ -115,19 +97,6 @@ struct Stage {
     int n, c, heads;
 };
 
-// bump allocator over the engine's workspace; `plan` = dry run of the sequencing that only measures the peak
-struct Arena {
-    char* base = nullptr;
-    size_t top = 0, peak = 0;
-    bool plan = false;
-    void* take(size_t bytes) {
-        const size_t at = top;
-        top += (bytes + 255) / 256 * 256;
-        if (top > peak) peak = top;
-        return base + at;   // plan mode: base == nullptr, the pointer is never dereferenced or launched on
-    }
-};
-
 }  // namespace
 
 struct fw_restormer {
@@ -154,24 +123,6 @@ struct fw_restormer {
 };
 
 namespace {
-
-int fail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
-}
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
 
 // a building block failed: its message is already in fw_last_error()
 void chk(int status) {
@@ -581,12 +532,7 @@ int fw_restormer_denoise_u8(fw_restormer* n, const uint8_t* in_bgr, int in_loc, 
         P.plan = true;
         forward(n, P, nullptr, H, W, nullptr, nullptr, nullptr);
         const size_t total = 2 * frame + P.peak;
-        if (n->ws.bytes < total) {
-            FW_HIP_CHECK(hipDeviceSynchronize());
-            n->ws.release();
-            FW_HIP_CHECK(hipMalloc(&n->ws.p, total));
-            n->ws.bytes = total;
-        }
+        ensure_workspace(n->ws, total);
         char* base = (char*)n->ws.p;
         const uint8_t* d_in = in_bgr;
         if (in_loc == FW_HOST) {

@@ -13,8 +13,7 @@
 #include <memory>
 #include <cstdio>
 #include <cstdlib>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "engine_common.h"
 
 namespace fw {
 
@@ -25,11 +24,6 @@ struct ConvLayer {
     void* d_wphase = nullptr;   // conv_up1 / conv_up2: the same weights as four 2x2 phase convolutions (conv_up2x_phase.hip)
     void* d_wwino = nullptr;    // conv5 of a dense block, f16: the same weights as row-wise Winograd fragments (conv3x3_wino.hip)
     bool set = false;
-};
-
-struct Workspace {
-    char* base = nullptr;
-    size_t bytes = 0;
 };
 
 }  // namespace fw
@@ -52,7 +46,7 @@ struct fw_rrdbnet {
     std::mutex mu;
     ConvLayer conv_first, conv_body, conv_up1, conv_up2, conv_hr, conv_last;
     std::vector<ConvLayer> body;  // [num_block][3][5]
-    Workspace ws;
+    DevBuf ws;
     int fuse_mask = 3;       // bit 0: conv1+conv2, bit 1: conv3+conv4 (FW_RRDB_FUSE_MASK, for A/B runs)
     bool fuse_pairs = true;  // conv1+conv2 / conv3+conv4 in one kernel (FW_RRDB_FUSE_PAIRS=0 disables, for A/B runs)
     // residual trunk as typed hi + typed lo planes (EPI_RESIDUAL_SPLIT): the residual adds run on the matrix cores as
@@ -81,15 +75,7 @@ struct fw_rrdbnet {
     // FW_RRDB_GRAPH_MAX_PX.
     int graph_mode = 0;
     long graph_max_px = 512L * 512L;
-    struct GraphEntry {
-        int H, W, bits;
-        const void* in;
-        void* out;
-        float* rgb;
-        hipGraph_t graph;
-        hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> graphs;
+    GraphCache graphs;
     bool warmed = false;
     // profiling
     bool profile = false;
@@ -100,25 +86,6 @@ struct fw_rrdbnet {
 };
 
 namespace {
-
-int fail(int code, const std::string& msg) {
-    fw::last_error_ref() = msg;
-    return code;
-}
-
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -210,41 +177,35 @@ void free_layer(ConvLayer& l) {
 
 double conv_flops(const ConvLayer& l, size_t pixels) { return 2.0 * 9.0 * l.cin * l.cout * (double)pixels; }
 
+// Runs `launch` on `st`; with profiling on, between two events of the pool and with its algorithmic `flops` added to the count
+template <typename F>
+void timed(fw_rrdbnet* n, hipStream_t st, double flops, F&& launch) {
+    if (!n->profile) {
+        launch();
+        return;
+    }
+    if (n->ev_used + 2 > n->ev_pool.size()) {
+        size_t old = n->ev_pool.size();
+        n->ev_pool.resize(old + 1024);
+        for (size_t i = old; i < n->ev_pool.size(); ++i) FW_HIP_CHECK(hipEventCreate(&n->ev_pool[i]));
+    }
+    FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
+    launch();
+    FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
+    n->prof_flops += flops;
+    n->prof_stream = st;
+}
+
 void run_conv(fw_rrdbnet* n, const ConvLayer& l, ConvEpilogue epi, ConvParams p, hipStream_t st) {
     p.cin_chunks = l.chunks;
     p.wpk = l.d_w;
     p.bias = l.d_b;
-    if (n->profile) {
-        if (n->ev_used + 2 > n->ev_pool.size()) {
-            size_t old = n->ev_pool.size();
-            n->ev_pool.resize(old + 1024);
-            for (size_t i = old; i < n->ev_pool.size(); ++i) FW_HIP_CHECK(hipEventCreate(&n->ev_pool[i]));
-        }
-        FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-        launch_conv3x3(n->dt, l.ct, epi, p, st);
-        FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-        n->prof_flops += conv_flops(l, (size_t)p.H * p.W);
-        n->prof_stream = st;
-    } else {
-        launch_conv3x3(n->dt, l.ct, epi, p, st);
-    }
+    timed(n, st, conv_flops(l, (size_t)p.H * p.W), [&] { launch_conv3x3(n->dt, l.ct, epi, p, st); });
 }
 
 void run_pair(fw_rrdbnet* n, const ConvLayer& a, const ConvLayer& b, const ConvPairParams& q, hipStream_t st) {
-    if (n->profile) {
-        if (n->ev_used + 2 > n->ev_pool.size()) {
-            size_t old = n->ev_pool.size();
-            n->ev_pool.resize(old + 1024);
-            for (size_t i = old; i < n->ev_pool.size(); ++i) FW_HIP_CHECK(hipEventCreate(&n->ev_pool[i]));
-        }
-        FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-        launch_conv3x3_pair(n->dt, q, st);
-        FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-        n->prof_flops += conv_flops(a, (size_t)q.H * q.W) + conv_flops(b, (size_t)q.H * q.W);  // algorithmic, no recompute
-        n->prof_stream = st;
-    } else {
-        launch_conv3x3_pair(n->dt, q, st);
-    }
+    // algorithmic FLOPs, no recompute
+    timed(n, st, conv_flops(a, (size_t)q.H * q.W) + conv_flops(b, (size_t)q.H * q.W), [&] { launch_conv3x3_pair(n->dt, q, st); });
 }
 
 // bits = 8: d_in / d_out are uint8 BGR; bits = 16: uint16 BGR (range 65535)
@@ -252,7 +213,7 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     int Ht, Wt;
     trunk_size(n, H, W, &Ht, &Wt);
     const Plan pl = make_plan(n, H, W);
-    char* ws = n->ws.base;
+    char* ws = (char*)n->ws.p;
     void* in32 = ws + pl.in32;
     void* cat[3] = {ws + pl.cat0, ws + pl.cat1, ws + pl.cat2};
     const int ncat = n->split_trunk ? 3 : 2;
@@ -387,20 +348,8 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
                     p.cin_chunks = L[4].chunks;
                     p.wpk = L[4].d_wwino;
                     p.bias = L[4].d_b;
-                    if (n->profile) {
-                        if (n->ev_used + 2 > n->ev_pool.size()) {
-                            size_t old = n->ev_pool.size();
-                            n->ev_pool.resize(old + 1024);
-                            for (size_t i = old; i < n->ev_pool.size(); ++i) FW_HIP_CHECK(hipEventCreate(&n->ev_pool[i]));
-                        }
-                        FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-                        launch_conv3x3_wino_split(p, st);
-                        FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-                        n->prof_flops += conv_flops(L[4], (size_t)p.H * p.W);   // algorithmic: the nine-tap count
-                        n->prof_stream = st;
-                    } else {
-                        launch_conv3x3_wino_split(p, st);
-                    }
+                    // algorithmic FLOPs: the nine-tap count
+                    timed(n, st, conv_flops(L[4], (size_t)p.H * p.W), [&] { launch_conv3x3_wino_split(p, st); });
                 } else {
                     run_conv(n, L[4], EPI_RESIDUAL_SPLIT, p, st);
                 }
@@ -444,20 +393,8 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
             u.out = dst;
             u.out_cstride = 32;
             u.out_pstride = dst_pstride;
-            if (n->profile) {
-                if (n->ev_used + 2 > n->ev_pool.size()) {
-                    size_t old = n->ev_pool.size();
-                    n->ev_pool.resize(old + 1024);
-                    for (size_t i = old; i < n->ev_pool.size(); ++i) FW_HIP_CHECK(hipEventCreate(&n->ev_pool[i]));
-                }
-                FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-                launch_conv_up2x_phase(n->dt, u, st);
-                FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-                n->prof_flops += conv_flops(l, (size_t)4 * Hs * Ws);   // algorithmic: the nine-tap count of the reference's conv
-                n->prof_stream = st;
-            } else {
-                launch_conv_up2x_phase(n->dt, u, st);
-            }
+            // algorithmic FLOPs: the nine-tap count of the reference's conv
+            timed(n, st, conv_flops(l, (size_t)4 * Hs * Ws), [&] { launch_conv_up2x_phase(n->dt, u, st); });
         } else {
             ConvParams p = base;
             p.H = 2 * Hs;
@@ -487,20 +424,7 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
             p.cin_chunks = n->conv_hr.chunks;
             p.wpk = n->conv_hr.d_wwino;
             p.bias = n->conv_hr.d_b;
-            if (n->profile) {
-                if (n->ev_used + 2 > n->ev_pool.size()) {
-                    size_t old = n->ev_pool.size();
-                    n->ev_pool.resize(old + 1024);
-                    for (size_t i = old; i < n->ev_pool.size(); ++i) FW_HIP_CHECK(hipEventCreate(&n->ev_pool[i]));
-                }
-                FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-                launch_conv3x3_wino_store(p, st);
-                FW_HIP_CHECK(hipEventRecord(n->ev_pool[n->ev_used++], st));
-                n->prof_flops += conv_flops(n->conv_hr, (size_t)p.H * p.W);
-                n->prof_stream = st;
-            } else {
-                launch_conv3x3_wino_store(p, st);
-            }
+            timed(n, st, conv_flops(n->conv_hr, (size_t)p.H * p.W), [&] { launch_conv3x3_wino_store(p, st); });
         } else {
             run_conv(n, n->conv_hr, EPI_STORE, p, st);
         }
@@ -647,14 +571,6 @@ double fw_rrdbnet_flops(const fw_rrdbnet* n, int H, int W) {
     return 2.0 * mac * px;
 }
 
-static void drop_graphs(fw_rrdbnet* n) {
-    for (auto& g : n->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    n->graphs.clear();
-}
-
 static int upscale_any(fw_rrdbnet* n, const void* in_bgr, int in_loc, int bits, int H, int W, void* out_bgr, int out_loc,
                        float* out_rgb_f32, void* stream, const char* who) {
     const std::string w(who);
@@ -672,26 +588,18 @@ static int upscale_any(fw_rrdbnet* n, const void* in_bgr, int in_loc, int bits, 
         hipStream_t st = (hipStream_t)stream;
         StreamOrder::Scope in_order(n->order, st);
         const Plan pl = make_plan(n, H, W);
-        if (n->ws.bytes < pl.total) {
-            // the previous workspace may still be in use by work queued on some stream
-            FW_HIP_CHECK(hipDeviceSynchronize());
-            drop_graphs(n);   // they hold the old workspace's addresses
-            if (n->ws.base) (void)hipFree(n->ws.base);
-            n->ws.base = nullptr;
-            n->ws.bytes = 0;
-            FW_HIP_CHECK(hipMalloc((void**)&n->ws.base, pl.total));
-            n->ws.bytes = pl.total;
-        }
+        ensure_workspace(n->ws, pl.total, &n->graphs);
+        char* ws = (char*)n->ws.p;
         const size_t in_bytes = (size_t)H * W * 3 * (bits / 8);
         const size_t out_bytes = in_bytes * n->scale * n->scale;
         const void* d_in = in_bgr;
         if (in_loc == FW_HOST) {
-            void* stage = n->ws.base + pl.in_u8;
+            void* stage = ws + pl.in_u8;
             FW_HIP_CHECK(hipMemcpyAsync(stage, in_bgr, in_bytes, hipMemcpyHostToDevice, st));
             d_in = stage;
         }
         void* d_out = out_bgr;
-        if (out_bgr && out_loc == FW_HOST) d_out = n->ws.base + pl.out_u8;
+        if (out_bgr && out_loc == FW_HOST) d_out = ws + pl.out_u8;
         // (the engine's first forward always runs uncaptured: one-time initialisations inside the launchers must not land in a
         // capture)
         const bool graphed = n->warmed && !n->profile &&
@@ -700,39 +608,8 @@ static int upscale_any(fw_rrdbnet* n, const void* in_bgr, int in_loc, int bits, 
         if (!graphed) {
             forward(n, d_in, bits, H, W, d_out, out_rgb_f32, st);
         } else {
-            fw_rrdbnet::GraphEntry* hit = nullptr;
-            for (auto& g : n->graphs)
-                if (g.H == H && g.W == W && g.bits == bits && g.in == d_in && g.out == d_out && g.rgb == out_rgb_f32) hit = &g;
-            if (!hit) {
-                if (n->graphs.size() >= 16) drop_graphs(n);   // callers that never reuse their buffers: do not grow without bound
-                (void)conv_zero_page();                       // its first use allocates: not inside a capture
-                // capture on a stream of our own: the caller's stream may be the legacy default stream, which cannot capture
-                hipStream_t cs = nullptr;
-                FW_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-                fw_rrdbnet::GraphEntry e{H, W, bits, d_in, d_out, out_rgb_f32, nullptr, nullptr};
-                hipError_t err = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-                if (err == hipSuccess) {
-                    try {
-                        forward(n, d_in, bits, H, W, d_out, out_rgb_f32, cs);
-                    } catch (...) {
-                        hipGraph_t junk = nullptr;
-                        (void)hipStreamEndCapture(cs, &junk);
-                        if (junk) (void)hipGraphDestroy(junk);
-                        (void)hipStreamDestroy(cs);
-                        throw;
-                    }
-                    err = hipStreamEndCapture(cs, &e.graph);
-                }
-                if (err == hipSuccess) err = hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0);
-                (void)hipStreamDestroy(cs);
-                if (err != hipSuccess) {
-                    if (e.graph) (void)hipGraphDestroy(e.graph);
-                    FW_HIP_CHECK(err);
-                }
-                n->graphs.push_back(e);
-                hit = &n->graphs.back();
-            }
-            FW_HIP_CHECK(hipGraphLaunch(hit->exec, st));
+            const GraphCache::Key key = {(uint64_t)H, (uint64_t)W, (uint64_t)bits, (uint64_t)d_in, (uint64_t)d_out, (uint64_t)out_rgb_f32};
+            n->graphs.launch(key, st, [&](hipStream_t cs) { forward(n, d_in, bits, H, W, d_out, out_rgb_f32, cs); });
         }
         if (out_bgr && out_loc == FW_HOST) {
             FW_HIP_CHECK(hipMemcpyAsync(out_bgr, d_out, out_bytes, hipMemcpyDeviceToHost, st));
@@ -796,8 +673,8 @@ int fw_rrdbnet_destroy(fw_rrdbnet* n) {
     free_layer(n->conv_up2);
     free_layer(n->conv_hr);
     free_layer(n->conv_last);
-    drop_graphs(n);
-    if (n->ws.base) (void)hipFree(n->ws.base);
+    n->graphs.clear();
+    n->ws.release();
     for (auto e : n->ev_pool) (void)hipEventDestroy(e);
     if (prev >= 0) (void)hipSetDevice(prev);
     n->order.destroy();

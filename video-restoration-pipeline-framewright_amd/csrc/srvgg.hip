@@ -16,22 +16,11 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "engine_common.h"
 
 using namespace fw;
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
 
 struct Layer {
     DevBuf w, b, slopes;
@@ -54,31 +43,6 @@ struct fw_srvgg {
 };
 
 namespace {
-
-int fail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
-}
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
-
-void upload(DevBuf& b, const void* src, size_t bytes) {
-    b.release();
-    FW_HIP_CHECK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    FW_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-}
 
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -243,12 +207,7 @@ int upscale_any(fw_srvgg* n, const void* in_bgr, int bits, int in_loc, int H, in
         hipStream_t st = (hipStream_t)stream;
         StreamOrder::Scope in_order(n->order, st);
         const Plan pl = make_plan(n, H, W);
-        if (n->ws.bytes < pl.total) {
-            FW_HIP_CHECK(hipDeviceSynchronize());
-            n->ws.release();
-            FW_HIP_CHECK(hipMalloc(&n->ws.p, pl.total));
-            n->ws.bytes = pl.total;
-        }
+        ensure_workspace(n->ws, pl.total);
         char* ws = (char*)n->ws.p;
         const size_t in_bytes = (size_t)H * W * 3 * (bits / 8), out_bytes = in_bytes * n->scale * n->scale;
         const void* d_in = in_bgr;
