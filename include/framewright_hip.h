@@ -525,6 +525,31 @@ size_t fw_preserve_edges_scratch_bytes(int height, int width);
 int fw_preserve_edges_u8(const uint8_t* original, const uint8_t* denoised, int height, int width, double low_threshold,
                          double high_threshold, void* scratch, uint8_t* out, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Dense optical flow for the classical temporal denoise (csrc/optical_flow.hip): Farneback's algorithm as
+ * cv2.calcOpticalFlowFarneback runs it (reference temporal_denoise.py:294-305: pyr_scale 0.5, levels 3, winsize 15, iterations 3,
+ * poly_n 5, poly_sigma 1.1, flags 0), restated from OpenCV's published source (tests/farneback_ref.py is the contract; cv2 parity
+ * unpinned).  Device pointers, caller-owned scratch, explicit stream; nothing is allocated and nothing synchronises.
+ *   prev / next : uint8 H x W (channels 1, gray) or H x W x 3 (channels 3, BGR -> gray with cv2's 14-bit weights)
+ *   flow_x / flow_y : fp32 [H][W], the displacement from `prev` to `next`
+ *   scratch : fw_farneback_scratch_bytes(height, width, levels) bytes
+ * Refused with FW_ERR_INVALID and a message, never ignored: poly_n != 5, flags != 0 (OPTFLOW_USE_INITIAL_FLOW,
+ * OPTFLOW_FARNEBACK_GAUSSIAN), even or > 31 winsize, pyr_scale outside (0, 1), a pyramid level below scale 1/8 (its smoothing kernel
+ * would exceed 19 taps), channels other than 1 or 3. */
+size_t fw_farneback_scratch_bytes(int height, int width, int levels);
+int fw_farneback_flow_u8(const uint8_t* prev, const uint8_t* next, int channels, int height, int width, double pyr_scale, int levels,
+                         int winsize, int iterations, int poly_n, double poly_sigma, int flags, void* scratch, float* flow_x,
+                         float* flow_y, void* stream);
+/* magnitude = sqrt(flow_x^2 + flow_y^2) (numpy's float32 rounding; may be NULL) and the local variance of `_compute_flow_confidence`
+ * (temporal_denoise.py:406-431): 5 x 5 box means (BORDER_REFLECT_101) of the components and of their squared deviations, summed. */
+int fw_flow_stats_f32(const float* flow_x, const float* flow_y, int height, int width, float* magnitude, float* variance, void* stream);
+/* confidence = 1 - clip(variance / (*variance_p95 + 1e-6), 0, 1) (temporal_denoise.py:435-436) and, with weight_map != NULL,
+ * weight_map = confidence * (magnitude > *motion_threshold ? 0.5 : 1): the per-pixel weight of `_denoise_with_flow` (:1560-1564) for
+ * fw_flow_accumulate_u8(weight_map, magnitude = NULL).  Both scalars are read from DEVICE memory, so the caller never waits for an
+ * order statistic.  confidence or weight_map may be NULL (not both). */
+int fw_flow_confidence_f32(const float* variance, const float* variance_p95, const float* magnitude, const float* motion_threshold,
+                           int height, int width, float* confidence, float* weight_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

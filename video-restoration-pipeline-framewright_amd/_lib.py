@@ -42,6 +42,7 @@ EXPORTS = [
     "fw_attn_matrix", "fw_attn_apply", "fw_attn_pack", "fw_attn_proj_pack", "fw_pixel_shuffle2_f32", "fw_copy_channels_f32", "fw_f32_to_planar", "fw_tap_post_u8",
     "fw_flow_accumulate_u8", "fw_flow_accumulate_finish_u8", "fw_resize_lanczos4_u8", "fw_resize_linear_u8", "fw_face_paste_u8", "fw_grain_addback_u8", "fw_attn_softmax_rows", "fw_pack_pointwise_transposed", "fw_attn_qk_scratch_elems", "fw_attn_matrix_mfma",
     "fw_pack_conv3x3_wino", "fw_conv3x3_split_nhwc", "fw_conv3x3_wino_nhwc", "fw_conv3x3_wino_check_fields",
+    "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
 ]
 
 
@@ -269,6 +270,14 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_flow_accumulate_finish_u8.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.fw_tap_post_u8.restype = i32
     lib.fw_tap_post_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.fw_farneback_scratch_bytes.restype = sz
+    lib.fw_farneback_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.fw_farneback_flow_u8.restype = i32
+    lib.fw_farneback_flow_u8.argtypes = [vp, vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, C.c_double, i32, vp, vp, vp, vp]
+    lib.fw_flow_stats_f32.restype = i32
+    lib.fw_flow_stats_f32.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    lib.fw_flow_confidence_f32.restype = i32
+    lib.fw_flow_confidence_f32.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
 
 
 def load() -> C.CDLL:
