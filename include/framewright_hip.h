@@ -550,6 +550,39 @@ int fw_flow_stats_f32(const float* flow_x, const float* flow_y, int height, int 
 int fw_flow_confidence_f32(const float* variance, const float* variance_p95, const float* magnitude, const float* motion_threshold,
                            int height, int width, float* confidence, float* weight_map, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Non-local-means spatial denoise for the classical temporal denoise (csrc/nlmeans.hip): the reference's `_apply_spatial_denoise`
+ * (temporal_denoise.py:1611-1634), cv2.fastNlMeansDenoisingColored(frame, None, h, h, 7, 21) with h = int(3 + strength * 7).
+ * OpenCV's 8-bit algorithm restated (tests/nlmeans_ref.py is the contract, held bit for bit; cv2 parity unpinned).  Device
+ * pointers, caller-owned scratch, explicit stream; both device entries only launch kernels and never wait for the device, except
+ * that the first call with a given (device, h, channels, windows) uploads its weight table (one allocation, one blocking copy; the
+ * colour tables likewise, once per device).
+ *   fw_nlmeans_u8 : the core on a uint8 H x W x channels plane (channels 1, 2 or 3, pixels interleaved; the weights use
+ *     h^2 * channels and the patch distances sum over the channels).  src != dst.  `scratch` is not touched (may be NULL): the
+ *     whole neighbourhood is kept on chip.
+ *   fw_nlmeans_colored_u8 : 8-bit linear BGR -> Lab (COLOR_LBGR2Lab: no gamma, D65), the core on L with h and on the interleaved
+ *     ab plane with h_color, Lab -> BGR.  scratch : fw_nlmeans_scratch_bytes(height, width, search_window) bytes.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: channels outside 1 .. 3, h <= 0, a template window other than 3, 5
+ * or 7, a search window that is not odd or outside 3 .. 41 (even sizes are REJECTED, where cv2 would force them odd), a side of
+ * 1 px (reflect-101 needs 2), NULL pointers, and an h so large that its weight table does not fit the kernel's LDS next to the
+ * tile (several thousand non-zero entries; h = 10 has 528 to 1584).
+ * fw_nlmeans_scratch_bytes returns 0 on invalid arguments. */
+size_t fw_nlmeans_scratch_bytes(int height, int width, int search_window);
+int fw_nlmeans_u8(const uint8_t* src, int channels, int height, int width, double h, int template_window, int search_window,
+                  void* scratch, uint8_t* dst, void* stream);
+int fw_nlmeans_colored_u8(const uint8_t* src_bgr, int height, int width, double h, double h_color, int template_window,
+                          int search_window, void* scratch, uint8_t* dst_bgr, void* stream);
+/* HOST functions (no GPU needed).  The fixed-point weight table the core's launcher uploads: t[i] = round(mult * exp(-(i m) /
+ * (h h channels))), mult = INT32_MAX / (search^2 * 255), m = 2^shift / template^2, zero below 0.001 mult - written truncated behind
+ * its last non-zero entry; returns that length (out = NULL: the length only), 0 on invalid arguments (any odd windows are accepted
+ * here) or when `capacity` is too small. */
+int fw_nlmeans_weight_table(double h, int channels, int template_window, int search_window, int32_t* out, int capacity);
+/* The integer tables of the two colour transforms, built once in float64, for comparison with the contract's: which = 0 the
+ * 65281-entry f(t) table of the forward transform (16 fractional bits), 1 its 3 x 3 matrix over (B, G, R) (20 bits), 2 the four
+ * 256-entry tables of the inverse (fy, Y, a / 500, b / 200), 3 its 3 x 3 matrix (rows B, G, R) and the three constants of the
+ * piecewise cube.  Same return convention as fw_nlmeans_weight_table. */
+int fw_nlmeans_lab_tables(int which, int32_t* out, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ EXPORTS = [
     "fw_flow_accumulate_u8", "fw_flow_accumulate_finish_u8", "fw_resize_lanczos4_u8", "fw_resize_linear_u8", "fw_face_paste_u8", "fw_grain_addback_u8", "fw_attn_softmax_rows", "fw_pack_pointwise_transposed", "fw_attn_qk_scratch_elems", "fw_attn_matrix_mfma",
     "fw_pack_conv3x3_wino", "fw_conv3x3_split_nhwc", "fw_conv3x3_wino_nhwc", "fw_conv3x3_wino_check_fields",
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
+    "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
 ]
 
 
@@ -278,6 +279,16 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_flow_stats_f32.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.fw_flow_confidence_f32.restype = i32
     lib.fw_flow_confidence_f32.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.fw_nlmeans_scratch_bytes.restype = sz
+    lib.fw_nlmeans_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.fw_nlmeans_u8.restype = i32
+    lib.fw_nlmeans_u8.argtypes = [vp, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp]
+    lib.fw_nlmeans_colored_u8.restype = i32
+    lib.fw_nlmeans_colored_u8.argtypes = [vp, i32, i32, C.c_double, C.c_double, i32, i32, vp, vp, vp]
+    lib.fw_nlmeans_weight_table.restype = i32
+    lib.fw_nlmeans_weight_table.argtypes = [C.c_double, i32, i32, i32, vp, i32]
+    lib.fw_nlmeans_lab_tables.restype = i32
+    lib.fw_nlmeans_lab_tables.argtypes = [i32, vp, i32]
 
 
 def load() -> C.CDLL:

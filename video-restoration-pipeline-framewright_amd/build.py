@@ -23,7 +23,8 @@ LIB_PATH = LIB_DIR / "libframewright_hip.so"
 ARCH = "gfx950"
 # frame_ops.hip restates float32 numpy arithmetic bit for bit (a*b + c rounds twice): no FMA contraction there
 # optical_flow.hip: the flow magnitude is numpy's sqrt(fx**2 + fy**2), and the flow follows tests/farneback_ref.py's float32 order
-PER_FILE_FLAGS = {"frame_ops.hip": ["-ffp-contract=off"], "optical_flow.hip": ["-ffp-contract=off"]}
+# nlmeans.hip: its host code builds the weight and colour tables in float64, operation for operation as tests/nlmeans_ref.py does
+PER_FILE_FLAGS = {"frame_ops.hip": ["-ffp-contract=off"], "optical_flow.hip": ["-ffp-contract=off"], "nlmeans.hip": ["-ffp-contract=off"]}
 EXTRA = os.environ.get("FW_EXTRA_CXXFLAGS", "").split()
 CXXFLAGS = [*EXTRA, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -12,6 +12,11 @@ parameters (:294-305), the magnitude (:320) and the confidence map (:406-438), c
 a window is uploaded once, flows, statistics and percentiles are computed there, and the host waits once per output frame.
 cv2 is not available where this is built, so parity of the flow with cv2.calcOpticalFlowFarneback is unpinned; the kernels are held
 to a float64 numpy restatement of OpenCV's algorithm (tests/farneback_ref.py).
+
+`DeviceSpatialDenoiser` is `_apply_spatial_denoise` (:1611-1634), cv2.fastNlMeansDenoisingColored(frame, None, h, h, 7, 21) with
+h = int(3 + strength * 7), on the device (csrc/nlmeans.hip): the step the reference's defaults (noise_strength 0.5 > 0.3) take on
+every frame, between the accumulate and the edge-preserve.  Held bit for bit to the integer restatement in tests/nlmeans_ref.py;
+cv2 parity unpinned.
 """
 from __future__ import annotations
 
@@ -199,6 +204,84 @@ class DeviceFlowEstimator:
         return DeviceTemporalAccumulator(gpu_id=self.gpu_id).warp_frame(frame, flow, inverse=inverse)
 
 
+class DeviceSpatialDenoiser:
+    """`TemporalDenoiser._apply_spatial_denoise` (temporal_denoise.py:1611-1634) on one GPU: non-local means on the Lab planes of a
+    BGR frame (fw_nlmeans_colored_u8), and the plain core on a 1-, 2- or 3-channel plane (fw_nlmeans_u8).  The windows are the
+    reference's (7, 21); the kernels take a template window of 3, 5 or 7 and an odd search window of 3 .. 41, and even sizes are
+    rejected where cv2 would force them odd.  tests/nlmeans_ref.py is the contract (bit-exact); cv2 parity unpinned."""
+
+    def __init__(self, gpu_id: int = 0, template_window: int = 7, search_window: int = 21):
+        self.gpu_id, self.template_window, self.search_window = int(gpu_id), int(template_window), int(search_window)
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self._scratch = None
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.gpu_id)
+
+    @staticmethod
+    def h_for_strength(strength: float) -> int:
+        """The filter strength of the reference's call (:1627)."""
+        return int(3 + strength * 7)
+
+    def _scratch_for(self, h: int, w: int, dev):
+        import torch
+        need = int(self._lib.fw_nlmeans_scratch_bytes(h, w, self.search_window))
+        if need <= 0:
+            raise ValueError(f"non-local means: bad frame size {h} x {w} or search window {self.search_window}")
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._scratch
+
+    @_lib.on_tensor_device
+    def denoise_device(self, t, h: float, h_color: Optional[float] = None):
+        """cv2.fastNlMeansDenoisingColored(t, None, h, h_color, template, search) of a uint8 BGR (H x W x 3) device tensor -> a new
+        device tensor; `t` is left untouched, nothing is fetched and nothing waits for the device.  h_color defaults to h, the
+        reference's call."""
+        import torch
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_cuda:
+            raise ValueError("the spatial denoise expects a uint8 BGR (H x W x 3) device frame")
+        t = t.contiguous()
+        dev = t.device
+        hh, ww = int(t.shape[0]), int(t.shape[1])
+        scratch = self._scratch_for(hh, ww, dev)
+        out = torch.empty_like(t)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self._lib.fw_nlmeans_colored_u8(C.c_void_p(t.data_ptr()), hh, ww, float(h), float(h if h_color is None else h_color),
+                                                   self.template_window, self.search_window, C.c_void_p(scratch.data_ptr()),
+                                                   C.c_void_p(out.data_ptr()), st))
+        return out
+
+    @_lib.on_tensor_device
+    def nlmeans_device(self, plane, h: float):
+        """The plain core (cv2.fastNlMeansDenoising's 8-bit algorithm) on a uint8 device plane, H x W or H x W x C with C = 1, 2, 3
+        interleaved channels that share one weight per offset -> a new device tensor of the same shape."""
+        import torch
+        if plane.dtype != torch.uint8 or plane.dim() not in (2, 3) or (plane.dim() == 3 and not 1 <= plane.shape[2] <= 3) or not plane.is_cuda:
+            raise ValueError("non-local means expects a uint8 device plane, H x W or H x W x C with C = 1, 2 or 3")
+        plane = plane.contiguous()
+        dev = plane.device
+        out = torch.empty_like(plane)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self._lib.fw_nlmeans_u8(C.c_void_p(plane.data_ptr()), 1 if plane.dim() == 2 else int(plane.shape[2]), int(plane.shape[0]),
+                                           int(plane.shape[1]), float(h), self.template_window, self.search_window, None,
+                                           C.c_void_p(out.data_ptr()), st))
+        return out
+
+    def denoise(self, frame: np.ndarray, strength: float) -> np.ndarray:
+        """`_apply_spatial_denoise(frame, strength)`: numpy uint8 BGR in and out."""
+        import torch
+        frame = np.ascontiguousarray(frame)
+        if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError("the spatial denoise expects a uint8 BGR (H x W x 3) frame")
+        dev = self._dev()
+        with torch.cuda.device(dev):
+            out = self.denoise_device(torch.from_numpy(frame).to(dev), self.h_for_strength(strength))
+            torch.cuda.current_stream(dev).synchronize()
+            return out.cpu().numpy()
+
+
 class DeviceTemporalAccumulator:
     """The float64 accumulate of `_denoise_with_flow` / `_denoise_simple` on one GPU.
 
@@ -216,6 +299,7 @@ class DeviceTemporalAccumulator:
         self.decay, self.gpu_id = float(temporal_weight_decay), int(gpu_id)
         self.flow_fn = flow_fn or _default_flow_fn
         self.flow_estimator = flow_estimator
+        self._spatial = None
 
     def _dev(self):
         import torch
@@ -321,30 +405,62 @@ class DeviceTemporalAccumulator:
         _lib.check(self._lib.fw_flow_accumulate_finish_u8(p(acc), p(ws), h, w, p(out), st))
         return out
 
-    def denoise_sequence(self, frames: Sequence[np.ndarray], temporal_radius: int = 3, preserve_edges: bool = False,
-                         edge_threshold: int = 30) -> Iterator[np.ndarray]:
-        """The reference's sliding window over a clip (temporal_denoise.py:1480-1503): frame i is denoised from the window
-        [i - radius, i + radius] clipped to the clip, one result per input frame, in order.  With a `flow_estimator` the clip is
-        uploaded once and each output frame costs one wait and one download; `preserve_edges` chains `_preserve_edges`
-        (:1636-1667, fw_preserve_edges_u8) on the device.  Scene cuts, the spatial denoise and flicker reduction are not part of it."""
-        import torch
+    SPATIAL_THRESHOLD = 0.3     # `if self.config.noise_strength > 0.3` (temporal_denoise.py:1506)
+
+    @staticmethod
+    def _check_sequence_args(n: int, temporal_radius: int, noise_strength: Optional[float], scene_changes: Sequence[int]):
+        """Validation of `denoise_sequence`'s arguments (no GPU involved) -> (run the spatial step?, set of scene-cut frames)."""
         if temporal_radius < 1:
             raise ValueError(f"temporal_radius must be >= 1, got {temporal_radius}")
+        if noise_strength is not None:
+            if isinstance(noise_strength, bool) or not isinstance(noise_strength, (int, float, np.integer, np.floating)) or \
+                    not math.isfinite(noise_strength) or noise_strength < 0:
+                raise ValueError(f"noise_strength must be None or a finite number >= 0, got {noise_strength!r}")
+        cuts = set()
+        for c in scene_changes:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+                raise ValueError(f"scene_changes must hold frame indices (int), got {c!r}")
+            if not 0 <= int(c) < n:
+                raise ValueError(f"scene_changes: frame index {int(c)} outside the clip of {n} frames")
+            cuts.add(int(c))
+        return noise_strength is not None and noise_strength > DeviceTemporalAccumulator.SPATIAL_THRESHOLD, cuts
+
+    def _spatial_denoiser(self) -> "DeviceSpatialDenoiser":
+        if self._spatial is None:
+            self._spatial = DeviceSpatialDenoiser(gpu_id=self.gpu_id)
+        return self._spatial
+
+    def denoise_sequence(self, frames: Sequence[np.ndarray], temporal_radius: int = 3, preserve_edges: bool = False,
+                         edge_threshold: int = 30, noise_strength: Optional[float] = None,
+                         scene_changes: Sequence[int] = ()) -> Iterator[np.ndarray]:
+        """The reference's per-frame chain over a clip (temporal_denoise.py:1480-1514): frame i is denoised from the window
+        [i - radius, i + radius] clipped to the clip - a frame listed in `scene_changes` from a window of itself alone (:1483-1489) -
+        one result per input frame, in order.  With `noise_strength` given and > 0.3 the spatial denoise (:1506-1507,
+        `DeviceSpatialDenoiser`, h = int(3 + 7 noise_strength)) follows the accumulate; `preserve_edges` chains `_preserve_edges`
+        (:1636-1667, fw_preserve_edges_u8) behind it, the reference's order.  With a `flow_estimator` the clip is uploaded once, every
+        step stays on the device and each output frame costs one wait and one download.  Detecting the scene cuts and flicker
+        reduction are not part of it."""
+        import torch
         frames = list(frames)
         n = len(frames)
+        spatial, cuts = self._check_sequence_args(n, temporal_radius, noise_strength, scene_changes)
         dev = self._dev()
         if self.flow_estimator is None:
             for i in range(n):
-                lo, hi = max(0, i - temporal_radius), min(n, i + temporal_radius + 1)
+                lo, hi = (i, i + 1) if i in cuts else (max(0, i - temporal_radius), min(n, i + temporal_radius + 1))
                 out = self.denoise_with_flow(i - lo, frames[lo:hi])
+                if spatial:
+                    out = self._spatial_denoiser().denoise(out, noise_strength)
                 yield self.preserve_edges(frames[i], out, edge_threshold) if preserve_edges else out
             return
         with torch.cuda.device(dev):
             devs = [torch.from_numpy(np.ascontiguousarray(f)).to(dev) for f in frames]
         for i in range(n):
-            lo, hi = max(0, i - temporal_radius), min(n, i + temporal_radius + 1)
+            lo, hi = (i, i + 1) if i in cuts else (max(0, i - temporal_radius), min(n, i + temporal_radius + 1))
             with torch.cuda.device(dev):
                 out = self._window_device(i - lo, devs[lo:hi])
+                if spatial:
+                    out = self._spatial_denoiser().denoise_device(out, DeviceSpatialDenoiser.h_for_strength(noise_strength))
                 if preserve_edges:
                     h, w = int(out.shape[0]), int(out.shape[1])
                     scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
