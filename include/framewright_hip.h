@@ -583,6 +583,29 @@ int fw_nlmeans_weight_table(double h, int channels, int template_window, int sea
  * piecewise cube.  Same return convention as fw_nlmeans_weight_table. */
 int fw_nlmeans_lab_tables(int which, int32_t* out, int capacity);
 
+/* -------------------------------------------------------------------------------------------------
+ * Clip analysis and the temporal-consistency pass of the classical temporal denoise (csrc/temporal_chain.hip).  Device pointers,
+ * explicit stream; the three entries only enqueue work and never wait for the device.  tests/temporal_chain_ref.py is the contract
+ * (held exactly); cv2 parity unpinned.
+ *   fw_frame_stats_u8 : for each of `count` contiguous uint8 BGR H x W x 3 frames, hist[f][256] = the histogram of gray =
+ *     (1868 B + 9617 G + 4899 R + 8192) >> 14 (cv2.cvtColor BGR2GRAY) and lap_sums[f] = {sum lap, sum lap^2} as exact integers,
+ *     lap = cv2.Laplacian(gray, CV_64F) with ksize 1 (taps [[0,1,0],[1,-4,1],[0,1,0]], BORDER_REFLECT_101): what the reference's
+ *     `analyze` (temporal_denoise.py:1110-1300) and `_estimate_noise_reduction` (:1734-1788) need of a frame.  Both outputs are
+ *     zeroed on `stream` by the call.  count <= 65535.
+ *   fw_flow_accumulate_affine_u8 : fw_flow_accumulate_u8's remap and accumulate with the per-pixel float64 weight
+ *     w = w_const + w_conf * (double)confidence[p] (product rounded, then the sum), the neighbour step of
+ *     `TemporalConsistencyFilter._apply_flow_guided_filter` (:975-1005).  confidence = NULL: the scalar weight w_const;
+ *     flow_x = flow_y = NULL: the frame as it is.
+ *   fw_add_weighted_u8 : cv2.addWeighted(a, alpha, b, beta, 0) on uint8 (:1016-1020, :1055-1059): alpha and beta rounded once to
+ *     float32, t = fl32(fl32(a * alpha) + fl32(b * beta)), rounded half to even, saturated to 0 .. 255.  `out` may alias `a` or `b`.
+ *     (fw_strength_blend_u8 truncates: it is numpy's astype, not this.) */
+int fw_frame_stats_u8(const uint8_t* frames_bgr, int count, int height, int width, uint32_t* hist /* [count][256] */,
+                      int64_t* lap_sums /* [count][2] */, void* stream);
+int fw_flow_accumulate_affine_u8(const uint8_t* frame_bgr, const float* flow_x, const float* flow_y, const float* confidence,
+                                 double w_const, double w_conf, int inverse, int height, int width, double* accumulated,
+                                 double* weight_sum, void* stream);
+int fw_add_weighted_u8(const uint8_t* a, double alpha, const uint8_t* b, double beta, size_t nbytes, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,15 +17,29 @@ to a float64 numpy restatement of OpenCV's algorithm (tests/farneback_ref.py).
 h = int(3 + strength * 7), on the device (csrc/nlmeans.hip): the step the reference's defaults (noise_strength 0.5 > 0.3) take on
 every frame, between the accumulate and the edge-preserve.  Held bit for bit to the integer restatement in tests/nlmeans_ref.py;
 cv2 parity unpinned.
+
+`DeviceTemporalDenoiser` is the reference's entry point, `TemporalDenoiser.denoise_frames` (:1302-1424), from the first frame to the
+last on the device: `DeviceClipAnalyzer` is phase 1 (`analyze`, :1110-1300: scene cuts, noise level, flicker metrics and the
+recommendations, all from fw_frame_stats_u8's per-frame histogram and Laplacian sums), the chain above is phase 3, and
+`DeviceTemporalConsistencyFilter` is phase 4 (`TemporalConsistencyFilter`, :839-1061: fw_flow_accumulate_affine_u8,
+fw_add_weighted_u8), followed by `_estimate_noise_reduction` (:1734-1788).  tests/temporal_chain_ref.py is the contract of the new
+kernels and of the host arithmetic; cv2 parity unpinned.
+Not built:
+  - flicker REDUCTION (phase 2).  The reference's first choice is the external ffmpeg `deflicker` filter, and its fallback needs
+    gamma-corrected 8-bit Lab, which the non-local-means colour tables (linear Lab) do not provide.  `denoise_clip(frames,
+    deflicker_fn=...)` is the seam: a host function from the list of frames to the list of deflickered frames.  The flicker
+    METRICS of the analysis are computed.
+  - `AutoTemporalDenoiser`: its default preset asks for DIS flow, which `DeviceFlowEstimator` refuses.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass
-from enum import Enum
+import time
+from dataclasses import dataclass, field
+from enum import Enum, auto
 from pathlib import Path
-from typing import Callable, Iterator, List, Optional, Sequence, Union
+from typing import Any, Callable, Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -458,21 +472,52 @@ class DeviceTemporalAccumulator:
         for i in range(n):
             lo, hi = (i, i + 1) if i in cuts else (max(0, i - temporal_radius), min(n, i + temporal_radius + 1))
             with torch.cuda.device(dev):
-                out = self._window_device(i - lo, devs[lo:hi])
-                if spatial:
-                    out = self._spatial_denoiser().denoise_device(out, DeviceSpatialDenoiser.h_for_strength(noise_strength))
-                if preserve_edges:
-                    h, w = int(out.shape[0]), int(out.shape[1])
-                    scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
-                    blended = torch.empty_like(out)
-                    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                    _lib.check(self._lib.fw_preserve_edges_u8(C.c_void_p(devs[i].data_ptr()), C.c_void_p(out.data_ptr()), h, w,
-                                                              float(edge_threshold), float(edge_threshold * 3),
-                                                              C.c_void_p(scratch.data_ptr()), C.c_void_p(blended.data_ptr()), st))
-                    out = blended
+                out = self._chain_device(i - lo, devs[lo:hi], noise_strength if spatial else None, preserve_edges, edge_threshold)
                 torch.cuda.synchronize(dev)
                 res = out.cpu().numpy()
             yield res
+
+    @_lib.on_tensor_device
+    def _chain_device(self, center_local_idx: int, window_dev, spatial_strength: Optional[float], preserve_edges: bool,
+                      edge_threshold: int, simple: bool = False):
+        """One frame of the reference's chain (:1499-1511) on a window of uint8 BGR device frames -> the uint8 device result:
+        accumulate (`_denoise_simple`'s weights with `simple`), the spatial denoise when `spatial_strength` is given, the edge
+        preserve against the window's centre frame.  Only launches, apart from the edge mask's hysteresis (fw_preserve_edges_u8)."""
+        import torch
+        center = window_dev[center_local_idx]
+        dev = center.device
+        out = self._window_simple_device(window_dev) if simple else self._window_device(center_local_idx, window_dev)
+        if spatial_strength is not None:
+            out = self._spatial_denoiser().denoise_device(out, DeviceSpatialDenoiser.h_for_strength(spatial_strength))
+        if preserve_edges:
+            h, w = int(out.shape[0]), int(out.shape[1])
+            scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
+            blended = torch.empty_like(out)
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(self._lib.fw_preserve_edges_u8(C.c_void_p(center.data_ptr()), C.c_void_p(out.data_ptr()), h, w,
+                                                      float(edge_threshold), float(edge_threshold * 3),
+                                                      C.c_void_p(scratch.data_ptr()), C.c_void_p(blended.data_ptr()), st))
+            out = blended
+        return out
+
+    @_lib.on_tensor_device
+    def _window_simple_device(self, frames_dev):
+        """`_denoise_simple` (:1582-1605) for a window of uint8 BGR device frames: scalar weights exp(-|i - len // 2| decay), the
+        reference's centre (the middle of the WINDOW, also where the clip's edge has clipped it)."""
+        import torch
+        dev = frames_dev[0].device
+        h, w = int(frames_dev[0].shape[0]), int(frames_dev[0].shape[1])
+        acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
+        ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        center_idx = len(frames_dev) // 2
+        for i, fd in enumerate(frames_dev):
+            _lib.check(self._lib.fw_flow_accumulate_u8(C.c_void_p(fd.data_ptr()), None, None, None, math.exp(-abs(i - center_idx) * self.decay),
+                                                       None, 0.0, 0, h, w, C.c_void_p(acc.data_ptr()), C.c_void_p(ws.data_ptr()), st))
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        _lib.check(self._lib.fw_flow_accumulate_finish_u8(C.c_void_p(acc.data_ptr()), C.c_void_p(ws.data_ptr()), h, w,
+                                                          C.c_void_p(out.data_ptr()), st))
+        return out
 
     def preserve_edges(self, original: np.ndarray, denoised: np.ndarray, edge_threshold: int = 30) -> np.ndarray:
         """`TemporalDenoiser._preserve_edges` (temporal_denoise.py:1636-1667): the original frame shows through a blurred,
@@ -509,3 +554,484 @@ class DeviceTemporalAccumulator:
             self._accumulate(torch.from_numpy(np.ascontiguousarray(frame)).to(dev), None, math.exp(-abs(i - center_idx) * self.decay),
                              None, None, False, acc, ws)
         return self._finish(acc, ws)
+
+
+# ---- the reference's entry point: analysis, the chain above, the temporal-consistency pass ------------------------------------------
+
+class DenoiseMethod(Enum):
+    """The reference's enum (temporal_denoise.py:59-75), value for value."""
+    MULTI_FRAME_AVERAGE = auto()
+    OPTICAL_FLOW_WARP = auto()
+    NON_LOCAL_MEANS_TEMPORAL = auto()
+    BILATERAL_TEMPORAL = auto()
+    VBM4D = auto()
+
+
+class FlickerMode(Enum):
+    """The reference's enum (temporal_denoise.py:78-91), value for value."""
+    LIGHT = "light"
+    MEDIUM = "medium"
+    AGGRESSIVE = "aggressive"
+    ADAPTIVE = "adaptive"
+
+
+@dataclass
+class TemporalDenoiseConfig:
+    """Field for field the reference dataclass and its validation (temporal_denoise.py:113-163)."""
+    temporal_radius: int = 3
+    noise_strength: float = 0.5
+    method: DenoiseMethod = DenoiseMethod.OPTICAL_FLOW_WARP
+    enable_optical_flow: bool = True
+    optical_flow_method: OpticalFlowMethod = OpticalFlowMethod.FARNEBACK
+    enable_flicker_reduction: bool = True
+    flicker_mode: FlickerMode = FlickerMode.ADAPTIVE
+    preserve_edges: bool = True
+    edge_threshold: int = 30
+    temporal_weight_decay: float = 0.5
+    scene_change_threshold: float = 0.7
+    gpu_id: int = 0
+    chunk_size: int = 50
+
+    def __post_init__(self) -> None:
+        if self.temporal_radius < 1:
+            raise ValueError(f"temporal_radius must be >= 1, got {self.temporal_radius}")
+        if not 0.0 <= self.noise_strength <= 1.0:
+            raise ValueError(f"noise_strength must be 0-1, got {self.noise_strength}")
+        if not 0.0 <= self.temporal_weight_decay <= 1.0:
+            raise ValueError(f"temporal_weight_decay must be 0-1, got {self.temporal_weight_decay}")
+        if not 0.0 <= self.scene_change_threshold <= 1.0:
+            raise ValueError(f"scene_change_threshold must be 0-1, got {self.scene_change_threshold}")
+        if self.chunk_size < 10:
+            raise ValueError(f"chunk_size must be >= 10, got {self.chunk_size}")
+
+
+@dataclass
+class TemporalDenoiseResult:
+    """Field for field the reference dataclass (temporal_denoise.py:166-187)."""
+    frames_processed: int = 0
+    frames_failed: int = 0
+    output_dir: Optional[Path] = None
+    scene_changes_detected: List[int] = field(default_factory=list)
+    avg_noise_reduction: float = 0.0
+    flicker_reduction_applied: bool = False
+    processing_time_seconds: float = 0.0
+    peak_memory_mb: int = 0
+
+
+# Pure host functions: from the per-frame (histogram, sum lap, sum lap^2) of fw_frame_stats_u8 to every number `analyze` reports.
+
+def brightness_from_hist(hist) -> float:
+    """np.mean(gray) (:564) from gray's histogram: sum v hist[v] / N.  Both integers are below 2^53, so the quotient is the one
+    numpy forms from its exact float64 sum."""
+    h = [int(c) for c in hist]
+    return sum(v * c for v, c in enumerate(h)) / sum(h)
+
+
+def laplacian_variance(n_pixels: int, sum_lap: int, sum_lap_sq: int) -> float:
+    """cv2.Laplacian(gray, CV_64F).var() (:1236-1237) from the exact sums: (N S2 - S1^2) / N^2 in integers, rounded once."""
+    n, s1, s2 = int(n_pixels), int(sum_lap), int(sum_lap_sq)
+    return (n * s2 - s1 * s1) / (n * n)
+
+
+def hist_correlation(hist1, hist2) -> float:
+    """cv2.compareHist(h1, h2, HISTCMP_CORREL) of two float32 histograms: the five sums run in double in bin order, then
+    (s12 - s1 s2 / n) / sqrt((s11 - s1^2 / n) (s22 - s2^2 / n)), 1.0 where the denominator's square is within DBL_EPSILON of 0."""
+    a, b = np.asarray(hist1, np.float32).reshape(-1).tolist(), np.asarray(hist2, np.float32).reshape(-1).tolist()
+    s1 = s2 = s11 = s12 = s22 = 0.0
+    for x, y in zip(a, b):
+        s12 += x * y
+        s1 += x
+        s11 += x * x
+        s2 += y
+        s22 += y * y
+    scale = 1.0 / len(a)
+    num = s12 - s1 * s2 * scale
+    denom2 = (s11 - s1 * s1 * scale) * (s22 - s2 * s2 * scale)
+    return num / math.sqrt(denom2) if abs(denom2) > 2.220446049250313e-16 else 1.0
+
+
+def scene_changes_from_hists(hists, sample_rate: int, threshold: float) -> List[int]:
+    """`_detect_scene_changes` (:1158-1207) to the letter, from the gray histograms of the frames (hists[i] is read only for the
+    frames the loop visits; the others may be None): the pairs are (i, min(i + sample_rate, n - 1)), the histograms float32 and
+    normalised by sum + 1e-6 (in float32, as cv2.calcHist's output is), and the index recorded is i + sample_rate - which the last
+    pair can put at or beyond n."""
+    n = len(hists)
+    if n < 2:
+        return []
+    if sample_rate < 1:
+        raise ValueError(f"sample_rate must be >= 1, got {sample_rate}")
+
+    def norm(h):
+        h = np.asarray(h).astype(np.float32)
+        return h / (h.sum() + 1e-6)
+
+    out = []
+    for i in range(0, n - 1, sample_rate):
+        if hist_correlation(norm(hists[i]), norm(hists[min(i + sample_rate, n - 1)])) < threshold:
+            out.append(i + sample_rate)
+    return out
+
+
+def noise_level_from_variances(variances: Sequence[float], sample_rate: int) -> float:
+    """`_estimate_noise_level` (:1230-1252) from the Laplacian variance of every frame: every `sample_rate`-th, the first 50 of
+    those, the median, / 5000, clipped to [0, 1]."""
+    picked = list(variances)[::sample_rate][:50]
+    if not picked:
+        return 0.0
+    return float(np.clip(np.median(picked) / 5000, 0, 1))
+
+
+def flicker_metrics_from_brightness(brightness: Sequence[float], sample_rate: int = 1, max_samples: int = 200) -> Dict[str, Any]:
+    """`FlickerReducer.analyze_flicker` (:538-625) from the mean gray level of every frame of the clip."""
+    quiet = {"severity": 0.0, "temporal_variance": 0.0, "frequency": 0.0, "recommended_mode": FlickerMode.LIGHT.value}
+    values = list(brightness)
+    if len(values) < 3:
+        return quiet
+    values = values[::sample_rate][:max_samples]
+    if len(values) < 3:
+        return quiet
+    b = np.array(values)
+    temporal_variance = np.std(b) / (np.mean(b) + 1e-6)
+    diffs = np.abs(np.diff(b))
+    mean_diff, max_diff = np.mean(diffs), np.max(diffs)
+    fft = np.fft.fft(b - np.mean(b))
+    power = np.abs(fft[:len(fft) // 2]) ** 2
+    if len(power) > 1:
+        dominant_freq_idx = np.argmax(power[1:]) + 1
+        dominant_power = power[dominant_freq_idx] / (np.sum(power) + 1e-6)
+    else:
+        dominant_freq_idx, dominant_power = 0, 0.0
+    severity = min(1.0, (temporal_variance * 2 + (mean_diff / 255) * 3 + dominant_power * 0.5))
+    recommended = FlickerMode.LIGHT if severity < 0.1 else FlickerMode.MEDIUM if severity < 0.3 else FlickerMode.AGGRESSIVE
+    return {"severity": float(severity), "temporal_variance": float(temporal_variance), "frequency": float(dominant_freq_idx),
+            "mean_brightness_diff": float(mean_diff), "max_brightness_diff": float(max_diff), "recommended_mode": recommended.value}
+
+
+def generate_recommendations(analysis: Dict[str, Any], config: TemporalDenoiseConfig) -> Dict[str, Any]:
+    """`_generate_recommendations` (:1254-1300)."""
+    rec = {"temporal_radius": config.temporal_radius, "noise_strength": config.noise_strength,
+           "enable_flicker_reduction": config.enable_flicker_reduction, "flicker_mode": config.flicker_mode.value}
+    noise_level = analysis.get("noise_level", 0.0)
+    flicker_severity = analysis.get("flicker_metrics", {}).get("severity", 0.0)
+    rec["noise_strength"] = 0.3 if noise_level < 0.2 else 0.5 if noise_level < 0.5 else 0.7
+    if len(analysis.get("scene_changes", [])) > 10:
+        rec["temporal_radius"] = 2
+    elif noise_level > 0.5:
+        rec["temporal_radius"] = 4
+    if flicker_severity > 0.3:
+        rec["enable_flicker_reduction"] = True
+        rec["flicker_mode"] = analysis.get("flicker_metrics", {}).get("recommended_mode", "medium")
+    return rec
+
+
+def noise_reduction_from_variances(input_variances: Sequence[float], output_variances: Sequence[float]) -> float:
+    """The tail of `_estimate_noise_reduction` (:1777-1788): 1 - mean(out) / mean(in), clipped to [0, 1]; 0 without frames or
+    where the input has no Laplacian energy."""
+    if not len(input_variances) or not len(output_variances):
+        return 0.0
+    avg_input, avg_output = np.mean(input_variances), np.mean(output_variances)
+    if avg_input <= 0:
+        return 0.0
+    return float(np.clip(1 - (avg_output / avg_input), 0, 1))
+
+
+def _check_clip(frames) -> List[np.ndarray]:
+    """A clip as a list of contiguous uint8 BGR frames of one size (no GPU involved)."""
+    frames = [np.ascontiguousarray(f) for f in frames]
+    for f in frames:
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape != frames[0].shape:
+            raise ValueError("a clip is a sequence of uint8 BGR (H x W x 3) frames of one size")
+    return frames
+
+
+class DeviceClipAnalyzer:
+    """Phase 1 of the reference, `TemporalDenoiser.analyze` (temporal_denoise.py:1110-1300), with the per-frame work on one GPU:
+    fw_frame_stats_u8 reads a resident batch of frames once and leaves 256 histogram bins and two integer sums per frame; the
+    pure host functions above turn those into the reference's `analysis` dict.  Only the frames the reference samples are uploaded
+    (every `sample_rate`-th and the last), at most `config.chunk_size` at a time.
+
+    Gray is always cv2.cvtColor(BGR2GRAY)'s 14-bit form.  The reference's noise estimate reads its frames with IMREAD_GRAYSCALE,
+    where the image decoder does the conversion: those need not be the same bytes, so `noise_level` is the reference's only up to
+    that difference."""
+
+    def __init__(self, config: Optional[TemporalDenoiseConfig] = None):
+        self.config = config or TemporalDenoiseConfig()
+        self.gpu_id = int(self.config.gpu_id)
+        self._lib = _lib.load()
+        _lib.require_gpu()
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.gpu_id)
+
+    @_lib.on_tensor_device
+    def stats_device(self, clip_u8) -> Tuple[np.ndarray, np.ndarray]:
+        """(hist [count][256] uint32, sums [count][2] int64 = sum lap, sum lap^2) of a uint8 count x H x W x 3 BGR device tensor: one
+        launch for the whole batch, one wait, one download of count x 258 words."""
+        import torch
+        if clip_u8.dtype != torch.uint8 or clip_u8.dim() != 4 or clip_u8.shape[3] != 3 or not clip_u8.is_cuda or clip_u8.shape[0] < 1:
+            raise ValueError("frame statistics expect a uint8 count x H x W x 3 BGR device tensor")
+        clip_u8 = clip_u8.contiguous()
+        dev = clip_u8.device
+        count, h, w = (int(v) for v in clip_u8.shape[:3])
+        buf = torch.empty(count * 130, dtype=torch.int64, device=dev)       # count x 256 uint32, then count x 2 int64
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self._lib.fw_frame_stats_u8(C.c_void_p(clip_u8.data_ptr()), count, h, w, C.c_void_p(buf.data_ptr()),
+                                               C.c_void_p(buf.data_ptr() + count * 1024), st))
+        torch.cuda.current_stream(dev).synchronize()
+        host = buf.cpu().numpy()
+        return host[:count * 128].view(np.uint32).reshape(count, 256).copy(), host[count * 128:].reshape(count, 2).copy()
+
+    def frame_stats(self, frames: Sequence[np.ndarray]):
+        """`stats_device` of host frames, uploaded `config.chunk_size` at a time -> (hist, sums) over all of them."""
+        import torch
+        frames = _check_clip(frames)
+        dev, step = self._dev(), int(self.config.chunk_size)
+        hists, sums = [np.zeros((0, 256), np.uint32)], [np.zeros((0, 2), np.int64)]
+        for s in range(0, len(frames), step):
+            with torch.cuda.device(dev):
+                hs, ss = self.stats_device(torch.from_numpy(np.stack(frames[s:s + step])).to(dev))
+            hists.append(hs)
+            sums.append(ss)
+        return np.concatenate(hists), np.concatenate(sums)
+
+    def laplacian_variances(self, frames: Sequence[np.ndarray]) -> List[float]:
+        """cv2.Laplacian(gray, CV_64F).var() of every frame."""
+        frames = _check_clip(frames)
+        if not frames:
+            return []
+        n_px = frames[0].shape[0] * frames[0].shape[1]
+        return [laplacian_variance(n_px, s1, s2) for s1, s2 in self.frame_stats(frames)[1].tolist()]
+
+    def analyze(self, frames: Sequence[np.ndarray], sample_rate: int = 5) -> Dict[str, Any]:
+        """The reference's `analysis` dict for a clip of uint8 BGR frames."""
+        frames = _check_clip(frames)
+        if sample_rate < 1:
+            raise ValueError(f"sample_rate must be >= 1, got {sample_rate}")
+        if not frames:
+            return {"error": "No frames found"}
+        n = len(frames)
+        analysis = {"total_frames": n, "noise_level": 0.0, "flicker_metrics": {}, "scene_changes": [], "recommended_config": {}}
+        picked = sorted(set(range(0, n, sample_rate)) | {n - 1})            # what the three loops of the reference read
+        hist, sums = self.frame_stats([frames[i] for i in picked])
+        n_px = frames[0].shape[0] * frames[0].shape[1]
+        hists: List[Optional[np.ndarray]] = [None] * n
+        for k, i in enumerate(picked):
+            hists[i] = hist[k]
+        sampled = [k for k, i in enumerate(picked) if i % sample_rate == 0]  # frames[::sample_rate]
+        if self.config.enable_flicker_reduction:
+            # analyze_flicker samples frames[::sample_rate][:200] of a clip of at least three frames
+            analysis["flicker_metrics"] = flicker_metrics_from_brightness(
+                [brightness_from_hist(hist[k]) for k in sampled] if n >= 3 else [], 1, 200)
+        analysis["scene_changes"] = scene_changes_from_hists(hists, sample_rate, self.config.scene_change_threshold)
+        analysis["noise_level"] = noise_level_from_variances(
+            [laplacian_variance(n_px, int(sums[k][0]), int(sums[k][1])) for k in sampled], 1)
+        analysis["recommended_config"] = generate_recommendations(analysis, self.config)
+        return analysis
+
+
+class DeviceTemporalConsistencyFilter:
+    """Phase 4 of the reference, `TemporalConsistencyFilter` (temporal_denoise.py:839-1061), on one GPU.
+
+    Flow-guided form (`use_optical_flow` and more than one frame in the window, :955-1022): every neighbour is remapped onto the
+    centre frame by `flow_estimator.maps_device(neighbour, centre)` and accumulated in float64 with the per-pixel weight
+    tw (1 - s) + tw s confidence, tw = exp(-0.5 distance) (fw_flow_accumulate_affine_u8); the centre frame has weight 1, a
+    neighbour whose flow raises the scalar weight tw, unaligned; the quotient (fw_flow_accumulate_finish_u8) is blended with the
+    centre frame by cv2.addWeighted(centre, 1 - s, result, s) (fw_add_weighted_u8).  Simple form (:1024-1061): scalar weights tw,
+    blend with s / 2.  Windows always read the INPUT frames: the filter is not recursive."""
+
+    def __init__(self, strength: float = 0.5, temporal_radius: int = 2, use_optical_flow: bool = True,
+                 flow_estimator: Optional[DeviceFlowEstimator] = None, gpu_id: int = 0):
+        if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)) or not math.isfinite(strength):
+            raise ValueError(f"strength must be a finite number, got {strength!r}")
+        if isinstance(temporal_radius, bool) or not isinstance(temporal_radius, (int, np.integer)) or temporal_radius < 0:
+            raise ValueError(f"temporal_radius must be an int >= 0, got {temporal_radius!r}")
+        self.strength, self.temporal_radius, self.use_optical_flow = float(strength), int(temporal_radius), bool(use_optical_flow)
+        self.gpu_id = int(gpu_id)
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.flow_estimator = flow_estimator or (DeviceFlowEstimator(gpu_id=self.gpu_id) if self.use_optical_flow else None)
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.gpu_id)
+
+    @_lib.on_tensor_device
+    def apply_device(self, devs, i: int):
+        """The filtered frame i of a clip of uint8 BGR device frames, as a uint8 device tensor.  Only launches."""
+        import torch
+        n, s = len(devs), self.strength
+        if not 0 <= i < n:
+            raise ValueError(f"frame index {i} outside the clip of {n} frames")
+        lo, hi = max(0, i - self.temporal_radius), min(n, i + self.temporal_radius + 1)
+        center = devs[i]
+        dev = center.device
+        h, w = int(center.shape[0]), int(center.shape[1])
+        acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
+        ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        guided = self.use_optical_flow and hi - lo > 1
+        for j in range(lo, hi):
+            tw = float(np.exp(-abs(j - i) * 0.5))
+            fx = fy = conf = None
+            w_const, w_conf = tw, 0.0                                  # the simple form, and a neighbour whose flow failed
+            if guided and j == i:
+                w_const = 1.0
+            elif guided:
+                try:
+                    fx, fy, _, conf = self.flow_estimator.maps_device(devs[j], center)
+                    w_const, w_conf = tw * (1 - s), tw * s
+                except Exception:                                      # "Flow estimation failed" (:993-996)
+                    fx = fy = conf = None
+            _lib.check(self._lib.fw_flow_accumulate_affine_u8(p(devs[j]), p(fx), p(fy), p(conf), w_const, w_conf, 0, h, w, p(acc), p(ws), st))
+        result = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        _lib.check(self._lib.fw_flow_accumulate_finish_u8(p(acc), p(ws), h, w, p(result), st))
+        blend = s if guided else s * 0.5
+        out = torch.empty_like(result)
+        _lib.check(self._lib.fw_add_weighted_u8(p(center), 1 - blend, p(result), blend, h * w * 3, p(out), st))
+        return out
+
+    def apply_sequence(self, frames: Sequence[np.ndarray]) -> Iterator[np.ndarray]:
+        """`TemporalConsistencyFilter.apply` over a clip of numpy frames: the clip is uploaded once, one wait and one download per
+        output frame."""
+        import torch
+        frames = _check_clip(frames)
+        dev = self._dev()
+        with torch.cuda.device(dev):
+            devs = [torch.from_numpy(f).to(dev) for f in frames]
+        for i in range(len(frames)):
+            with torch.cuda.device(dev):
+                out = self.apply_device(devs, i)
+                torch.cuda.synchronize(dev)
+                res = out.cpu().numpy()
+            yield res
+
+
+class DeviceTemporalDenoiser:
+    """`TemporalDenoiser` (temporal_denoise.py:1064-1424) on one GPU: analysis, the accumulate -> non-local means -> edge-preserve
+    chain, the temporal-consistency pass and the noise-reduction estimate, with the clip on the device from the upload of a frame to
+    the download of its result.  The reference hands PNG directories from phase to phase (lossless: the same bytes).  Flicker
+    reduction is the caller's (`deflicker_fn`, see the module docstring)."""
+
+    NOISE_REDUCTION_FRAMES = 20     # `_estimate_noise_reduction` reads the first 20 (:1751)
+
+    def __init__(self, config: Optional[TemporalDenoiseConfig] = None):
+        self.config = config or TemporalDenoiseConfig()
+        c = self.config
+        self._analyzer = DeviceClipAnalyzer(c)
+        self._flow_estimator = DeviceFlowEstimator(method=c.optical_flow_method, gpu_id=c.gpu_id)
+        self._accumulator = DeviceTemporalAccumulator(temporal_weight_decay=c.temporal_weight_decay, gpu_id=c.gpu_id,
+                                                      flow_estimator=self._flow_estimator)
+        self._consistency_filter = DeviceTemporalConsistencyFilter(strength=c.noise_strength, temporal_radius=c.temporal_radius,
+                                                                   use_optical_flow=c.enable_optical_flow,
+                                                                   flow_estimator=self._flow_estimator, gpu_id=c.gpu_id)
+        self._scene_changes: List[int] = []
+
+    def analyze(self, frames: Sequence[np.ndarray], sample_rate: int = 5) -> Dict[str, Any]:
+        analysis = self._analyzer.analyze(frames, sample_rate)
+        self._scene_changes = analysis.get("scene_changes", [])
+        return analysis
+
+    def denoise_clip(self, frames: Sequence[np.ndarray], deflicker_fn: Optional[Callable] = None,
+                     progress_callback: Optional[Callable[[float], None]] = None) -> Tuple[List[np.ndarray], TemporalDenoiseResult]:
+        """`denoise_frames` on a clip in memory -> (the output frames, the reference's result record).
+
+        Frames stream through the two device phases chunk by chunk: at most chunk_size + 2 radius input frames and as many denoised
+        frames are resident, a denoised frame is dropped once the last consistency window that reads it is done, and every frame is
+        computed from the same windows whatever `chunk_size` is - the output does not depend on it.  Scene-cut indices at or beyond
+        the clip's end (`scene_changes_from_hists`) match no frame in the reference and are dropped here.
+        Progress: the reference's fractions at the phase boundaries and per chunk of phase 3; phase 4 runs interleaved with it, so its
+        per-frame fractions are not reported."""
+        import torch
+        start = time.time()
+        c = self.config
+        tell = progress_callback or (lambda p: None)
+        frames = _check_clip(frames)
+        result = TemporalDenoiseResult()
+        n = len(frames)
+        if n == 0:
+            return [], result
+        tell(0.02)
+        analysis = self.analyze(frames)
+        result.scene_changes_detected = analysis.get("scene_changes", [])
+        tell(0.05)
+        current = frames
+        if c.enable_flicker_reduction and deflicker_fn is not None:
+            current = _check_clip(deflicker_fn(list(frames)))
+            if len(current) != n or current[0].shape != frames[0].shape:
+                raise ValueError("deflicker_fn must return as many frames, of the same size, as it was given")
+            result.flicker_reduction_applied = True
+        tell(0.25)
+        cuts = {i for i in self._scene_changes if i < n}
+        r, step = c.temporal_radius, c.chunk_size
+        spatial = c.noise_strength if c.noise_strength > DeviceTemporalAccumulator.SPATIAL_THRESHOLD else None
+        dev = self._analyzer._dev()
+        inputs: Dict[int, Any] = {}       # resident input frames
+        denoised: Dict[int, Any] = {}     # resident phase-3 results
+        outputs: List[np.ndarray] = []
+        out_vars: List[float] = []
+        n_px = frames[0].shape[0] * frames[0].shape[1]
+        for s in range(0, n, step):
+            e = min(s + step, n)
+            with torch.cuda.device(dev):
+                for i in [k for k in inputs if k < s - r]:
+                    del inputs[i]
+                for i in range(max(0, s - r), min(n, e + r)):
+                    if i not in inputs:
+                        inputs[i] = torch.from_numpy(current[i]).to(dev)
+                for i in range(s, e):
+                    lo, hi = (i, i + 1) if i in cuts else (max(0, i - r), min(n, i + r + 1))
+                    window = [inputs[k] for k in range(lo, hi)]
+                    denoised[i] = self._accumulator._chain_device(i - lo, window, spatial, c.preserve_edges, c.edge_threshold,
+                                                                  simple=not (c.enable_optical_flow and len(window) > 1))
+                tell(0.25 + (e / n) * 0.6)
+                # phase 4 for every frame whose window is complete
+                done = len(outputs)
+                ready = n if e == n else max(done, e - r)
+                base = max(0, done - r)
+                clip = [denoised[k] for k in range(base, e)]
+                finished = []
+                for i in range(done, ready):
+                    finished.append(self._consistency_filter.apply_device(clip, i - base))
+                torch.cuda.synchronize(dev)
+                head = [t for i, t in zip(range(done, ready), finished) if i < self.NOISE_REDUCTION_FRAMES]
+                if head:
+                    out_vars += [laplacian_variance(n_px, s1, s2) for s1, s2 in self._analyzer.stats_device(torch.stack(head))[1].tolist()]
+                outputs += [t.cpu().numpy() for t in finished]
+                for i in [k for k in denoised if k < ready - r]:
+                    del denoised[i]
+        tell(0.85)
+        tell(0.95)
+        result.frames_processed = len(outputs)
+        result.frames_failed = n - result.frames_processed
+        result.avg_noise_reduction = noise_reduction_from_variances(
+            self._analyzer.laplacian_variances(frames[:self.NOISE_REDUCTION_FRAMES]), out_vars)
+        result.processing_time_seconds = time.time() - start
+        tell(1.0)
+        return outputs, result
+
+    def denoise_frames(self, input_dir: Union[str, Path], output_dir: Union[str, Path],
+                       progress_callback: Optional[Callable[[float], None]] = None) -> TemporalDenoiseResult:
+        """The directory form (:1302-1424): `*.png`, else `*.jpg`, sorted; the results are written under the same names."""
+        from PIL import Image
+        input_dir, output_dir = Path(input_dir), Path(output_dir)
+        output_dir.mkdir(parents=True, exist_ok=True)
+        paths = sorted(input_dir.glob("*.png")) or sorted(input_dir.glob("*.jpg"))
+        if not paths:
+            return TemporalDenoiseResult()
+        start = time.time()
+        outputs, result = self.denoise_clip([DeviceFlowEstimator._load(p) for p in paths], progress_callback=progress_callback)
+        for p, frame in zip(paths, outputs):
+            Image.fromarray(np.ascontiguousarray(frame[:, :, ::-1])).save(str(output_dir / p.name))
+        result.output_dir = output_dir
+        result.processing_time_seconds = time.time() - start
+        return result
+
+
+def create_temporal_denoiser(strength: float = 0.5, temporal_radius: int = 3, enable_optical_flow: bool = True,
+                             enable_flicker_reduction: bool = True, gpu_id: int = 0) -> DeviceTemporalDenoiser:
+    """The reference's factory (temporal_denoise.py:1894-1920)."""
+    return DeviceTemporalDenoiser(TemporalDenoiseConfig(noise_strength=strength, temporal_radius=temporal_radius,
+                                                        enable_optical_flow=enable_optical_flow,
+                                                        enable_flicker_reduction=enable_flicker_reduction, gpu_id=gpu_id))
