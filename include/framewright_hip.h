@@ -421,6 +421,14 @@ int fw_ifnet_build_x(const float* img0, const float* img1, const float* flow, co
 int fw_unshuffle2_cast(int dtype, const void* src, int src_is_f32, int height, int width, int channels, int src_cstride,
                        void* dst, int dst_channels, void* stream);
 
+/* An IFBlock's whole input in one kernel, as the engine runs it: fw_ifnet_build_x, F.interpolate(x, 1/scale),
+ * F.interpolate(flow, 1/scale) / scale, cat, pixel_unshuffle(2) and the cast of fw_unshuffle2_cast ->
+ * dst operand-typed [height/scale/2][width/scale/2][dst_channels], channel c*4 + dy*2 + dx over the 7 channels (flow == mask == NULL)
+ * or the 12 channels (8 of x, 4 of flow) of the block's input, zero above.  height and width multiples of 2*scale; dst_channels a
+ * multiple of 8, at least 28 / 48 and at most 64; flow and dst 16-byte aligned. */
+int fw_ifnet_stage_input(int dtype, const float* img0, const float* img1, const float* flow, const float* mask, int height, int width,
+                         float timestep, int scale, void* dst, int dst_channels, void* stream);
+
 /* [h][w][>=96] with channel ((c6*4 + qy*2 + qx)*4 + py*2 + px) -> [4h][4w][6]: ConvTranspose2d(4,2,1) evaluated as a
  * 3x3 conv with 4 output parities, followed by PixelShuffle(2). */
 int fw_depth_to_space4_f32(const float* src, int height, int width, int src_cstride, float* dst, void* stream);
@@ -428,6 +436,12 @@ int fw_depth_to_space4_f32(const float* src, int height, int width, int src_cstr
 /* flow (+)= bilinear_up(tmp)[:4] * scale ; mask (+)= bilinear_up(tmp)[4]   (first != 0: assign). */
 int fw_ifnet_accumulate(const float* tmp, int tmp_h, int tmp_w, int height, int width, float scale, float* flow, float* mask,
                         int first, void* stream);
+
+/* fw_ifnet_accumulate reading the lastconv output in place, without the depth-to-space copy: tmp[Y][X][c6] =
+ * t96[Y >> 2][X >> 2][pos*6 + c6] with pos = ((Y&1)*2 + (X&1))*4 + ((Y>>1)&1)*2 + ((X>>1)&1), t96 [feat_h][feat_w][src_cstride]
+ * (the row order the engine gives lastconv's weights).  src_cstride even and >= 96, t96 8-byte and flow 16-byte aligned. */
+int fw_ifnet_accumulate_d2s(const float* t96, int feat_h, int feat_w, int src_cstride, int height, int width, float scale, float* flow,
+                            float* mask, int first, void* stream);
 
 /* merged = warp(img0, flow[:2]) * sigmoid(mask) + warp(img1, flow[2:4]) * (1 - sigmoid(mask)), cropped to H x W;
  * out_bgr = round_half_even(clamp(merged, 0, 1) * 255) (BGR), out_rgb_f32 = merged (RGB); either may be NULL. */
@@ -494,6 +508,9 @@ int fw_ifnet_finalize(fw_ifnet* net);
  * Asynchronous on `stream` for device buffers; host outputs are complete on return. */
 int fw_ifnet_interp_u8(fw_ifnet* net, const uint8_t* frame0, const uint8_t* frame1, int in_loc, int height, int width,
                        float timestep, uint8_t* out_bgr, int out_loc, float* out_rgb_f32, void* stream);
+/* Flow [Hp][Wp][4] (pixels) and mask [Hp][Wp] (before the sigmoid) of the handle's last forward, Hp / Wp = height / width rounded up to
+ * a multiple of 32, copied to device buffers on `stream` (either may be NULL).  FW_ERR_INVALID unless the last forward had this size. */
+int fw_ifnet_last_flow(fw_ifnet* net, int height, int width, float* flow_out, float* mask_out, void* stream);
 size_t fw_ifnet_workspace_bytes(const fw_ifnet* net, int height, int width);
 double fw_ifnet_flops(const fw_ifnet* net, int height, int width);
 int fw_ifnet_destroy(fw_ifnet* net);

@@ -30,6 +30,7 @@ EXPORTS = [
     "fw_strength_blend_u8",
     "fw_conv3x3_nhwc_ex", "fw_conv3x3_pair_nhwc", "fw_pack_conv_up2x_phase", "fw_conv_up2x_phase_nhwc", "fw_u8_to_rgb_f32", "fw_resize_bilinear_f32", "fw_ifnet_build_x", "fw_unshuffle2_cast",
     "fw_depth_to_space4_f32", "fw_ifnet_accumulate", "fw_ifnet_blend", "fw_unsharp_mask_u8",
+    "fw_ifnet_stage_input", "fw_ifnet_accumulate_d2s", "fw_ifnet_last_flow",
     "fw_ifnet_create", "fw_ifnet_set_tensor", "fw_ifnet_finalize", "fw_ifnet_interp_u8", "fw_ifnet_workspace_bytes", "fw_ifnet_flops",
     "fw_ifnet_destroy",
     "fw_aesrgan_create", "fw_aesrgan_set_tensor", "fw_aesrgan_finalize", "fw_aesrgan_forward_rgb", "fw_aesrgan_workspace_bytes", "fw_aesrgan_destroy",
@@ -165,6 +166,12 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_depth_to_space4_f32.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.fw_ifnet_accumulate.restype = i32
     lib.fw_ifnet_accumulate.argtypes = [vp, i32, i32, i32, i32, f32, vp, vp, i32, vp]
+    lib.fw_ifnet_stage_input.restype = i32
+    lib.fw_ifnet_stage_input.argtypes = [i32, vp, vp, vp, vp, i32, i32, f32, i32, vp, i32, vp]
+    lib.fw_ifnet_accumulate_d2s.restype = i32
+    lib.fw_ifnet_accumulate_d2s.argtypes = [vp, i32, i32, i32, i32, i32, f32, vp, vp, i32, vp]
+    lib.fw_ifnet_last_flow.restype = i32
+    lib.fw_ifnet_last_flow.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.fw_ifnet_blend.restype = i32
     lib.fw_ifnet_blend.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.fw_aesrgan_create.restype = i32

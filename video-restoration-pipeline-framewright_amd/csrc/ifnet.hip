@@ -179,6 +179,7 @@ struct fw_ifnet {
     bool narrow_groups = true;  // 32-channel output groups for the conv chains of blocks with few tiles (FW_IFNET_NARROW=0: A/B;
     long narrow_below = 128;    //   FW_IFNET_NARROW_BELOW: below that many 64-channel workgroups per launch)
     bool warmed = false;
+    int last_h = 0, last_w = 0;   // frame size of the forward whose flow and mask the workspace holds (fw_ifnet_last_flow)
     GraphCache graphs;
 };
 
@@ -557,10 +558,29 @@ int fw_ifnet_interp_u8(fw_ifnet* n, const uint8_t* frame0, const uint8_t* frame1
             const GraphCache::Key key = {(uint64_t)H, (uint64_t)W, t_bits, (uint64_t)d0, (uint64_t)d1, (uint64_t)d_out, (uint64_t)out_rgb_f32};
             n->graphs.launch(key, st, [&](hipStream_t cs) { forward(n, d0, d1, H, W, timestep, d_out, out_rgb_f32, cs); });
         }
+        n->last_h = H;
+        n->last_w = W;
         if (out_bgr && out_loc == FW_HOST) {
             FW_HIP_CHECK(hipMemcpyAsync(out_bgr, d_out, bytes, hipMemcpyDeviceToHost, st));
             FW_HIP_CHECK(hipStreamSynchronize(st));
         }
+    });
+}
+
+int fw_ifnet_last_flow(fw_ifnet* n, int H, int W, float* flow_out, float* mask_out, void* stream) {
+    if (!n || (!flow_out && !mask_out)) return fail(FW_ERR_INVALID, "fw_ifnet_last_flow: NULL argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        if (H < 1 || W < 1 || H != n->last_h || W != n->last_w || !n->ws.p)
+            throw Error(FW_ERR_INVALID, "fw_ifnet_last_flow: the last forward of this handle was not of that frame size");
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        const Plan pl = make_plan(H, W);
+        const size_t px = (size_t)pad_to(H, 32) * pad_to(W, 32);
+        const char* ws = (const char*)n->ws.p;
+        if (flow_out) FW_HIP_CHECK(hipMemcpyAsync(flow_out, ws + pl.flow, px * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (mask_out) FW_HIP_CHECK(hipMemcpyAsync(mask_out, ws + pl.mask, px * sizeof(float), hipMemcpyDeviceToDevice, st));
     });
 }
 

@@ -509,23 +509,39 @@ int fw_unshuffle2_cast(int dtype, const void* src, int src_is_f32, int height, i
     if (!src || !dst || height < 2 || width < 2 || (height & 1) || (width & 1) || channels < 1 || src_cstride < channels ||
         dst_channels < 4 * channels || (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16))
         return fail(FW_ERR_INVALID, "fw_unshuffle2_cast: bad argument");
-    const long n = (long)(height / 2) * (width / 2) * dst_channels;
-    dim3 g(grid_for(n)), b(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FW_DTYPE_BF16) {
-        if (src_is_f32)
-            hipLaunchKernelGGL((unshuffle_cast_kernel<__bf16, float>), g, b, 0, st, (const float*)src, height, width, channels,
-                               src_cstride, (__bf16*)dst, dst_channels);
-        else
-            hipLaunchKernelGGL((unshuffle_cast_kernel<__bf16, __bf16>), g, b, 0, st, (const __bf16*)src, height, width,
-                               channels, src_cstride, (__bf16*)dst, dst_channels);
-    } else {
-        if (src_is_f32)
-            hipLaunchKernelGGL((unshuffle_cast_kernel<_Float16, float>), g, b, 0, st, (const float*)src, height, width,
-                               channels, src_cstride, (_Float16*)dst, dst_channels);
-        else
-            hipLaunchKernelGGL((unshuffle_cast_kernel<_Float16, _Float16>), g, b, 0, st, (const _Float16*)src, height, width,
-                               channels, src_cstride, (_Float16*)dst, dst_channels);
+    // the engine's own dispatch: a typed source with even channel counts takes unshuffle_typed8_kernel
+    fw::launch_unshuffle2_cast((DType)dtype, src, src_is_f32 != 0, height, width, channels, src_cstride, dst, dst_channels, (hipStream_t)stream);
+    FW_LAUNCHED();
+    return FW_OK;
+}
+
+int fw_ifnet_stage_input(int dtype, const float* img0, const float* img1, const float* flow, const float* mask, int height, int width,
+                         float timestep, int scale, void* dst, int dst_channels, void* stream) {
+    if (!img0 || !img1 || !dst || height < 1 || width < 1 || scale < 1 || (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16))
+        return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: bad argument");
+    if (dst_channels > 64 || (dst_channels & 7) || dst_channels < 4 * (flow ? 12 : 7) || height % (2 * scale) || width % (2 * scale))
+        return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: bad shape");
+    if ((flow == nullptr) != (mask == nullptr)) return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: flow and mask go together");
+    if (((size_t)flow & 15) || ((size_t)dst & 15)) return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: flow and dst must be 16-byte aligned");
+    try {
+        fw::launch_ifnet_stage_input((DType)dtype, img0, img1, flow, mask, height, width, timestep, scale, dst, dst_channels, (hipStream_t)stream);
+    } catch (const fw::Error& e) {
+        return fail(FW_ERR_INVALID, e.what());
+    }
+    FW_LAUNCHED();
+    return FW_OK;
+}
+
+int fw_ifnet_accumulate_d2s(const float* t96, int feat_h, int feat_w, int src_cstride, int height, int width, float scale, float* flow,
+                            float* mask, int first, void* stream) {
+    if (!t96 || !flow || !mask || feat_h < 1 || feat_w < 1 || height < 1 || width < 1 || src_cstride < 96 || !(scale >= 1.f))
+        return fail(FW_ERR_INVALID, "fw_ifnet_accumulate_d2s: bad argument");
+    if ((src_cstride & 1) || ((size_t)t96 & 7) || ((size_t)flow & 15))
+        return fail(FW_ERR_INVALID, "fw_ifnet_accumulate_d2s: t96 must be 8-byte aligned with an even channel stride, flow 16-byte aligned");
+    try {
+        fw::launch_ifnet_accumulate_d2s(t96, feat_h, feat_w, src_cstride, height, width, scale, flow, mask, first, (hipStream_t)stream);
+    } catch (const fw::Error& e) {
+        return fail(FW_ERR_INVALID, e.what());
     }
     FW_LAUNCHED();
     return FW_OK;

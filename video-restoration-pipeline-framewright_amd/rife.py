@@ -180,6 +180,20 @@ class IFNetEngine:
                                                 _lib.FW_DEVICE, p(out_rgb_f32), st))
         return out if out is not None else out_rgb_f32
 
+    def last_flow(self, height: int, width: int):
+        """Flow ``[Hp][Wp][4]`` (pixels) and mask ``[Hp][Wp]`` (before the sigmoid) of the last forward, which must have been of
+        ``height`` x ``width``; Hp / Wp are those rounded up to a multiple of 32.  fp32 CUDA tensors, asynchronous on torch's
+        current stream."""
+        import torch
+        hp, wp = (int(height) + 31) // 32 * 32, (int(width) + 31) // 32 * 32
+        with torch.cuda.device(self._dev):
+            flow = torch.empty((hp, wp, 4), dtype=torch.float32, device=self._dev)
+            mask = torch.empty((hp, wp), dtype=torch.float32, device=self._dev)
+            st = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+            _lib.check(self._lib.fw_ifnet_last_flow(self._h, int(height), int(width), C.c_void_p(flow.data_ptr()),
+                                                    C.c_void_p(mask.data_ptr()), st))
+        return flow, mask
+
     def interpolate(self, img0: np.ndarray, img1: np.ndarray, timestep: float = 0.5) -> np.ndarray:
         """Host frames in, host frame out (the engine stages them: ``FW_HOST`` buffers through the C-ABI)."""
         if not self._loaded:
