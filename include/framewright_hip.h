@@ -56,8 +56,10 @@ typedef struct fw_nafnet fw_nafnet;
 /* Message of the last failing call on this thread ("" if none).  Never NULL. */
 const char* fw_last_error(void);
 
-/* ABI version of this header: 4.  Bumped whenever entry points are added or changed (1 -> 2, 2 -> 3 and 3 -> 4 were additive: a
- * binder of version 1, 2 or 3 keeps working against this library). */
+/* ABI version of this header: 4.  Bumped whenever an existing entry point changes (1 -> 2, 2 -> 3 and 3 -> 4 were additive: a
+ * binder of version 1, 2 or 3 keeps working against this library).  Additive entries no longer bump the version: the flicker
+ * reduction entries (fw_bgr_to_lab_u8 ... fw_gamma_lab_tables) were added at version 4, so a binder that needs them looks the
+ * symbols up instead of comparing versions. */
 int fw_abi_version(void);
 
 /* Number of visible HIP devices (0 when there is no GPU; never fails). */
@@ -622,6 +624,32 @@ int fw_flow_accumulate_affine_u8(const uint8_t* frame_bgr, const float* flow_x, 
                                  double w_const, double w_conf, int inverse, int height, int width, double* accumulated,
                                  double* weight_sum, void* stream);
 int fw_add_weighted_u8(const uint8_t* a, double alpha, const uint8_t* b, double beta, size_t nbytes, uint8_t* out, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Flicker reduction of the classical temporal denoise (csrc/flicker.hip): the reference's Python path,
+ * `FlickerReducer._apply_python_deflicker` (temporal_denoise.py:764-836), brightness normalisation in 8-bit gamma Lab
+ * (cv2.COLOR_BGR2LAB / COLOR_LAB2BGR).  The ffmpeg `deflicker` filter, the reference's first choice, is not built.  The sRGB and CIE
+ * Lab formulas restated in fixed point (tests/flicker_ref.py is the contract, held bit for bit; cv2 parity unpinned).  Device
+ * pointers, explicit stream; the four device entries only enqueue work and never wait for the device, except that the first call on
+ * a device uploads the tables (an allocation and a blocking copy).
+ *   fw_bgr_to_lab_u8 / fw_lab_to_bgr_u8 : the two transforms on n_pixels interleaved 3-byte pixels (sRGB decode, D65, L * 255 / 100,
+ *     a + 128, b + 128).  dst may alias src.
+ *   fw_lab_l_sums_u8 : l_sums[f] = the sum of L over frame f of `count` contiguous uint8 BGR H x W x 3 frames, an exact integer
+ *     (64 bits: an 8K frame exceeds 2^32).  The output is zeroed on `stream` by the call.
+ *   fw_deflicker_lab_u8 : per frame f, BGR -> Lab, L = l_luts[f][L], Lab -> BGR in one pass: one read and one write of the frames,
+ *     no Lab plane in memory.  l_luts is count x 256 bytes of DEVICE memory.  dst_bgr may alias frames_bgr.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, count outside 1 .. 65535, non-positive sizes, more
+ * than 2^30 pixels per frame. */
+int fw_bgr_to_lab_u8(const uint8_t* src_bgr, int64_t n_pixels, uint8_t* dst_lab, void* stream);
+int fw_lab_to_bgr_u8(const uint8_t* src_lab, int64_t n_pixels, uint8_t* dst_bgr, void* stream);
+int fw_lab_l_sums_u8(const uint8_t* frames_bgr, int count, int height, int width, int64_t* l_sums /* [count] */, void* stream);
+int fw_deflicker_lab_u8(const uint8_t* frames_bgr, int count, int height, int width, const uint8_t* l_luts /* [count][256] */,
+                        uint8_t* dst_bgr, void* stream);
+/* HOST function (no GPU needed).  The tables the gamma transforms add to fw_nlmeans_lab_tables', built once in float64, for
+ * comparison with the contract's: which = 0 the 256-entry sRGB decode to the 0 .. 65280 scale, 1 the 65281-entry sRGB encode of
+ * that scale to 0 .. 255, 2 the same map as 255 thresholds (the first index whose entry exceeds k), which is what the kernels
+ * search.  Same return convention as fw_nlmeans_weight_table. */
+int fw_gamma_lab_tables(int which, int32_t* out, int capacity);
 
 #ifdef __cplusplus
 }

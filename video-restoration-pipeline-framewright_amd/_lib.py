@@ -46,6 +46,7 @@ EXPORTS = [
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
+    "fw_bgr_to_lab_u8", "fw_lab_to_bgr_u8", "fw_lab_l_sums_u8", "fw_deflicker_lab_u8", "fw_gamma_lab_tables",
 ]
 
 
@@ -303,6 +304,16 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_flow_accumulate_affine_u8.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp]
     lib.fw_add_weighted_u8.restype = i32
     lib.fw_add_weighted_u8.argtypes = [vp, C.c_double, vp, C.c_double, sz, vp, vp]
+    lib.fw_bgr_to_lab_u8.restype = i32
+    lib.fw_bgr_to_lab_u8.argtypes = [vp, C.c_int64, vp, vp]
+    lib.fw_lab_to_bgr_u8.restype = i32
+    lib.fw_lab_to_bgr_u8.argtypes = [vp, C.c_int64, vp, vp]
+    lib.fw_lab_l_sums_u8.restype = i32
+    lib.fw_lab_l_sums_u8.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.fw_deflicker_lab_u8.restype = i32
+    lib.fw_deflicker_lab_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    lib.fw_gamma_lab_tables.restype = i32
+    lib.fw_gamma_lab_tables.argtypes = [i32, vp, i32]
 
 
 def load() -> C.CDLL:

@@ -13,6 +13,7 @@
 // offset loop; HBM traffic is one read and one write per plane.
 #include "fw_internal.h"
 #include "framewright_hip.h"
+#include "lab_tables.h"
 
 #include <cmath>
 #include <map>
@@ -140,18 +141,7 @@ __global__ __launch_bounds__(NLM_NT) void nlmeans_kernel(const uint8_t* __restri
 }
 
 // ---- 8-bit linear BGR <-> Lab (COLOR_LBGR2Lab / COLOR_Lab2LBGR), integers over tables built once in float64 ----
-constexpr int F_BITS = 16, COEF_BITS = 20, INV_COEF_BITS = 14, CBRT_STEPS = 256, CBRT_N = 255 * CBRT_STEPS + 1;
-constexpr int L_SCALE_BITS = 6;
-
-struct LabFwd {
-    int coef[9];        // rows X / Xn, Y, Z / Zn over (B, G, R), each summing to 2^20
-    int l_scale, l_offset;
-};
-struct LabInv {
-    int coef[9];        // rows B, G, R over (X, Y, Z)
-    int thr, c16, kinv;
-};
-
+// constants, LabFwd, LabInv, LabTables and lab_tables(): lab_tables.h (shared with flicker.hip)
 __global__ __launch_bounds__(256) void bgr_to_lab_kernel(const uint8_t* __restrict__ bgr, long n, LabFwd k, const int* __restrict__ cbrt_tab,
                                                          uint8_t* __restrict__ Lp, uint8_t* __restrict__ abp) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -190,65 +180,6 @@ __global__ __launch_bounds__(256) void lab_to_bgr_kernel(const uint8_t* __restri
     }
 }
 
-struct LabTables {
-    std::vector<int> cbrt_tab, t256;
-    LabFwd fwd;
-    LabInv inv;
-};
-
-const LabTables& lab_tables() {
-    static const LabTables t = [] {
-        LabTables r;
-        const double XN = 0.950456, ZN = 1.088754, T0 = 0.008856;
-        const double M[3][3] = {{0.412453, 0.357580, 0.180423}, {0.212671, 0.715160, 0.072169}, {0.019334, 0.119193, 0.950227}};
-        const double MI[3][3] = {{3.240479, -1.53715, -0.498535}, {-0.969256, 1.875991, 0.041556}, {0.055648, -0.204043, 1.057311}};
-        const double wp[3] = {XN, 1.0, ZN};
-        const double f_thresh = 7.787 * T0 + 16.0 / 116.0, l_thresh = T0 * 903.3;
-        r.cbrt_tab.resize(CBRT_N);
-        for (int i = 0; i < CBRT_N; ++i) {
-            const double x = (double)i / (double)(CBRT_N - 1);
-            const double f = x > T0 ? std::cbrt(x) : 7.787 * x + 16.0 / 116.0;
-            r.cbrt_tab[i] = (int)std::nearbyint((double)(1 << F_BITS) * f);
-        }
-        for (int q = 0; q < 3; ++q) {
-            double row[3];
-            for (int j = 0; j < 3; ++j) row[j] = M[q][j] / wp[q];
-            const double s = (row[0] + row[1]) + row[2];
-            long c[3], sum = 0;
-            int big = 0;
-            for (int j = 0; j < 3; ++j) {                     // (B, G, R) order: column 2 - j of the RGB matrix
-                c[j] = (long)std::nearbyint(row[2 - j] / s * (double)(1 << COEF_BITS));
-                sum += c[j];
-                if (c[j] > c[big]) big = j;
-            }
-            c[big] += (1l << COEF_BITS) - sum;
-            for (int j = 0; j < 3; ++j) r.fwd.coef[3 * q + j] = (int)c[j];
-        }
-        r.fwd.l_scale = (int)std::nearbyint(116.0 * 2.55 * (double)(1 << L_SCALE_BITS));
-        r.fwd.l_offset = (int)std::nearbyint(16.0 * 2.55 * (double)(1 << (F_BITS + L_SCALE_BITS)));
-        r.t256.resize(1024);
-        for (int i = 0; i < 256; ++i) {
-            const double L = (double)i * 100.0 / 255.0;
-            const double y_low = L / 903.3;
-            const double fy = L <= l_thresh ? 7.787 * y_low + 16.0 / 116.0 : (L + 16.0) / 116.0;
-            const double yl = L <= l_thresh ? y_low : fy * fy * fy;
-            const double ab = (double)i - 128.0;
-            r.t256[i] = (int)std::nearbyint(fy * (double)(1 << F_BITS));
-            r.t256[256 + i] = (int)std::nearbyint(yl * (double)(1 << F_BITS));
-            r.t256[512 + i] = (int)std::nearbyint(ab / 500.0 * (double)(1 << F_BITS));
-            r.t256[768 + i] = (int)std::nearbyint(ab / 200.0 * (double)(1 << F_BITS));
-        }
-        for (int q = 0; q < 3; ++q)                           // rows B, G, R
-            for (int j = 0; j < 3; ++j)
-                r.inv.coef[3 * q + j] = (int)std::nearbyint(MI[2 - q][j] * wp[j] * 255.0 * (double)(1 << INV_COEF_BITS));
-        r.inv.thr = (int)std::nearbyint(f_thresh * (double)(1 << F_BITS));
-        r.inv.c16 = (int)std::nearbyint(16.0 / 116.0 * (double)(1 << F_BITS));
-        r.inv.kinv = (int)std::nearbyint((double)(1 << F_BITS) / 7.787);
-        return r;
-    }();
-    return t;
-}
-
 // ---- the weight table (host, float64) ----
 struct TableShape {
     int mult, shift, n;
@@ -281,10 +212,6 @@ std::vector<int> weight_table(double h, int channels, const TableShape& s) {
 }
 
 // ---- device-resident copies: made on first use (an allocation and a blocking copy), then only read ----
-struct DeviceLab {
-    int* cbrt_tab = nullptr;
-    int* t256 = nullptr;
-};
 struct DeviceTable {
     int* ptr = nullptr;
     int n = 0;
@@ -298,16 +225,6 @@ int* upload(const std::vector<int>& v) {
     int* d = nullptr;
     FW_HIP_CHECK(hipMalloc((void**)&d, v.size() * sizeof(int)));
     FW_HIP_CHECK(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-    return d;
-}
-
-DeviceLab device_lab() {
-    int dev = 0;
-    FW_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceLab& d = g_lab[dev];
-    if (!d.cbrt_tab) d.cbrt_tab = upload(lab_tables().cbrt_tab);
-    if (!d.t256) d.t256 = upload(lab_tables().t256);
     return d;
 }
 
@@ -392,6 +309,71 @@ void run_core(const CorePlan& p, const uint8_t* src, int channels, int H, int W,
 }
 
 }  // namespace
+
+// ---- declared in lab_tables.h ----
+const LabTables& lab_tables() {
+    static const LabTables t = [] {
+        LabTables r;
+        const double XN = 0.950456, ZN = 1.088754, T0 = 0.008856;
+        const double M[3][3] = {{0.412453, 0.357580, 0.180423}, {0.212671, 0.715160, 0.072169}, {0.019334, 0.119193, 0.950227}};
+        const double MI[3][3] = {{3.240479, -1.53715, -0.498535}, {-0.969256, 1.875991, 0.041556}, {0.055648, -0.204043, 1.057311}};
+        const double wp[3] = {XN, 1.0, ZN};
+        const double f_thresh = 7.787 * T0 + 16.0 / 116.0, l_thresh = T0 * 903.3;
+        r.cbrt_tab.resize(CBRT_N);
+        for (int i = 0; i < CBRT_N; ++i) {
+            const double x = (double)i / (double)(CBRT_N - 1);
+            const double f = x > T0 ? std::cbrt(x) : 7.787 * x + 16.0 / 116.0;
+            r.cbrt_tab[i] = (int)std::nearbyint((double)(1 << F_BITS) * f);
+        }
+        for (int q = 0; q < 3; ++q) {
+            double row[3];
+            for (int j = 0; j < 3; ++j) row[j] = M[q][j] / wp[q];
+            const double s = (row[0] + row[1]) + row[2];
+            long c[3], sum = 0;
+            int big = 0;
+            for (int j = 0; j < 3; ++j) {                     // (B, G, R) order: column 2 - j of the RGB matrix
+                c[j] = (long)std::nearbyint(row[2 - j] / s * (double)(1 << COEF_BITS));
+                sum += c[j];
+                if (c[j] > c[big]) big = j;
+            }
+            c[big] += (1l << COEF_BITS) - sum;
+            for (int j = 0; j < 3; ++j) r.fwd.coef[3 * q + j] = (int)c[j];
+        }
+        r.fwd.l_scale = (int)std::nearbyint(116.0 * 2.55 * (double)(1 << L_SCALE_BITS));
+        r.fwd.l_offset = (int)std::nearbyint(16.0 * 2.55 * (double)(1 << (F_BITS + L_SCALE_BITS)));
+        r.t256.resize(1024);
+        for (int i = 0; i < 256; ++i) {
+            const double L = (double)i * 100.0 / 255.0;
+            const double y_low = L / 903.3;
+            const double fy = L <= l_thresh ? 7.787 * y_low + 16.0 / 116.0 : (L + 16.0) / 116.0;
+            const double yl = L <= l_thresh ? y_low : fy * fy * fy;
+            const double ab = (double)i - 128.0;
+            r.t256[i] = (int)std::nearbyint(fy * (double)(1 << F_BITS));
+            r.t256[256 + i] = (int)std::nearbyint(yl * (double)(1 << F_BITS));
+            r.t256[512 + i] = (int)std::nearbyint(ab / 500.0 * (double)(1 << F_BITS));
+            r.t256[768 + i] = (int)std::nearbyint(ab / 200.0 * (double)(1 << F_BITS));
+        }
+        for (int q = 0; q < 3; ++q)                           // rows B, G, R
+            for (int j = 0; j < 3; ++j)
+                r.inv.coef[3 * q + j] = (int)std::nearbyint(MI[2 - q][j] * wp[j] * 255.0 * (double)(1 << INV_COEF_BITS));
+        r.inv.thr = (int)std::nearbyint(f_thresh * (double)(1 << F_BITS));
+        r.inv.c16 = (int)std::nearbyint(16.0 / 116.0 * (double)(1 << F_BITS));
+        r.inv.kinv = (int)std::nearbyint((double)(1 << F_BITS) / 7.787);
+        return r;
+    }();
+    return t;
+}
+
+DeviceLab device_lab() {
+    int dev = 0;
+    FW_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DeviceLab& d = g_lab[dev];
+    if (!d.cbrt_tab) d.cbrt_tab = upload(lab_tables().cbrt_tab);
+    if (!d.t256) d.t256 = upload(lab_tables().t256);
+    return d;
+}
+
 }  // namespace fw
 
 using namespace fw;

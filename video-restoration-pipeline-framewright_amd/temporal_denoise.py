@@ -24,11 +24,15 @@ recommendations, all from fw_frame_stats_u8's per-frame histogram and Laplacian 
 `DeviceTemporalConsistencyFilter` is phase 4 (`TemporalConsistencyFilter`, :839-1061: fw_flow_accumulate_affine_u8,
 fw_add_weighted_u8), followed by `_estimate_noise_reduction` (:1734-1788).  tests/temporal_chain_ref.py is the contract of the new
 kernels and of the host arithmetic; cv2 parity unpinned.
+
+`DeviceFlickerReducer` is phase 2, the reference's `FlickerReducer` (:480-836) on its Python path, `_apply_python_deflicker`
+(:764-836): brightness normalisation in 8-bit gamma Lab (csrc/flicker.hip: fw_lab_l_sums_u8, fw_deflicker_lab_u8), held bit for bit
+to tests/flicker_ref.py; cv2 parity unpinned.  It is opt-in: `DeviceTemporalDenoiser(config, device_flicker=True)` deflickers every
+input frame on the device as it is uploaded.  Without the flag nothing changes: `denoise_clip(frames, deflicker_fn=...)` stays the
+seam for a host function from the list of frames to the list of deflickered frames, and without either no frame is deflickered.
 Not built:
-  - flicker REDUCTION (phase 2).  The reference's first choice is the external ffmpeg `deflicker` filter, and its fallback needs
-    gamma-corrected 8-bit Lab, which the non-local-means colour tables (linear Lab) do not provide.  `denoise_clip(frames,
-    deflicker_fn=...)` is the seam: a host function from the list of frames to the list of deflickered frames.  The flicker
-    METRICS of the analysis are computed.
+  - the external ffmpeg `deflicker` filter, the reference's first choice for phase 2 (it works on swscale's YUV planes; ffmpeg
+    is not available where this is built and nothing here can restate it).
   - `AutoTemporalDenoiser`: its default preset asks for DIS flow, which `DeviceFlowEstimator` refuses.
 """
 from __future__ import annotations
@@ -830,6 +834,136 @@ class DeviceClipAnalyzer:
         return analysis
 
 
+class DeviceFlickerReducer:
+    """`FlickerReducer` (temporal_denoise.py:480-836) on one GPU, on the reference's Python path `_apply_python_deflicker`
+    (:764-836); the ffmpeg `deflicker` filter it tries first is not built, so this path is the behaviour, not the fallback.
+
+    target = np.median of the mean gray level of frames[::10][:50] (fw_frame_stats_u8's histograms); per frame, L of 8-bit gamma Lab
+    becomes clip(L + clip(target - mean L, -20, 20) * 0.5, 0, 255), truncated, and the frame returns to BGR.  The reference's quirk
+    is kept: the target is a GRAY brightness, the frame's own value a mean of L.  For each batch of at most `chunk_size` resident
+    frames the host waits once for the L sums (fw_lab_l_sums_u8), builds the 256-byte maps in float64 - what NumPy >= 2 computes for
+    `l.astype(np.float32) + np.float64 scalar` - uploads them and launches fw_deflicker_lab_u8.  The mode changes no pixel on this
+    path (it only chose ffmpeg parameters); `reduce_flicker` reports it as the reference does."""
+
+    def __init__(self, mode: FlickerMode = FlickerMode.ADAPTIVE, preserve_brightness_changes: bool = True, gpu_id: int = 0,
+                 chunk_size: int = 50):
+        if chunk_size < 1:
+            raise ValueError(f"chunk_size must be >= 1, got {chunk_size}")
+        self.mode, self.preserve_brightness_changes = FlickerMode(mode), bool(preserve_brightness_changes)
+        self.gpu_id, self.chunk_size = int(gpu_id), int(chunk_size)
+        self._detected_severity: Optional[float] = None
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self._analyzer = DeviceClipAnalyzer(TemporalDenoiseConfig(gpu_id=self.gpu_id, chunk_size=max(10, self.chunk_size)))
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.gpu_id)
+
+    def analyze_flicker(self, frames: Sequence[np.ndarray], sample_rate: int = 1, max_samples: int = 200) -> Dict[str, Any]:
+        """`analyze_flicker` (:518-625) of a clip of uint8 BGR frames; only the sampled frames are uploaded.  The severity is
+        remembered: it resolves ADAPTIVE in `reduce_flicker`."""
+        frames = _check_clip(frames)
+        if sample_rate < 1:
+            raise ValueError(f"sample_rate must be >= 1, got {sample_rate}")
+        picked = frames[::sample_rate][:max_samples] if len(frames) >= 3 else []
+        metrics = flicker_metrics_from_brightness([brightness_from_hist(h) for h in self._analyzer.frame_stats(picked)[0]], 1, max_samples)
+        self._detected_severity = metrics["severity"]
+        return metrics
+
+    def resolved_mode(self) -> FlickerMode:
+        """:660-668."""
+        if self.mode == FlickerMode.ADAPTIVE and self._detected_severity is not None:
+            s = self._detected_severity
+            return FlickerMode.LIGHT if s < 0.1 else FlickerMode.MEDIUM if s < 0.3 else FlickerMode.AGGRESSIVE
+        return self.mode
+
+    @staticmethod
+    def l_luts(l_sums: Sequence[int], n_pixels: int, target) -> np.ndarray:
+        """uint8 [count][256]: the map of each frame's L plane (:825-832), float64 throughout, truncated."""
+        levels = np.arange(256, dtype=np.float64)
+        out = np.empty((len(l_sums), 256), np.uint8)
+        for k, s in enumerate(l_sums):
+            adjustment = np.clip(target - int(s) / int(n_pixels), -20, 20)
+            out[k] = np.clip(levels + adjustment * 0.5, 0, 255).astype(np.uint8)
+        return out
+
+    def target_brightness(self, frames: Sequence[np.ndarray]):
+        """:806-814 for a clip of numpy frames: only frames[::10][:50] are uploaded."""
+        picked = _check_clip(list(frames)[::10][:50])
+        return np.median([brightness_from_hist(h) for h in self._analyzer.frame_stats(picked)[0]])
+
+    @_lib.on_tensor_device
+    def target_brightness_device(self, devs):
+        """The same from resident frames (a list, or a count x H x W x 3 stack)."""
+        import torch
+        picked = list(devs)[::10][:50]
+        return np.median([brightness_from_hist(h) for h in self._analyzer.stats_device(torch.stack(picked))[0]])
+
+    @_lib.on_tensor_device
+    def deflicker_batch_device(self, batch, target, out=None):
+        """One batch: a uint8 count x H x W x 3 BGR device tensor -> the deflickered batch (`out`, which may be `batch` itself, or a
+        new tensor).  One wait (the L sums), one upload of count x 256 bytes, two launches."""
+        import torch
+        if batch.dtype != torch.uint8 or batch.dim() != 4 or batch.shape[3] != 3 or not batch.is_cuda or batch.shape[0] < 1:
+            raise ValueError("flicker reduction expects a uint8 count x H x W x 3 BGR device tensor")
+        batch = batch.contiguous()
+        dev = batch.device
+        count, h, w = (int(v) for v in batch.shape[:3])
+        if out is None:
+            out = torch.empty_like(batch)
+        elif out.shape != batch.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+            raise ValueError("flicker reduction: `out` must be a contiguous uint8 device tensor of the batch's shape")
+        sums = torch.empty(count, dtype=torch.int64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(self._lib.fw_lab_l_sums_u8(C.c_void_p(batch.data_ptr()), count, h, w, C.c_void_p(sums.data_ptr()), st))
+        torch.cuda.current_stream(dev).synchronize()
+        luts = torch.from_numpy(self.l_luts(sums.cpu().numpy().tolist(), h * w, target)).to(dev)
+        _lib.check(self._lib.fw_deflicker_lab_u8(C.c_void_p(batch.data_ptr()), count, h, w, C.c_void_p(luts.data_ptr()),
+                                                 C.c_void_p(out.data_ptr()), st))
+        # `luts` is freed when this returns; the caching allocator hands the block out again on this stream only, behind the launch
+        return out
+
+    @_lib.on_tensor_device
+    def reduce_flicker_device(self, devs, target=None):
+        """Resident uint8 BGR frames in - a list of H x W x 3 tensors or a count x H x W x 3 stack - resident deflickered frames out, in
+        the same form.  `target` defaults to the one these frames give (frames[::10][:50]); a caller that streams a clip through in
+        pieces passes the whole clip's."""
+        import torch
+        stacked = isinstance(devs, torch.Tensor)
+        frames = devs if stacked else list(devs)
+        if len(frames) == 0:
+            return devs if stacked else []
+        if target is None:
+            target = self.target_brightness_device(frames)
+        outs = []
+        for s in range(0, len(frames), self.chunk_size):
+            part = frames[s:s + self.chunk_size]
+            outs.append(self.deflicker_batch_device(part if stacked else torch.stack(part), target))
+        if stacked:
+            return torch.cat(outs) if len(outs) > 1 else outs[0]
+        return [f for o in outs for f in o.unbind(0)]
+
+    def reduce_flicker(self, frames: Sequence[np.ndarray]) -> Tuple[List[np.ndarray], Dict[str, Any]]:
+        """The host form of `reduce_flicker` (:626-700): numpy frames in, (numpy frames, the reference's result dict) out.  The clip
+        is uploaded `chunk_size` frames at a time; the target comes from the sampled frames only."""
+        import torch
+        frames = _check_clip(frames)
+        if not frames:
+            return [], {"frames_processed": 0, "mode_used": None}
+        mode = self.resolved_mode()
+        target = self.target_brightness(frames)
+        dev = self._dev()
+        out: List[np.ndarray] = []
+        for s in range(0, len(frames), self.chunk_size):
+            with torch.cuda.device(dev):
+                batch = torch.from_numpy(np.stack(frames[s:s + self.chunk_size])).to(dev)
+                res = self.deflicker_batch_device(batch, target, out=batch)
+                torch.cuda.current_stream(dev).synchronize()
+                out += list(res.cpu().numpy())
+        return out, {"success": True, "frames_processed": len(out), "method": "python_brightness_normalization", "mode_used": mode.value}
+
+
 class DeviceTemporalConsistencyFilter:
     """Phase 4 of the reference, `TemporalConsistencyFilter` (temporal_denoise.py:839-1061), on one GPU.
 
@@ -912,13 +1046,18 @@ class DeviceTemporalDenoiser:
     """`TemporalDenoiser` (temporal_denoise.py:1064-1424) on one GPU: analysis, the accumulate -> non-local means -> edge-preserve
     chain, the temporal-consistency pass and the noise-reduction estimate, with the clip on the device from the upload of a frame to
     the download of its result.  The reference hands PNG directories from phase to phase (lossless: the same bytes).  Flicker
-    reduction is the caller's (`deflicker_fn`, see the module docstring)."""
+    reduction (phase 2) is opt-in: with `device_flicker=True` and `config.enable_flicker_reduction` every input frame is deflickered on
+    the device as it is uploaded (`DeviceFlickerReducer`), with the target of the whole clip's samples; otherwise it is the
+    caller's (`deflicker_fn`, see the module docstring) or does not happen."""
 
     NOISE_REDUCTION_FRAMES = 20     # `_estimate_noise_reduction` reads the first 20 (:1751)
 
-    def __init__(self, config: Optional[TemporalDenoiseConfig] = None):
+    def __init__(self, config: Optional[TemporalDenoiseConfig] = None, device_flicker: bool = False):
         self.config = config or TemporalDenoiseConfig()
         c = self.config
+        self.device_flicker = bool(device_flicker)
+        self._flicker_reducer = DeviceFlickerReducer(mode=c.flicker_mode, gpu_id=c.gpu_id, chunk_size=c.chunk_size) \
+            if self.device_flicker else None
         self._analyzer = DeviceClipAnalyzer(c)
         self._flow_estimator = DeviceFlowEstimator(method=c.optical_flow_method, gpu_id=c.gpu_id)
         self._accumulator = DeviceTemporalAccumulator(temporal_weight_decay=c.temporal_weight_decay, gpu_id=c.gpu_id,
@@ -942,8 +1081,13 @@ class DeviceTemporalDenoiser:
         computed from the same windows whatever `chunk_size` is - the output does not depend on it.  Scene-cut indices at or beyond
         the clip's end (`scene_changes_from_hists`) match no frame in the reference and are dropped here.
         Progress: the reference's fractions at the phase boundaries and per chunk of phase 3; phase 4 runs interleaved with it, so its
-        per-frame fractions are not reported."""
+        per-frame fractions are not reported.
+        With `device_flicker` (and `config.enable_flicker_reduction`) the analysis reads the original frames, the target brightness
+        comes from the whole clip's samples before phase 3 starts, and each input frame is deflickered on the device when it is
+        uploaded: nothing returns to the host between the phases.  `deflicker_fn` together with `device_flicker` is a ValueError."""
         import torch
+        if deflicker_fn is not None and self.device_flicker:
+            raise ValueError("pass deflicker_fn (a host hook) or build the denoiser with device_flicker=True, not both")
         start = time.time()
         c = self.config
         tell = progress_callback or (lambda p: None)
@@ -962,6 +1106,10 @@ class DeviceTemporalDenoiser:
             if len(current) != n or current[0].shape != frames[0].shape:
                 raise ValueError("deflicker_fn must return as many frames, of the same size, as it was given")
             result.flicker_reduction_applied = True
+        target = None
+        if c.enable_flicker_reduction and self.device_flicker:
+            target = self._flicker_reducer.target_brightness(frames)
+            result.flicker_reduction_applied = True
         tell(0.25)
         cuts = {i for i in self._scene_changes if i < n}
         r, step = c.temporal_radius, c.chunk_size
@@ -977,9 +1125,14 @@ class DeviceTemporalDenoiser:
             with torch.cuda.device(dev):
                 for i in [k for k in inputs if k < s - r]:
                     del inputs[i]
-                for i in range(max(0, s - r), min(n, e + r)):
-                    if i not in inputs:
+                fresh = [i for i in range(max(0, s - r), min(n, e + r)) if i not in inputs]
+                if target is None:
+                    for i in fresh:
                         inputs[i] = torch.from_numpy(current[i]).to(dev)
+                elif fresh:
+                    batch = torch.from_numpy(np.stack([current[i] for i in fresh])).to(dev)
+                    for i, t in zip(fresh, self._flicker_reducer.reduce_flicker_device(batch, target).unbind(0)):
+                        inputs[i] = t
                 for i in range(s, e):
                     lo, hi = (i, i + 1) if i in cuts else (max(0, i - r), min(n, i + r + 1))
                     window = [inputs[k] for k in range(lo, hi)]
@@ -1030,8 +1183,9 @@ class DeviceTemporalDenoiser:
 
 
 def create_temporal_denoiser(strength: float = 0.5, temporal_radius: int = 3, enable_optical_flow: bool = True,
-                             enable_flicker_reduction: bool = True, gpu_id: int = 0) -> DeviceTemporalDenoiser:
-    """The reference's factory (temporal_denoise.py:1894-1920)."""
+                             enable_flicker_reduction: bool = True, gpu_id: int = 0, device_flicker: bool = False) -> DeviceTemporalDenoiser:
+    """The reference's factory (temporal_denoise.py:1894-1920); `device_flicker` opts into phase 2 on the device."""
     return DeviceTemporalDenoiser(TemporalDenoiseConfig(noise_strength=strength, temporal_radius=temporal_radius,
                                                         enable_optical_flow=enable_optical_flow,
-                                                        enable_flicker_reduction=enable_flicker_reduction, gpu_id=gpu_id))
+                                                        enable_flicker_reduction=enable_flicker_reduction, gpu_id=gpu_id),
+                                  device_flicker=device_flicker)
