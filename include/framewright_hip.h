@@ -243,6 +243,28 @@ int fw_nafnet_denoise_u8(fw_nafnet* net, const uint8_t* in_bgr, int in_loc, int 
 double fw_nafnet_flops(const fw_nafnet* net, int height, int width);
 int fw_nafnet_destroy(fw_nafnet* net);
 
+/* Single steps of a forward on the caller's buffers (tests, tools): the same launches, workspace, mutex and stream ordering as
+ * fw_nafnet_denoise_u8, dispatched by the handle's own switches (FW_NAF_* read at create).
+ * run_block: `key` names a block like fw_nafnet_set_tensor does ("encoders.1.0.", "middle_blks.3.", "decoders.2.1."); stream_f32
+ * is a device fp32 [height][width][c] buffer, updated in place; sca_out (optional, device float[c]) receives the block's SCA
+ * scale.  FW_ERR_INVALID: unknown key, unfinalizable handle, non-positive size.
+ * block_paths: which fused kernels that block dispatches to, as FW_NAF_PATH_* bits.
+ * run_resample: up = 0: the 2x2 stride-2 conv of `level`, src fp32 [height][width][c] -> dst fp32 [height/2][width/2][2c] (even
+ * sides); up = 1: the step INTO `level` (ups[num_levels - 1 - level]): src fp32 [height][width][2c'] of level + 1, 1x1 conv,
+ * PixelShuffle(2), added in place to the skip buffer dst fp32 [2 height][2 width][c'], c' = width << level. */
+#define FW_NAF_PATH_FRONT 1    /* norm1 + conv1 + depthwise + gate in one kernel (c = 64, 128) */
+#define FW_NAF_PATH_TAIL128 2  /* conv3 .. conv5 in one kernel, c = 128 */
+#define FW_NAF_PATH_TAIL64 4   /* conv3 .. conv5 in one kernel, c = 64 */
+#define FW_NAF_PATH_GEMM 8     /* 1x1 convs on the pipelined GEMM kernel (c >= 256) */
+#define FW_NAF_PATH_FUSE_LN 16 /* at least one LayerNorm2d of the block runs inside the staging of the conv that follows it (c = 64, a fused kernel off) */
+int fw_nafnet_run_block(fw_nafnet* net, const char* key, float* stream_f32, int height, int width, float* sca_out, void* stream);
+int fw_nafnet_block_paths(fw_nafnet* net, const char* key, int* flags);
+int fw_nafnet_run_resample(fw_nafnet* net, int level, int up, const float* src_f32, int height, int width, float* dst_f32, void* stream);
+/* NAFNet's pre-processing: uint8 BGR H x W x 3 -> typed [padded_height][padded_width][32], RGB / 255 in channels 0..2, zeros in
+ * channels 3..31 and outside H x W (tap_denoise.py:373-397 + NAFNet.check_image_size). */
+int fw_u8_to_nhwc_padded(int dtype, const uint8_t* in_bgr, int height, int width, int padded_height, int padded_width, void* out,
+                         void* stream);
+
 /* -------------------------------------------------------------------------------------------------
  * TAP driver arithmetic on uint8 frames (all pointers device memory; bit-exact restatements)
  * ------------------------------------------------------------------------------------------------- */

@@ -16,6 +16,7 @@ LIB_PATH = PKG_DIR / "lib" / "libframewright_hip.so"
 FW_OK, FW_ERR_INVALID, FW_ERR_OOM, FW_ERR_HIP, FW_ERR_INTERNAL = 0, 1, 2, 3, 4
 FW_HOST, FW_DEVICE = 0, 1
 FW_DTYPE_BF16, FW_DTYPE_F16 = 0, 1
+FW_NAF_PATH_FRONT, FW_NAF_PATH_TAIL128, FW_NAF_PATH_TAIL64, FW_NAF_PATH_GEMM, FW_NAF_PATH_FUSE_LN = 1, 2, 4, 8, 16
 DTYPES = {"bf16": FW_DTYPE_BF16, "bfloat16": FW_DTYPE_BF16, "f16": FW_DTYPE_F16, "fp16": FW_DTYPE_F16,
           "float16": FW_DTYPE_F16, "half": FW_DTYPE_F16}
 
@@ -26,7 +27,7 @@ EXPORTS = [
     "fw_rrdbnet_workspace_bytes", "fw_rrdbnet_flops", "fw_rrdbnet_profile_enable", "fw_rrdbnet_profile_read",
     "fw_rrdbnet_destroy", "fw_pack_conv3x3", "fw_conv3x3_nhwc",
     "fw_nafnet_create", "fw_nafnet_set_tensor", "fw_nafnet_finalize", "fw_nafnet_denoise_u8", "fw_nafnet_flops",
-    "fw_nafnet_destroy", "fw_u8_crop", "fw_tile_blend_accumulate", "fw_tile_blend_finish", "fw_temporal_average_u8",
+    "fw_nafnet_destroy", "fw_nafnet_run_block", "fw_nafnet_block_paths", "fw_nafnet_run_resample", "fw_u8_to_nhwc_padded", "fw_u8_crop", "fw_tile_blend_accumulate", "fw_tile_blend_finish", "fw_temporal_average_u8",
     "fw_strength_blend_u8",
     "fw_conv3x3_nhwc_ex", "fw_conv3x3_pair_nhwc", "fw_pack_conv_up2x_phase", "fw_conv_up2x_phase_nhwc", "fw_u8_to_rgb_f32", "fw_resize_bilinear_f32", "fw_ifnet_build_x", "fw_unshuffle2_cast",
     "fw_depth_to_space4_f32", "fw_ifnet_accumulate", "fw_ifnet_blend", "fw_unsharp_mask_u8",
@@ -115,6 +116,14 @@ def _declare_tap(lib: C.CDLL) -> None:
     lib.fw_nafnet_flops.argtypes = [vp, i32, i32]
     lib.fw_nafnet_destroy.restype = i32
     lib.fw_nafnet_destroy.argtypes = [vp]
+    lib.fw_nafnet_run_block.restype = i32
+    lib.fw_nafnet_run_block.argtypes = [vp, C.c_char_p, vp, i32, i32, vp, vp]
+    lib.fw_nafnet_block_paths.restype = i32
+    lib.fw_nafnet_block_paths.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
+    lib.fw_nafnet_run_resample.restype = i32
+    lib.fw_nafnet_run_resample.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp]
+    lib.fw_u8_to_nhwc_padded.restype = i32
+    lib.fw_u8_to_nhwc_padded.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp]
     lib.fw_u8_crop.restype = i32
     lib.fw_u8_crop.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.fw_tile_blend_accumulate.restype = i32

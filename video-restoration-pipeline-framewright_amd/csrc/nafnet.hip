@@ -197,8 +197,29 @@ Plan make_plan(const fw_nafnet* n, int H, int W) {
     return p;
 }
 
+// which kernels a block goes to: the one place that decides it, for run_block and for fw_nafnet_block_paths
+struct BlockDispatch {
+    bool front;       // norm1 + conv1 + depthwise conv + gate in one kernel (pw_dw_fused.hip)
+    bool tail128;     // conv3 .. conv5 in one kernel (naf_tail128.hip)
+    bool tail64;      // conv3 .. conv5 in one kernel (nn_ops.hip naf_tail64_kernel)
+    bool gemm;        // conv3 on the pipelined GEMM kernel with SCA-scaled weights (the other 1x1 convs follow their own packed copies)
+    bool fuse_ln;     // a LayerNorm2d left to the unfused path runs inside the staging pass of the GEMM that follows it
+    bool ln_staged() const { return fuse_ln && (!front || !(tail128 || tail64)); }   // ... and at least one is left
+};
+
+BlockDispatch block_dispatch(const fw_nafnet* n, const Block& b) {
+    BlockDispatch d{};
+    d.front = b.front.p != nullptr;
+    d.tail128 = b.tail128.p != nullptr;
+    d.tail64 = !d.tail128 && b.c == 64 && n->fuse_tail;
+    d.gemm = b.w3g.p != nullptr;
+    d.fuse_ln = b.c == 64 && n->fuse_ln;
+    return d;
+}
+
 void run_block(fw_nafnet* n, const Block& b, float* S, int H, int W, char* ws, const Plan& pl, hipStream_t st) {
     const int c = b.c;
+    const BlockDispatch disp = block_dispatch(n, b);
     const long M = (long)H * W;
     void* T1 = ws + pl.T1;
     void* T2 = ws + pl.T2;
@@ -207,10 +228,9 @@ void run_block(fw_nafnet* n, const Block& b, float* S, int H, int W, char* ws, c
     float* sca = (float*)(ws + pl.sca);
     // x = conv1(norm1(inp)); at width 64 (the full-resolution level: four fifths of the LayerNorm bytes) the LayerNorm runs
     // inside the GEMM's staging pass
-    const bool fuse_ln = c == 64 && n->fuse_ln;
+    const bool fuse_ln = disp.fuse_ln;
     PointwiseParams p{};
-    const bool front = b.front.p != nullptr;
-    if (front) {
+    if (disp.front) {
         // norm1, conv1, the depthwise conv and the gate in one kernel: the 2c-channel tensor stays in LDS (pw_dw_fused.hip)
         PwDwParams f{};
         f.x = S; f.ldx = c; f.H = H; f.W = W; f.cin = c; f.ln_eps = 1e-6f; f.blocks = b.front.p; f.n_chunks = 2 * c / 64; f.mode = PWDW_GATE_MUL;
@@ -231,14 +251,14 @@ void run_block(fw_nafnet* n, const Block& b, float* S, int H, int W, char* ws, c
     launch_dwconv3x3_gate(n->dt, T2, H, W, c, (const float*)b.wdw.p, (const float*)b.bdw.p, T3, csum, st);
     launch_sca(csum, dwconv_blocks(H, W, c), M, c, (const float*)b.wsca.p, (const float*)b.bsca.p, sca, st);
     }
-    if (b.tail128.p) {
+    if (disp.tail128) {
         // conv3 .. conv5 of a 128-channel block in one pass: its 128 KB of weights stream through LDS (naf_tail128.hip)
         NafTail128Params t{};
         t.x = T3; t.ldx = c; t.stream = S; t.lds_ = c; t.M = M; t.ln_eps = 1e-6f; t.blocks = b.tail128.p; t.w3_scratch = ws + pl.w3s;
         launch_naf_tail128(n->dt, t, sca, st);
         return;
     }
-    if (c == 64 && n->fuse_tail) {
+    if (disp.tail64) {
         // the rest of the block in one pass over the stream (nn_ops.hip naf_tail64_kernel)
         launch_naf_tail64(n->dt, T3, sca, S, M, b.w3.p, (const float*)b.b3.p, (const float*)b.beta.p, (const float*)b.n2w.p,
                           (const float*)b.n2b.p, 1e-6f, b.w4.p, (const float*)b.b4.p, b.w5.p, (const float*)b.b5.p,
@@ -249,7 +269,7 @@ void run_block(fw_nafnet* n, const Block& b, float* S, int H, int W, char* ws, c
     p = PointwiseParams{};
     p.a = T3; p.lda = c; p.M = M; p.K = c; p.a_scale = sca; p.wpk = b.w3.p; p.bias = (const float*)b.b3.p; p.N_tiles = c / 32;
     p.mode = PW_RESIDUAL; p.out_f32 = S; p.res_f32 = S; p.ldf = c; p.chan_scale = (const float*)b.beta.p;
-    if (b.w3g.p) {   // the GEMM kernel does not touch its activations: the SCA factors go into a scaled copy of the weights
+    if (disp.gemm) {   // the GEMM kernel does not touch its activations: the SCA factors go into a scaled copy of the weights
         launch_pw16_scale_weights(n->dt, b.w3g.p, sca, c, c, ws + pl.w3s, st);
         p.wpk16 = ws + pl.w3s;
         p.a_scale = nullptr;
@@ -272,6 +292,27 @@ void run_block(fw_nafnet* n, const Block& b, float* S, int H, int W, char* ws, c
     launch_pointwise(n->dt, p, st);
 }
 
+// down conv of level l: 2x2 stride 2, c -> 2c, src fp32 [h][w][c] -> dst fp32 [h/2][w/2][2c]
+PointwiseParams down_params(const fw_nafnet* n, int l, const float* src, int h, int w, float* dst) {
+    const int c = n->width << l;
+    PointwiseParams p{};
+    p.a = src; p.a_f32 = 1; p.lda = c; p.M = (long)(h / 2) * (w / 2); p.K = 4 * c; p.gather2x2 = 1; p.Win = w; p.Cin = c;
+    p.wpk = n->downs[l].w.p; p.bias = (const float*)n->downs[l].b.p; p.N_tiles = 2 * c / 32; p.mode = PW_STORE;
+    p.out_f32 = dst; p.ldf = 2 * c;
+    return p;
+}
+
+// up step into level l (ups[nlev - 1 - l]): x = PixelShuffle(conv1x1(x)) + skip, written in place into the skip buffer;
+// src fp32 [h][w][chi] of level l + 1, skip fp32 [2h][2w][chi / 2]
+PointwiseParams up_params(const fw_nafnet* n, int l, const float* src, int h, int w, float* skip) {
+    const int chi = n->width << (l + 1);    // channels of the coarser level
+    PointwiseParams p{};
+    p.a = src; p.a_f32 = 1; p.lda = chi; p.M = (long)h * w; p.K = chi; p.Win = w;
+    p.wpk = n->ups[n->nlev - 1 - l].w.p; p.bias = nullptr; p.N_tiles = 2 * chi / 32; p.mode = PW_SHUFFLE_UP;
+    p.out_f32 = skip; p.res_f32 = skip; p.ldf = chi / 2;
+    return p;
+}
+
 void forward(fw_nafnet* n, const uint8_t* d_in, int H, int W, uint8_t* d_out, float* d_rgb, hipStream_t st) {
     const Plan pl = make_plan(n, H, W);
     char* ws = (char*)n->ws.p;
@@ -292,26 +333,14 @@ void forward(fw_nafnet* n, const uint8_t* d_in, int H, int W, uint8_t* d_out, fl
     int h = Hp, w = Wp;
     for (int l = 0; l < n->nlev; ++l) {
         for (const Block& b : n->encoders[l]) run_block(n, b, S[l], h, w, ws, pl, st);
-        // down: 2x2 stride 2, c -> 2c
-        const int c = n->width << l;
-        PointwiseParams p{};
-        p.a = S[l]; p.a_f32 = 1; p.lda = c; p.M = (long)(h / 2) * (w / 2); p.K = 4 * c; p.gather2x2 = 1; p.Win = w; p.Cin = c;
-        p.wpk = n->downs[l].w.p; p.bias = (const float*)n->downs[l].b.p; p.N_tiles = 2 * c / 32; p.mode = PW_STORE;
-        p.out_f32 = S[l + 1]; p.ldf = 2 * c;
-        launch_pointwise(n->dt, p, st);
+        launch_pointwise(n->dt, down_params(n, l, S[l], h, w, S[l + 1]), st);
         h /= 2;
         w /= 2;
     }
     for (const Block& b : n->middle_blks) run_block(n, b, S[n->nlev], h, w, ws, pl, st);
     for (int i = 0; i < n->nlev; ++i) {
         const int l = n->nlev - 1 - i;          // target level
-        const int chi = n->width << (l + 1);    // channels of the coarser level
-        // x = PixelShuffle(conv1x1(x)) + skip, written in place into the skip buffer
-        PointwiseParams p{};
-        p.a = S[l + 1]; p.a_f32 = 1; p.lda = chi; p.M = (long)h * w; p.K = chi; p.Win = w;
-        p.wpk = n->ups[i].w.p; p.bias = nullptr; p.N_tiles = 2 * chi / 32; p.mode = PW_SHUFFLE_UP;
-        p.out_f32 = S[l]; p.res_f32 = S[l]; p.ldf = chi / 2;
-        launch_pointwise(n->dt, p, st);
+        launch_pointwise(n->dt, up_params(n, l, S[l + 1], h, w, S[l]), st);
         h *= 2;
         w *= 2;
         for (const Block& b : n->decoders[i]) run_block(n, b, S[l], h, w, ws, pl, st);
@@ -503,6 +532,67 @@ int fw_nafnet_denoise_u8(fw_nafnet* n, const uint8_t* in_bgr, int in_loc, int H,
             FW_HIP_CHECK(hipStreamSynchronize(st));
         }
     });
+}
+
+// ---- single steps of a forward, for tests and tools: what the engine runs for one block / one level change, on the caller's stream buffer ----
+int fw_nafnet_run_block(fw_nafnet* n, const char* key_c, float* stream_f32, int H, int W, float* sca_out, void* stream) {
+    if (!n || !key_c || !stream_f32) return fail(FW_ERR_INVALID, "fw_nafnet_run_block: NULL argument");
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(FW_ERR_INVALID, "fw_nafnet_run_block: bad size");
+    std::string rest;
+    Block* bl = find_block(n, key_c, &rest);
+    if (!bl || !rest.empty()) return fail(FW_ERR_INVALID, std::string("fw_nafnet_run_block: unknown block '") + key_c + "'");
+    int rc = fw_nafnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        // the workspace of the forward in which this block sees H x W pixels: level l = log2(c / width), frame (H << l) x (W << l)
+        int l = 0;
+        while ((n->width << l) < bl->c) ++l;
+        if (((long)H << l) > 16384 || ((long)W << l) > 16384) throw Error(FW_ERR_INVALID, "fw_nafnet_run_block: size beyond the largest frame");
+        const Plan pl = make_plan(n, H << l, W << l);
+        ensure_workspace(n->ws, pl.total, &n->graphs);
+        run_block(n, *bl, stream_f32, H, W, (char*)n->ws.p, pl, st);
+        if (sca_out)
+            FW_HIP_CHECK(hipMemcpyAsync(sca_out, (char*)n->ws.p + pl.sca, (size_t)bl->c * 4, hipMemcpyDeviceToDevice, st));
+    });
+}
+
+int fw_nafnet_block_paths(fw_nafnet* n, const char* key_c, int* flags) {
+    if (!n || !key_c || !flags) return fail(FW_ERR_INVALID, "fw_nafnet_block_paths: NULL argument");
+    std::string rest;
+    Block* bl = find_block(n, key_c, &rest);
+    if (!bl || !rest.empty()) return fail(FW_ERR_INVALID, std::string("fw_nafnet_block_paths: unknown block '") + key_c + "'");
+    int rc = fw_nafnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    std::lock_guard<std::mutex> lk(n->mu);
+    const BlockDispatch d = block_dispatch(n, *bl);   // what run_block consults
+    *flags = (d.front ? FW_NAF_PATH_FRONT : 0) | (d.tail128 ? FW_NAF_PATH_TAIL128 : 0) | (d.tail64 ? FW_NAF_PATH_TAIL64 : 0) |
+             (d.gemm ? FW_NAF_PATH_GEMM : 0) | (d.ln_staged() ? FW_NAF_PATH_FUSE_LN : 0);
+    return FW_OK;
+}
+
+int fw_nafnet_run_resample(fw_nafnet* n, int level, int up, const float* src_f32, int H, int W, float* dst_f32, void* stream) {
+    if (!n || !src_f32 || !dst_f32) return fail(FW_ERR_INVALID, "fw_nafnet_run_resample: NULL argument");
+    if (level < 0 || level >= n->nlev || H < 1 || W < 1 || H > 16384 || W > 16384) return fail(FW_ERR_INVALID, "fw_nafnet_run_resample: bad level or size");
+    if (!up && ((H | W) & 1)) return fail(FW_ERR_INVALID, "fw_nafnet_run_resample: the down conv needs even sides");
+    int rc = fw_nafnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        launch_pointwise(n->dt, up ? up_params(n, level, src_f32, H, W, dst_f32) : down_params(n, level, src_f32, H, W, dst_f32), st);
+    });
+}
+
+int fw_u8_to_nhwc_padded(int dtype, const uint8_t* in_bgr, int H, int W, int Hp, int Wp, void* out, void* stream) {
+    if (!in_bgr || !out || H < 1 || W < 1 || Hp < H || Wp < W) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc_padded: bad argument");
+    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc_padded: bad dtype");
+    return guarded([&] { launch_u8_to_nhwc_padded((DType)dtype, in_bgr, H, W, Hp, Wp, out, (hipStream_t)stream); });
 }
 
 double fw_nafnet_flops(const fw_nafnet* n, int H, int W) {

@@ -156,6 +156,50 @@ class NAFNetEngine:
             C.c_void_p(out_rgb_f32.data_ptr()) if out_rgb_f32 is not None else None, C.c_void_p(stream)))
         return out if out is not None else out_rgb_f32
 
+    # ---- single steps of a forward on the caller's buffers (tests, tools) ----
+    @_lib.on_tensor_device
+    def run_block(self, stream_f32, key: str, sca_out=None):
+        """One NAFBlock (``key`` as in the state dict: "encoders.0.0.", "middle_blks.0.") in place on a contiguous float32 CUDA
+        tensor H x W x c, dispatched as in a forward; ``sca_out`` (float32 CUDA, c) receives the block's SCA scale."""
+        import torch
+        if stream_f32.dtype != torch.float32 or not stream_f32.is_cuda or stream_f32.dim() != 3 or not stream_f32.is_contiguous():
+            raise ValueError("run_block expects a contiguous float32 CUDA tensor H x W x c")
+        parts, n = key.split("."), len(self.args["enc_blk_nums"])
+        level = {"encoders": lambda: int(parts[1]), "middle_blks": lambda: n, "decoders": lambda: n - 1 - int(parts[1])}.get(parts[0], lambda: -1)()
+        if not 0 <= level <= n or int(stream_f32.shape[2]) != self.args["width"] << level:
+            raise ValueError(f"run_block: {key!r} does not name a block of {int(stream_f32.shape[2])} channels")
+        if sca_out is not None and (sca_out.dtype != torch.float32 or not sca_out.is_cuda or sca_out.numel() < stream_f32.shape[2]):
+            raise ValueError("sca_out must be a float32 CUDA tensor of c elements")
+        st = torch.cuda.current_stream(stream_f32.device).cuda_stream
+        _lib.check(self._lib.fw_nafnet_run_block(self._h, key.encode(), C.c_void_p(stream_f32.data_ptr()), int(stream_f32.shape[0]),
+                                                 int(stream_f32.shape[1]), C.c_void_p(sca_out.data_ptr()) if sca_out is not None else None,
+                                                 C.c_void_p(st)))
+        return stream_f32
+
+    def block_paths(self, key: str) -> int:
+        """FW_NAF_PATH_* bits of the kernels that block dispatches to."""
+        flags = C.c_int(0)
+        _lib.check(self._lib.fw_nafnet_block_paths(self._h, key.encode(), C.byref(flags)))
+        return flags.value
+
+    @_lib.on_tensor_device
+    def run_resample(self, src_f32, level: int, up: bool, dst_f32):
+        """The down conv of ``level`` (src H x W x c -> dst H/2 x W/2 x 2c) or the up step into ``level`` (src H x W x 2c', 1x1 conv,
+        PixelShuffle, added in place to dst 2H x 2W x c'); contiguous float32 CUDA tensors."""
+        import torch
+        for t in (src_f32, dst_f32):
+            if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError("run_resample expects contiguous float32 CUDA tensors H x W x c")
+        c = self.args["width"] << int(level)
+        h, w = int(src_f32.shape[0]), int(src_f32.shape[1])
+        want = ((h, w, 2 * c), (2 * h, 2 * w, c)) if up else ((h, w, c), (h // 2, w // 2, 2 * c))
+        if not 0 <= int(level) < len(self.args["enc_blk_nums"]) or (tuple(src_f32.shape), tuple(dst_f32.shape)) != want or (not up and (h | w) & 1):
+            raise ValueError(f"run_resample: level {level} {'up' if up else 'down'} needs shapes {want}")
+        st = torch.cuda.current_stream(src_f32.device).cuda_stream
+        _lib.check(self._lib.fw_nafnet_run_resample(self._h, int(level), 1 if up else 0, C.c_void_p(src_f32.data_ptr()), int(src_f32.shape[0]),
+                                                    int(src_f32.shape[1]), C.c_void_p(dst_f32.data_ptr()), C.c_void_p(st)))
+        return dst_f32
+
     def flops(self, h: int, w: int) -> float:
         return float(self._lib.fw_nafnet_flops(self._h, h, w))
 
