@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic (build with FW_EXTRA_CXXFLAGS=-DFW_PAIR_STAMP): where the waves of the fused pair kernel and of the
-64-channel residual conv spend their cycles.  Shares only — a stamped build is slower than the product build."""
+64-channel residual conv spend their cycles.  Shares only — a stamped build is slower than the product build.
+The pair section reads the ring kernel's eight slots: run it with FW_PAIR_SLIDE=0.  The window kernel (conv3x3_pair_slide.hip) has
+sixteen slots of its own, printed per tile by tools/pair_tile_phases.py."""
 import ctypes as C, json, os, sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))

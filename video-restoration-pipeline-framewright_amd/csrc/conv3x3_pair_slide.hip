@@ -14,8 +14,9 @@
 // halo rows (2w .. 2w+4) of B fragments instead of four, conv_a reading them one row lower than conv_b.
 // The x_a tile keeps the standard 18-row halo format with row 0 = image row 16 ty - 2: rows 0,1 come from the carry buffer
 // (wave 7 copies rows 16,17 of the tile there after the x_a item), rows 2..17 are this tile's conv_a.  A workgroup whose
-// run starts in the middle of a column first runs the tile above it with conv_a only (no conv_b MFMAs, no x_a item, no
-// stores) to obtain the carry rows; at the top of a column the carry is zero (= conv_b's zero padding).
+// run starts in the middle of a column first computes the last two conv_a rows of the tile above it (the warm-up below: four
+// input rows per chunk and conv_a's weights, all chunks in flight at once) to obtain the carry rows; at the top of a column
+// the carry is zero (= conv_b's zero padding).
 #include <cstdlib>
 #include <type_traits>
 #include "fw_internal.h"
@@ -36,12 +37,41 @@ constexpr int PS_EXTRA = PS_PIECES - ACT_ITERS * NWAVES * 64;  // 24 pieces beyo
 constexpr int PS_REGION = 41 * 64;     // pieces per activation stage
 constexpr int PS_CARRY = 2 * ROW_PIECES;  // two x_a rows
 
+constexpr int PS_WARM_ROWS = 4;                           // input rows 16 ty - 3 .. 16 ty: what conv_a rows 16 ty - 2, 16 ty - 1 read
+constexpr int PS_WARM_PIECES = PS_WARM_ROWS * ROW_PIECES;  // 544 per chunk
+constexpr int PS_WARM_KIB = 9;                            // DMA instructions per chunk: a batch of 5 and a batch of 4 (32 pad pieces)
+constexpr int PS_WARM_SLOT = PS_WARM_KIB * 64;            // pieces per chunk slot in the second activation stage
+constexpr int PS_WARM_CHUNKS = 4;                         // chunk slots: a warm-up batch
+
 struct SlideSmem {
     static constexpr int W_REGION = 2 * W_FRAGS * 64;
     static constexpr int W_BASE = 2 * PS_REGION;
     static constexpr int CARRY = W_BASE + 2 * W_REGION;
-    static constexpr int TOTAL = CARRY + PS_CARRY;  // 10128 pieces = 162048 bytes
+    static constexpr int BIAS = CARRY + PS_CARRY;  // 64 floats: bias_a, bias_b
+    static constexpr int TOTAL = BIAS + 16;        // 10144 pieces = 162304 bytes
 };
+static_assert(PS_WARM_CHUNKS * PS_WARM_SLOT <= PS_REGION && 2 * PS_WARM_CHUNKS == NWAVES, "warm-up batch: two waves per chunk slot");
+
+// Phase slots of the stamped build (-DFW_PAIR_STAMP; tools/pair_tile_phases.py prints them per tile): 16 per wave, which is all
+// of stamp_buffer(0).  0 - 9: a tile of the run; 10 - 14: the warm-up; 15: the wave's lifetime in 100 MHz ticks.
+enum {
+    ST_BARRIER = 0, ST_SHARED = 1, ST_XA_ITEM = 2, ST_XA_LDS = 3, ST_SETUP = 4, ST_VMCNT = 5, ST_XA_EPI = 6, ST_XB_EPI = 7,
+    ST_CARRY = 8, ST_FIRST = 9, ST_W_BARRIER = 10, ST_W_MFMA = 11, ST_W_DMA = 12, ST_W_EPI = 13, ST_W_SETUP = 14, ST_LIFE = 15
+};
+#ifdef FW_PAIR_STAMP
+#undef FW_STAMP_INIT
+#undef FW_STAMP_FLUSH
+#define FW_STAMP_INIT()                                                                  \
+    unsigned long long stamp_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();                        \
+    const unsigned long long stamp_rt0 = __builtin_amdgcn_s_memrealtime()
+#define FW_STAMP_FLUSH(buf)                                                                                 \
+    do {                                                                                                    \
+        stamp_acc[ST_LIFE] = __builtin_amdgcn_s_memrealtime() - stamp_rt0;                                  \
+        if ((threadIdx.x & 63) == 0 && (buf))                                                               \
+            for (int k_ = 0; k_ < 16; ++k_) atomicAdd((buf) + (threadIdx.x >> 6) * 16 + k_, stamp_acc[k_]); \
+    } while (0)
+#endif
 static_assert(NWAVES == 8 && RPW == 2 && PS_EXTRA > 0 && PS_EXTRA <= 64, "written for 8 waves of 2 rows");
 static_assert(SlideSmem::TOTAL * 16 <= 160 * 1024, "LDS");
 
@@ -132,9 +162,8 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
 #else
     const int needs_warm = (t_lo % tiles_y) != 0;  // the run starts below the top of a column: conv_a of the tile above first
 #endif
-    const int t_begin = t_lo - needs_warm;
     const int na = p.na;
-    const int nitems = (t_hi - t_lo) * (na + 1) + needs_warm * na;
+    const int nitems = (t_hi - t_lo) * (na + 1);
 
     // ---- per-lane DMA plan: 2560 pieces as five batched KiB per "virtual wave" v, pieces 2560..2583 as one more DMA of wave 0.
     //      FW_DMA_OLD_ONLY: the older wave of every SIMD (waves 0-3) issues the batches of virtual waves 2w and 2w+1 and the
@@ -179,7 +208,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     unsigned f_ok = 0;            // bit bt * ACT_ITERS + i: piece i of batch bt is inside the image; bit 2 * ACT_ITERS: the extra piece
     bool f_all = true;
     const char* f_src = nullptr;  // halo origin (image row R0 - 2, column ox - 1) of (tile f_t, chunk f_c)
-    int f_t = t_begin, f_c = 0;
+    int f_t = t_lo, f_c = 0;
     auto plan_tile = [&]() {
         int R0, ox;
         origin(f_t, &R0, &ox);
@@ -234,13 +263,14 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             f_src += chunk_bytes;
         }
     };
-    auto issue_w = [&](int j, int ws) {
+    // halves: bit 0 = conv_a's fragments, bit 1 = conv_b's
+    auto issue_w = [&](int j, int ws, int halves = 3) {
         if (!issuer) return;
 #pragma unroll
         for (int bt = 0; bt < NBB; ++bt) {
             const int v = vwave(bt);
             const int half = v / (NWAVES / 2), k = v % (NWAVES / 2);
-            if (half == 1 || j < na)
+            if (((halves >> half) & 1) && (half == 1 || j < na))
                 issue_w_half((half ? wb_b : wa_b) + (size_t)j * (W_FRAGS * 1024),
                              lds_base + (unsigned)(SM::W_BASE + ws * SM::W_REGION + W_FRAGS * half * 64) * 16u, k, lane16);
         }
@@ -307,36 +337,173 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         }
     };
     uint4* carry = lds + SM::CARRY;
+    float* bias_l = reinterpret_cast<float*>(lds + SM::BIAS);  // [0, 32) bias_a, [32, 64) bias_b
+    // Loaded ahead of every DMA and read by the tiles from LDS: a global load at the top of a tile would make hipcc wait for
+    // vmcnt(0), that is for the x_b stores the wave has just issued, where the tile's first item does not wait at all.
+    float bias_g = 0.f;
+    if (tid < 64) bias_g = tid < 32 ? p.bias_a[tid] : p.bias_b[tid - 32];
 
-    issue_w(0, 0);
-    issue_act(0);
+    if (!needs_warm) {
+        issue_w(0, 0);
+        issue_act(0);
+        if (tid < 64) bias_l[tid] = bias_g;
+        __syncthreads();
+        FW_STAMP(ST_SETUP);
+    } else {
+        // ---- warm-up: x_a rows R0 - 2, R0 - 1 of the tile above the run into the carry buffer.  They read input rows R0 - 3 .. R0
+        //      and conv_a's weights only.  All chunks of a batch (up to four; the shapes of RRDBNet have two or four) are in flight
+        //      at once: four rows of chunk b in slot b of the second activation stage, conv_a's fragments of chunk 0 where the
+        //      first tile's item 0 wants them anyway (weight stage 0, first half), those of the others in the second weight
+        //      stage and, with a fourth chunk, in the second half of stage 0 - conv_b's fragments of item 0 then follow the
+        //      warm-up.  Waves 4 - 7 (one per SIMD) take one row x one pixel half each and both cout tiles, chunk by chunk
+        //      and tap by tap in the item's order, so every accumulator sees the sums of conv_item_lag in the same order.
+        int R0, ox;
+        origin(t_lo, &R0, &ox);
+        const int wr0 = R0 - 3;
+        const bool w_all = R0 < p.H && ox >= 1 && ox + TILE_W < p.W;  // rows wr0 .. R0, columns ox - 1 .. ox + 32 inside (uniform)
+        const char* w_src = in + ((long)wr0 * p.W + (ox - 1)) * p.in_cstride * 2;
+        const int w_slot = wave >> 1, w_hi = wave & 1;  // this wave's DMAs: KiB 0 .. 4 (even wave) or 5 .. 8 (odd) of chunk slot wave / 2
+        unsigned w_rel[5];
+        unsigned w_ok = 0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int li0 = (5 * w_hi + i) * 64 + lane;
+            const int li = li0 < PS_WARM_PIECES ? li0 : PS_WARM_PIECES - 1;  // pad pieces: any piece of the chunk
+            const int row = li / ROW_PIECES;
+            const int px = (li - row * ROW_PIECES) >> 2;
+            w_rel[i] = piece_off(li);
+            if ((unsigned)(wr0 + row) < (unsigned)p.H && (unsigned)(ox - 1 + px) < (unsigned)p.W) w_ok |= 1u << i;
+        }
+        auto warm_rows = [&](int b, int c) {  // chunk c -> slot b
+            const char* src = w_src + (long)c * chunk_bytes;
+            const unsigned dst = lds_base + (unsigned)(PS_REGION + b * PS_WARM_SLOT + 5 * w_hi * 64) * 16u;
+            if (w_all) {
+                unsigned vo[5];
+                if (w_hi == 0) {
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) vo[i] = w_rel[i] + (unsigned)(4 - i) * 1024u;
+                    glds16_batch_a(src, vo, dst + 4 * 1024u);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) vo[i] = w_rel[i] + (unsigned)(3 - i) * 1024u;
+                    glds16_batch_a4(src, vo, dst + 3 * 1024u);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 5; ++i)
+                    if (5 * w_hi + i < PS_WARM_KIB)
+                        glds16_v(((w_ok >> i) & 1u) ? src + w_rel[i] : reinterpret_cast<const char*>(p.zeros), dst + i * 1024u);
+            }
+        };
+        // weight slot s of a batch: the two halves of weight stage 1, then the second half of stage 0
+        auto w_slot_piece = [](int s) { return SM::W_BASE + (s < 2 ? SM::W_REGION + s * W_FRAGS * 64 : W_FRAGS * 64); };
+        const bool wb_late = na >= PS_WARM_CHUNKS;  // the third weight slot is in use: conv_b's fragments of item 0 after the warm-up
+        const int wrow = (wave >> 1) & 1, wph = wave & 1;
+        f32x4 wacc[2] = {};  // (bias_a from LDS behind the first barrier: a global load here would have hipcc wait for the DMAs)
+        for (int c0 = 0; c0 < na;) {
+            const int rest = na - c0;
+            const int nb = c0 == 0 ? (rest < PS_WARM_CHUNKS ? rest : PS_WARM_CHUNKS) : (rest < 3 ? rest : 3);
+            const int wc0 = c0 == 0 ? 1 : c0;        // first chunk whose fragments go to a slot
+            const int nws = c0 == 0 ? nb - 1 : nb;   // slots in use
+            if (w_slot < nb) warm_rows(w_slot, c0 + w_slot);
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+                if (s < nws && (wave >> 2) == (s & 1))
+                    issue_w_half(wa_b + (size_t)(wc0 + s) * (W_FRAGS * 1024), lds_base + (unsigned)w_slot_piece(s) * 16u, wave & 3, lane16);
+            if (c0 == 0) {
+                issue_w(0, 0, wb_late ? 1 : 3);
+                if (tid < 64) bias_l[tid] = bias_g;
+            }
+            FW_STAMP(ST_W_SETUP);
+            FW_WAIT_VMCNT(0);
+            FW_STAMP(ST_W_DMA);
+            if (c0 == 0) issue_act(0);  // the first tile's first stage lands behind the MFMAs below
+            __syncthreads();
+            FW_STAMP(ST_W_BARRIER);
+            if (wave >= NWAVES / 2) {
+                if (c0 == 0) {
+#pragma unroll
+                    for (int w = 0; w < 2; ++w) wacc[w] = *reinterpret_cast<const f32x4*>(bias_l + 16 * w + 4 * sl);
+                }
+                for (int b = 0; b < nb; ++b) {
+                    const uint4* xw = lds + PS_REGION + b * PS_WARM_SLOT;
+                    const uint4* wl = lds + (c0 + b == 0 ? SM::W_BASE : w_slot_piece(c0 + b - wc0)) + lane;
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) {
+                        const int px = 16 * wph + q + dx;
+                        const int xo = px * 4 + (sl ^ halo_swz(px));
+#pragma unroll
+                        for (int dy = 0; dy < 3; ++dy) {
+                            const uint4 xv = xw[(wrow + dy) * ROW_PIECES + xo];
+#pragma unroll
+                            for (int w = 0; w < 2; ++w)
+                                wacc[w] = Op<T>::mfma16(wl[widx(dy * 3 + dx, w) * 64], xv, wacc[w]);
+                        }
+                    }
+                }
+            }
+            FW_STAMP(ST_W_MFMA);
+            c0 += nb;
+            if (c0 < na) {
+                __syncthreads();  // the next batch overwrites the slots
+                FW_STAMP(ST_W_BARRIER);
+            }
+        }
+        if (wave >= NWAVES / 2) {
+            // as convert() and write_xa() do for rows 16, 17 of the x_a tile, straight into the carry buffer
+            const f32x4 va = lrelu4(wacc[0]), vb = lrelu4(wacc[1]);
+            const uint2 pa = Op<T>::pack4(va[0], va[1], va[2], va[3]);
+            const uint2 pb = Op<T>::pack4(vb[0], vb[1], vb[2], vb[3]);
+            const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
+            const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
+            uint4 v = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+            const int cp = 16 * wph + q, hp = cp + 1;
+            if (!((unsigned)(R0 - 2 + wrow) < (unsigned)p.H && (unsigned)(ox + cp) < (unsigned)p.W)) v = make_uint4(0, 0, 0, 0);
+            carry[(wrow * HALO_W + hp) * 4 + (ls ^ halo_swz(hp))] = v;
+        }
+        FW_STAMP(ST_W_EPI);
+        if (wb_late) {
+            __syncthreads();  // waves 4 - 7 are done with the fragments in the second half of weight stage 0
+            FW_STAMP(ST_W_BARRIER);
+            issue_w(0, 0, 2);
+            FW_STAMP(ST_W_SETUP);
+        }
+    }
 
     int n = 0;   // item counter (weight stage = n & 1)
     int qd = 0;  // DMA'd chunks consumed
-    for (int t = t_begin; t < t_hi; ++t) {
-        const bool warm = t < t_lo;  // conv_a only, nothing stored
+    for (int t = t_lo; t < t_hi; ++t) {
         int R0, ox;
         origin(t, &R0, &ox);
         const bool col_top = R0 == 0;
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
-            const f32x4 bv = *reinterpret_cast<const f32x4*>((w < 2 ? p.bias_a : p.bias_b) + 16 * (w & 1) + 4 * sl);
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(bias_l + 16 * w + 4 * sl);
 #pragma unroll
             for (int row = 0; row < RPW; ++row)
 #pragma unroll
                 for (int ph = 0; ph < 2; ++ph) acc[row][w][ph] = bv;
         }
-        FW_STAMP(4);  // tile set-up
-        const int ipt = warm ? na : na + 1;
-        // kind: 0 = shared chunk with both convs, 1 = shared chunk, conv_a only (warm-up), 2 = conv_b's x_a chunk
+        FW_STAMP(ST_SETUP);  // tile set-up
+        const int ipt = na + 1;
+        // kind: 0 = shared chunk with both convs, 2 = conv_b's x_a chunk
         auto run_item = [&](int j, auto kind_tag, bool wait_dma) {
             constexpr int KIND = decltype(kind_tag)::value;
             constexpr bool SHARED = KIND != 2;
-            FW_STAMP(SHARED ? 1 : 2);  // the previous phase ends
+            FW_STAMP(SHARED ? ST_SHARED : ST_XA_LDS);  // the previous phase ends
             if (wait_dma) FW_WAIT_VMCNT(0);
-            FW_STAMP(5);
+#ifdef FW_PAIR_STAMP
+            if (j == 0) {
+                __syncthreads();
+                FW_STAMP(ST_FIRST);  // the wait for the tile's first stage
+            } else {
+                FW_STAMP(ST_VMCNT);
+                __syncthreads();
+                FW_STAMP(ST_BARRIER);
+            }
+#else
             __syncthreads();
-            FW_STAMP(0);
+#endif
             const bool more = n + 1 < nitems;
             const int jn = (j + 1 == ipt) ? 0 : j + 1;
             const bool fetch = SHARED && more && (j + 1 < na || t + 1 < t_hi);
@@ -353,67 +520,45 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             auto& slot_fn = dma_slot;
             if constexpr (KIND == 0)
                 conv_item_lag<T, true>(acc, a, wl, rd_off, widx, slot_fn);
-            else if constexpr (KIND == 1) {
-                // warm-up: only the carry rows (conv_a rows 14, 15 = the last wave's) are wanted; the other waves just keep
-                // the DMA stream going
-                if (wave == NWAVES - 1) {
-                    conv_item_lag<T, false>(acc, a, wl, rd_off, widx, slot_fn);
-                } else {
-                    slot_fn(FW_DMA_SLOT_W);
-                    slot_fn(FW_DMA_SLOT_A);
-                }
-            }
             else
                 conv_item<T, NW, 2>(acc, a, wl, rd_off, widx, slot_fn, [](const uint4 (&)[RPW][2]) {}, [](int) {});
             if (SHARED) ++qd;
             ++n;
         };
-        bool wait_dma = t == t_begin;
+        bool wait_dma = t == t_lo;
 #pragma clang loop unroll(disable)
         for (int j = 0; j < na; ++j) {
-            if (warm)
-                run_item(j, std::integral_constant<int, 1>{}, wait_dma);
-            else
-                run_item(j, std::integral_constant<int, 0>{}, wait_dma);
+            run_item(j, std::integral_constant<int, 0>{}, wait_dma);
             wait_dma = true;
         }
-        FW_STAMP(1);
+        FW_STAMP(ST_SHARED);
         // conv_a done for this wave; the DMAs in flight are an item old: wait ahead of the stores (vmcnt counts stores too)
         FW_WAIT_VMCNT(0);
-        FW_STAMP(5);
+        FW_STAMP(ST_VMCNT);
         // everything this tile reads, computes and stores inside the image?  (uniform)
         const bool interior = ox >= 0 && ox + TILE_W <= p.W && R0 >= 1 && R0 + TILE_H <= p.H;
         uint4 pk[RPW][2];
-        if (!warm || wave == NWAVES - 1) convert(0, pk);
-        if (!warm) {
-            if (interior)
-                store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::true_type{});
-            else
-                store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::false_type{});
-        }
-        FW_STAMP(6);      // convert + stores of x_a
-        __syncthreads();  // every wave is done with the last chunk's stage: it becomes the x_a tile
-        FW_STAMP(0);
+        convert(0, pk);
+        if (interior)
+            store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::true_type{});
+        else
+            store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::false_type{});
+        FW_STAMP(ST_XA_EPI);  // convert + stores of x_a
+        __syncthreads();      // every wave is done with the last chunk's stage: it becomes the x_a tile
+        FW_STAMP(ST_BARRIER);
         uint4* xa = lds + ((qd - 1) & 1) * PS_REGION;
-        if (!warm || wave == NWAVES - 1) {
-            if (interior)
-                write_xa(pk, xa, R0, ox, std::true_type{});
-            else
-                write_xa(pk, xa, R0, ox, std::false_type{});
+        if (interior)
+            write_xa(pk, xa, R0, ox, std::true_type{});
+        else
+            write_xa(pk, xa, R0, ox, std::false_type{});
+        // x_a rows R0 - 2, R0 - 1 -> tile rows 0, 1: from the tile above (carry), zero at the top of a column
+        if (lane < PS_CARRY / NWAVES) {
+            const int i = wave * (PS_CARRY / NWAVES) + lane;
+            xa[i] = col_top ? make_uint4(0, 0, 0, 0) : carry[i];
         }
-        if (!warm) {
-            // x_a rows R0 - 2, R0 - 1 -> tile rows 0, 1: from the tile above (carry), zero at the top of a column
-            if (lane < PS_CARRY / NWAVES) {
-                const int i = wave * (PS_CARRY / NWAVES) + lane;
-                xa[i] = col_top ? make_uint4(0, 0, 0, 0) : carry[i];
-            }
-            FW_STAMP(3);  // x_a tile (own rows + carry rows) into LDS
-            run_item(na, std::integral_constant<int, 2>{}, false);
-            FW_STAMP(2);
-        } else {
-            __syncthreads();
-            FW_STAMP(0);
-        }
+        // (run_item's first stamp closes ST_XA_LDS: x_a tile, own rows + carry rows, into LDS)
+        run_item(na, std::integral_constant<int, 2>{}, false);
+        FW_STAMP(ST_XA_ITEM);
         // rows 16, 17 of the x_a tile (wave 7's own conv_a rows: its LDS writes are ordered before these reads) -> carry, after
         // the barrier that ends every wave's reading of the old carry
         if (wave == NWAVES - 1) {
@@ -423,18 +568,16 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
                 if (i < PS_CARRY) carry[i] = xa[16 * ROW_PIECES + i];
             }
         }
-        FW_STAMP(3);  // carry rows
-        if (!warm) {
-            // conv_b done for this wave: rows R0 - 1 + (2w, 2w + 1).  In flight: the x_a stores (an item old), the next weights.
-            FW_WAIT_VMCNT(0);
-            FW_STAMP(5);
-            convert(2, pk);
-            if (interior)
-                store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::true_type{});
-            else
-                store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::false_type{});
-            FW_STAMP(6);  // convert + stores of x_b
-        }
+        FW_STAMP(ST_CARRY);  // carry rows
+        // conv_b done for this wave: rows R0 - 1 + (2w, 2w + 1).  In flight: the x_a stores (an item old), the next weights.
+        FW_WAIT_VMCNT(0);
+        FW_STAMP(ST_VMCNT);
+        convert(2, pk);
+        if (interior)
+            store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::true_type{});
+        else
+            store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::false_type{});
+        FW_STAMP(ST_XB_EPI);  // convert + stores of x_b
     }
     FW_STAMP_FLUSH(p.stamps);
 }
