@@ -673,6 +673,30 @@ int fw_deflicker_lab_u8(const uint8_t* frames_bgr, int count, int height, int wi
  * search.  Same return convention as fw_nlmeans_weight_table. */
 int fw_gamma_lab_tables(int which, int32_t* out, int capacity);
 
+/* -------------------------------------------------------------------------------------------------
+ * Scene-cut detection of the frame interpolator (csrc/scene_cuts.hip): the two tests of the reference's
+ * `FrameInterpolator.detect_scene_change` (interpolation.py:267-366) on uint8 H x W x 3 frames in DEVICE memory (any channel order:
+ * both tests are symmetric in it).  Explicit stream; the entries only enqueue work and never wait for the device.
+ * tests/scene_cut_ref.py is the contract; skimage parity unpinned.
+ *   fw_scene_ssim_u8 : ssim[p] = skimage.metrics.structural_similarity (defaults, data_range 255: 7 x 7 uniform window, sample
+ *     covariance, K1 0.01, K2 0.03, 3 pixels cropped before the mean) of gray = (c0 + c1 + c2) / 3 of the frames at
+ *     frames_a + p * frame_stride_bytes and frames_b + p * frame_stride_bytes, p < pairs, in one launch.  A contiguous clip of n frames
+ *     is the n - 1 pairs (clip, clip + H W 3) with stride H W 3; two unrelated frames are pairs = 1 (the stride is not read).  Frames
+ *     need no alignment.  The window sums and central moments are exact integers; each map value is seven correctly rounded float64
+ *     operations; the sum runs in a fixed order without floating-point atomics, so ssim[p] is the same bits in every run, alone or
+ *     in a batch, contiguous or not, within (N + 8) 2^-53 of the contract's exactly rounded sum, N = (H - 6)(W - 6).
+ *     `workspace`: fw_scene_ssim_workspace_bytes(pairs, H, W) bytes of device memory, written by the call (no need to clear it).
+ *   fw_scene_ssim_workspace_bytes : that size; 0 for arguments fw_scene_ssim_u8 refuses.
+ *   fw_hist64x3_u8 : hist[f][c][b] = the number of bytes of channel c of frame f with value >> 2 == b, for `count` contiguous
+ *     frames (np.histogram(bins=64, range=(0, 256)) on uint8).  The output is zeroed on `stream` by the call.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, pairs / count outside 1 .. 65535, height or width
+ * below 7 (SSIM: the window exceeds the image, the caller falls back to the histograms) or below 1 (histograms), more than 2^30
+ * pixels per frame, a negative stride, a zero stride with more than one pair. */
+size_t fw_scene_ssim_workspace_bytes(int pairs, int height, int width);
+int fw_scene_ssim_u8(const uint8_t* frames_a, const uint8_t* frames_b, int64_t frame_stride_bytes, int pairs, int height, int width,
+                     double* ssim /* [pairs] */, void* workspace, void* stream);
+int fw_hist64x3_u8(const uint8_t* frames, int count, int height, int width, uint32_t* hist /* [count][3][64] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,7 @@ EXPORTS = [
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
     "fw_bgr_to_lab_u8", "fw_lab_to_bgr_u8", "fw_lab_l_sums_u8", "fw_deflicker_lab_u8", "fw_gamma_lab_tables",
+    "fw_scene_ssim_workspace_bytes", "fw_scene_ssim_u8", "fw_hist64x3_u8",
 ]
 
 
@@ -323,6 +324,12 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_deflicker_lab_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.fw_gamma_lab_tables.restype = i32
     lib.fw_gamma_lab_tables.argtypes = [i32, vp, i32]
+    lib.fw_scene_ssim_workspace_bytes.restype = sz
+    lib.fw_scene_ssim_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.fw_scene_ssim_u8.restype = i32
+    lib.fw_scene_ssim_u8.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, vp, vp]
+    lib.fw_hist64x3_u8.restype = i32
+    lib.fw_hist64x3_u8.argtypes = [vp, i32, i32, i32, vp, vp]
 
 
 def load() -> C.CDLL:

@@ -282,8 +282,13 @@ def _load_rgb(frame) -> np.ndarray:
 class FrameInterpolator:
     """Drop-in for the reference class (interpolation.py:130-995): same constructor ``(model, gpu_id, config)``, same public
     methods, argument names and defaults, ``InterpolationError`` on failure.  Where the reference shells out to
-    ``rife-ncnn-vulkan`` once per pass (:628-650) the IFNet v4.6 runs in libframewright_hip.so; ``engine`` / ``dtype`` are
-    keyword-only additions.
+    ``rife-ncnn-vulkan`` once per pass (:628-650) the IFNet v4.6 runs in libframewright_hip.so; ``engine`` / ``dtype`` /
+    ``device_scene_detection`` are keyword-only additions.
+
+    ``device_scene_detection=True`` takes the scene-cut decisions on the GPU (scene_cuts.DeviceSceneCutDetector: the same SSIM and
+    histogram tests as ``policy.scene_change``, on the uploaded frames), and ``interpolate`` then makes one pass over the files:
+    the cut of a pair is decided from the two tensors the stream already holds, every PNG is decoded and uploaded once.  Off (the
+    default) every path is the host one.
 
     Frame bookkeeping.  ``interpolate`` multiplies the frame count by 2^n (n from the fps ratio, :580-587), output names
     ``frame_%08d.png`` from 1 like the binary's ``-f`` pattern (:634).  The clip is streamed: a source pair (a, b) yields
@@ -305,7 +310,7 @@ class FrameInterpolator:
     SUPPORTED_TARGET_FPS = [24, 30, 48, 50, 60, 120]
 
     def __init__(self, model: str = "rife-v4.6", gpu_id: int = 0, config: Optional[InterpolationConfig] = None, *,
-                 engine: Optional[IFNetEngine] = None, dtype: str = "f16"):
+                 engine: Optional[IFNetEngine] = None, dtype: str = "f16", device_scene_detection: bool = False):
         if config is not None and not isinstance(config, InterpolationConfig):
             raise TypeError("config must be an InterpolationConfig (engine= and dtype= are keyword-only)")
         self.config = config or InterpolationConfig(rife_model=model, gpu_id=gpu_id)
@@ -313,6 +318,8 @@ class FrameInterpolator:
         self.gpu_id = self.config.gpu_id
         self._scene_boundaries: List[int] = []
         self._engine, self._dtype = engine, dtype
+        self._device_scene_detection = bool(device_scene_detection)
+        self._cut_detector = None
         self._mu = threading.Lock()
 
     # -- engine ------------------------------------------------------------------------------------------------------------
@@ -335,8 +342,31 @@ class FrameInterpolator:
             return self._engine
 
     # -- scene cuts (interpolation.py:267-401) -----------------------------------------------------------------------------
+    def _get_cut_detector(self):
+        with self._mu:
+            if self._cut_detector is None:
+                from .scene_cuts import DeviceSceneCutDetector
+                self._cut_detector = DeviceSceneCutDetector(self.gpu_id)
+            return self._cut_detector
+
+    def _upload_rgb(self, frame):
+        """A path or an array -> uint8 H x W x 3 tensor on the interpolator's GPU (what `_load_rgb` gives the host test)."""
+        import torch
+        img = np.asarray(_load_rgb(frame))
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise InterpolationError("device scene detection expects 8-bit H x W x 3 frames")
+        return torch.from_numpy(np.ascontiguousarray(img)).to(torch.device("cuda", self.gpu_id))
+
+    def _cut_on_device(self, a, b, scene_threshold: float) -> bool:
+        try:
+            return self._get_cut_detector().scene_change_device(a, b, scene_threshold)
+        except FramewrightHipError as e:
+            raise InterpolationError(f"scene detection failed: {e}") from e
+
     def detect_scene_change(self, frame1: Union[Path, np.ndarray], frame2: Union[Path, np.ndarray]) -> bool:
         """SSIM of the mean-gray images below ``1 - scene_threshold``; histogram intersection when the SSIM cannot be formed."""
+        if self._device_scene_detection:
+            return self._cut_on_device(self._upload_rgb(frame1), self._upload_rgb(frame2), self.config.scene_threshold)
         return policy.scene_change(_load_rgb(frame1), _load_rgb(frame2), self.config.scene_threshold)
 
     def _detect_scene_by_histogram(self, img1: np.ndarray, img2: np.ndarray, scene_threshold: Optional[float] = None) -> bool:
@@ -347,10 +377,12 @@ class FrameInterpolator:
         if len(frames) < 2:
             return []
         bounds: List[int] = []
-        prev = _load_rgb(frames[0])
+        # on the device: every file decoded and uploaded once, only the previous frame stays resident
+        load, is_cut = (self._upload_rgb, self._cut_on_device) if self._device_scene_detection else (_load_rgb, policy.scene_change)
+        prev = load(frames[0])
         for i in range(len(frames) - 1):
-            cur = _load_rgb(frames[i + 1])
-            if policy.scene_change(prev, cur, self.config.scene_threshold):
+            cur = load(frames[i + 1])
+            if is_cut(prev, cur, self.config.scene_threshold):
                 bounds.append(i + 1)
                 logger.info(f"Scene change detected at frame {i + 1}")
             prev = cur
@@ -448,9 +480,10 @@ class FrameInterpolator:
         mid = self._get_engine().interpolate_device(a, b, 0.5)
         return self._between(a, mid, n - 1, False) + [mid] + self._between(mid, b, n - 1, False)
 
-    def _stream(self, files: Sequence[Path], n: int, cuts, refine_passes: int):
+    def _stream(self, files: Sequence[Path], n: int, cuts, refine_passes: int, detect=None):
         """Generator of (is_source, frame tensor) in display order for the 2^n-fold clip (+ refinement passes, see the class
-        docstring); at most a few frames alive."""
+        docstring); at most a few frames alive.  Pair (i - 1, i) is a cut when ``i in cuts``, or, with ``detect``, when
+        ``detect(i, prev, cur)`` says so of the two tensors at hand (asked once per pair, in order)."""
         import torch
         dev = torch.device("cuda", self.gpu_id)
 
@@ -466,9 +499,10 @@ class FrameInterpolator:
             prev = load(files[0])
             for i in range(1, len(files)):
                 cur = load(files[i])
+                cut = detect(i, prev, cur) if detect is not None else (i in cuts)
                 yield True, prev
-                for t in self._between(prev, cur, n, i in cuts):
-                    yield (i in cuts), t            # copies across a cut are final: no refinement pass touches them
+                for t in self._between(prev, cur, n, cut):
+                    yield cut, t                    # copies across a cut are final: no refinement pass touches them
                 prev = cur
             yield True, prev
 
@@ -510,7 +544,21 @@ class FrameInterpolator:
         passes = {SmoothnessLevel.LOW: 1, SmoothnessLevel.MEDIUM: 2}.get(cfg.smoothness, 3)
         files = sorted(input_dir.glob("*.png"))
         cuts: set = set()
-        if cfg.enable_scene_detection:
+        detect = None
+        if cfg.enable_scene_detection and self._device_scene_detection and len(files) >= 2:
+            # one pass: the stream decides each pair's cut from the two tensors it holds; the boundaries are complete when it ends
+            if progress_callback:
+                progress_callback(0.02)
+            bounds: List[int] = []
+            self._scene_boundaries = bounds
+
+            def detect(i, prev, cur):
+                if not self._cut_on_device(prev, cur, cfg.scene_threshold):
+                    return False
+                bounds.append(i)
+                logger.info(f"Scene change detected at frame {i}")
+                return True
+        elif cfg.enable_scene_detection:
             if progress_callback:
                 progress_callback(0.02)
             saved = self.config
@@ -527,7 +575,7 @@ class FrameInterpolator:
         try:
             with torch.cuda.device(self.gpu_id):
                 total = (len(files) - 1) * (1 << n) + 1
-                for k, (_, t) in enumerate(self._stream(files, n, cuts, passes - 1)):
+                for k, (_, t) in enumerate(self._stream(files, n, cuts, passes - 1, detect)):
                     if cfg.enable_motion_blur_reduction:
                         t = self.apply_motion_blur_reduction_device(t, 1.0)
                     _imwrite(output_dir / f"frame_{k + 1:08d}.png", t.cpu().numpy())
@@ -537,6 +585,8 @@ class FrameInterpolator:
             raise InterpolationError(f"RIFE interpolation failed: {e}") from e
         if not list(output_dir.glob("*.png")):
             raise InterpolationError("No output frames generated")
+        if detect is not None:
+            logger.info(f"Detected {len(self._scene_boundaries)} scene changes")
         if progress_callback:
             progress_callback(1.0)
         return output_dir
