@@ -697,6 +697,33 @@ int fw_scene_ssim_u8(const uint8_t* frames_a, const uint8_t* frames_b, int64_t f
                      double* ssim /* [pairs] */, void* workspace, void* stream);
 int fw_hist64x3_u8(const uint8_t* frames, int count, int height, int width, uint32_t* hist /* [count][3][64] */, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Frame deduplication (csrc/dedup_hash.hip): the two frame hashes of the reference's `FrameDeduplicator`
+ * (processors/deduplication.py:106-164) on uint8 BGR H x W x 3 frames in DEVICE memory.  Both are Pillow thumbnails - `convert('L')`
+ * is L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, `resize(..., LANCZOS)` a horizontal then a vertical pass of integer taps with
+ * 22 fractional bits, each pass rounding to uint8, a pass left out when its size does not change - so the results are Pillow's bytes.
+ * tests/dedup_ref.py is the contract, held byte for byte against Pillow itself on the CPU; the dHash bit order is restated from
+ * imagehash's definition (imagehash parity unpinned).  Explicit stream; the device entries only enqueue work and never wait for the
+ * device, except that the first call for a pair of sizes on a device uploads its tap table (an allocation and a blocking copy).
+ *   fw_pil_lanczos_taps : HOST function (no GPU needed).  The table of one pass in_size -> out_size: for output index i the window
+ *     starts at xmin[i] and has count[i] taps, taps[i * ksize + k], zero behind the window.  Returns ksize (all three pointers NULL:
+ *     ksize only); 0 for sizes outside 1 .. 65536, a NULL among the pointers, or capacity < out_size * ksize.
+ *   fw_pil_thumb_u8 : thumbs[f] (out_h x out_w bytes) of the n frames at frames_bgr + f * frame_stride_bytes, in one call.
+ *     gray_first = 1: convert('L').resize((out_w, out_h), LANCZOS), the dHash thumbnail; gray_first = 0: resize, then convert('L'),
+ *     the pixel-hash thumbnail.  Frames need no alignment; a contiguous clip has stride H W 3, one frame is n = 1 (the stride is not
+ *     read).  No atomics and no floating point on the device: a thumbnail is the same bytes in every run, alone or in a batch.
+ *     `workspace`: fw_pil_thumb_workspace_bytes(...) bytes of device memory, written by the call (no need to clear it).
+ *   fw_pil_thumb_workspace_bytes : that size; 0 for arguments fw_pil_thumb_u8 refuses.
+ *   fw_dhash_pack_u8 : bits[f] = the hash_size^2 comparisons px[r][c + 1] > px[r][c] of thumbnail f ((hash_size + 1) wide, hash_size
+ *     high), row-major, as one big-endian integer in ceil(hash_size^2 / 8) bytes (the first bit most significant, zero bits in front).
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, n outside 1 .. 65535, non-positive sizes, height or
+ * width above 16384, out_w or out_h above 65, a negative stride, a zero stride with more than one frame, hash_size outside 2 .. 64. */
+int fw_pil_lanczos_taps(int in_size, int out_size, int32_t* xmin, int32_t* count, int32_t* taps, int capacity);
+size_t fw_pil_thumb_workspace_bytes(int n, int height, int width, int out_w, int out_h, int gray_first);
+int fw_pil_thumb_u8(const uint8_t* frames_bgr, int64_t frame_stride_bytes, int n, int height, int width, int out_w, int out_h,
+                    int gray_first, uint8_t* thumbs /* [n][out_h][out_w] */, void* workspace, void* stream);
+int fw_dhash_pack_u8(const uint8_t* thumbs, int n, int hash_size, uint8_t* bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

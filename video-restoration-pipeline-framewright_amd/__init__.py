@@ -6,3 +6,6 @@ importing the operator modules works anywhere, but creating an engine without th
 raises ``FramewrightHipError``.
 """
 __version__ = "0.1.0"
+
+from .dedup import (DeduplicationConfig, DeduplicationResult, DeviceFrameDeduplicator, analyze_hashes,  # noqa: E402,F401
+                    deduplicate_and_enhance, detect_duplicate_frames)

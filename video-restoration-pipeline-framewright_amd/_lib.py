@@ -49,6 +49,7 @@ EXPORTS = [
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
     "fw_bgr_to_lab_u8", "fw_lab_to_bgr_u8", "fw_lab_l_sums_u8", "fw_deflicker_lab_u8", "fw_gamma_lab_tables",
     "fw_scene_ssim_workspace_bytes", "fw_scene_ssim_u8", "fw_hist64x3_u8",
+    "fw_pil_lanczos_taps", "fw_pil_thumb_workspace_bytes", "fw_pil_thumb_u8", "fw_dhash_pack_u8",
 ]
 
 
@@ -330,6 +331,14 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_scene_ssim_u8.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, vp, vp]
     lib.fw_hist64x3_u8.restype = i32
     lib.fw_hist64x3_u8.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.fw_pil_lanczos_taps.restype = i32
+    lib.fw_pil_lanczos_taps.argtypes = [i32, i32, vp, vp, vp, i32]
+    lib.fw_pil_thumb_workspace_bytes.restype = sz
+    lib.fw_pil_thumb_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.fw_pil_thumb_u8.restype = i32
+    lib.fw_pil_thumb_u8.argtypes = [vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.fw_dhash_pack_u8.restype = i32
+    lib.fw_dhash_pack_u8.argtypes = [vp, i32, i32, vp, vp]
 
 
 def load() -> C.CDLL:

@@ -310,6 +310,11 @@ void launch_ifnet_accumulate(const float* tmp, int hs, int ws, int H, int W, flo
 void launch_ifnet_blend(const float* i0, const float* i1, const float* flow, const float* mask, int Hp, int Wp, int H, int W,
                         uint8_t* out_bgr, float* out_rgb, hipStream_t st);
 
+// ---- Pillow's 8-bit Lanczos coefficients (dedup_hash.hip; host only) -----------------------------------------------------------
+// taps per table row for in_size -> out_size, and the table itself: xmin[out], count[out], taps[out][ksize] (zero behind a window)
+int pil_lanczos_ksize(int in_size, int out_size);
+void pil_lanczos_fill(int in_size, int out_size, int32_t* xmin, int32_t* count, int32_t* taps);
+
 // thread-local message returned by fw_last_error()
 std::string& last_error_ref();
 

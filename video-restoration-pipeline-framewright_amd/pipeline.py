@@ -20,11 +20,17 @@ class DeviceRestorationPipeline:
 
     ``interp_passes`` x2 passes of frame interpolation (1 -> 2n-1 frames, 2 -> 4n-3, ...), as
     `FrameInterpolator.interpolate` runs them for a fps ratio (`policy.interpolation_exponent`).
+
+    ``deduplicator`` (a `dedup.DeviceFrameDeduplicator`; opt-in) analyses the clip that enters the upscale stage, as the reference
+    deduplicates what its enhancer reads: only unique frames are upscaled, the sequence is rebuilt by repetition before the
+    interpolation, and the analysis is kept as ``last_dedup_result``.  `run_device` / `run` only.
     """
 
-    def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1):
+    def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
+        self.deduplicator = deduplicator
+        self.last_dedup_result = None
 
     @classmethod
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
@@ -50,7 +56,10 @@ class DeviceRestorationPipeline:
             cur = [up(f) for f in frames]
             if self.denoiser is not None:
                 cur = self.denoiser.denoise_clip_device(cur)
-            if self.upscaler is not None:
+            if self.upscaler is not None and self.deduplicator is not None and cur:
+                self.last_dedup_result = res = self.deduplicator.analyze_clip_device(cur)
+                cur = self.deduplicator.reconstruct_device([self.upscaler.upscale_device(cur[i]) for i in res.unique_indices], res)
+            elif self.upscaler is not None:
                 cur = [self.upscaler.upscale_device(f) for f in cur]
             if self.interpolator is not None:
                 for _ in range(self.interp_passes):
@@ -121,7 +130,9 @@ class DeviceRestorationPipeline:
     def stream_device(self, frames: Iterable, block: int = 8):
         """Generator form of `run_device` for clips that do not fit (or have not arrived) in memory: ``frames`` is any iterator of
         uint8 BGR frames (numpy - e.g. `codec.RawVideoReader` - or CUDA tensors); yields the output frames, uint8 CUDA tensors, in
-        order, as soon as their inputs allow.  Identical frames to `run_device` on the whole clip."""
+        order, as soon as their inputs allow.  Identical frames to `run_device` on the whole clip - without a ``deduplicator``:
+        deduplication needs the clip's hashes in front of the upscale stage and is not part of the streaming form, which upscales
+        every frame."""
         import torch
         dev = self._device()
         if block < 1:
