@@ -724,6 +724,33 @@ int fw_pil_thumb_u8(const uint8_t* frames_bgr, int64_t frame_stride_bytes, int n
                     int gray_first, uint8_t* thumbs /* [n][out_h][out_w] */, void* workspace, void* stream);
 int fw_dhash_pack_u8(const uint8_t* thumbs, int n, int hash_size, uint8_t* bits, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Colour grade (csrc/color_lut.hip): the reference's `LUTManager.apply_to_image_fast` (integration/lut.py; core/restorer.py step 7c,
+ * the seasonal grade) on three-channel frames of H x W pixels without row padding in DEVICE memory.  Per sample v (maxv = 255 or
+ * 65535), every operation rounded on its own: in float32 x = v / maxv (IEEE division), s = x * (size - 1), lo = floor(s),
+ * hi = min(lo + 1, size - 1); then in float64, as NumPy promotes the reference's own lines, f = s - lo; eight corners of the float32
+ * table; four lerps along r, two along g, one along b, each a * (1 - f) + b * f as two products and a sum; clip to [0, 1], * maxv,
+ * truncate.  The results are the reference's bytes;
+ * tests/color_lut_ref.py is the contract, held byte for byte against the reference's own function on the CPU.  A LUT's domain is
+ * not applied (`apply_to_image_fast` ignores it).  Explicit stream; the calls only enqueue one launch and never wait or allocate.
+ *   fw_lut3d_apply_u8 : dst[f] = grade(src[f]) for the n frames at src + f * src_stride_bytes -> dst + f * dst_stride_bytes.
+ *     lut_f32: size^3 x 3 floats in device memory, order [r][g][b][rgb]; tables up to 17^3 are held in LDS, larger ones read through
+ *     L2.  bgr != 0: byte 0 of a pixel is blue (OpenCV order), else red.  Frames need no alignment; a contiguous clip has stride
+ *     H W 3, one frame is n = 1 (the strides are not read).  dst == src with equal strides grades in place; any other overlap of
+ *     source and destination is undefined.  Nothing outside the n frames is read or written.  No atomics: a frame's result is the
+ *     same bytes in every run, alone or in a batch, wherever it lies.
+ *   fw_lut3d_apply_u16 : the same for 16-bit samples (strides still in bytes; pointers and strides even).
+ *   fw_table3_apply_u8 : dst sample = tables[c][src sample] for stored channel c = 0, 1, 2 - a 1D LUT on 8-bit frames, its three
+ *     256-byte tables (device memory) built by the host (color_grade.py).
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, n outside 1 .. 65535, height or width outside
+ * 1 .. 16384, size outside 2 .. 65, a negative stride, a zero stride with more than one frame, odd 16-bit addresses or strides. */
+int fw_lut3d_apply_u8(const uint8_t* src, int64_t src_stride_bytes, int n, int height, int width, const float* lut_f32, int size, int bgr,
+                      uint8_t* dst, int64_t dst_stride_bytes, void* stream);
+int fw_lut3d_apply_u16(const uint16_t* src, int64_t src_stride_bytes, int n, int height, int width, const float* lut_f32, int size, int bgr,
+                       uint16_t* dst, int64_t dst_stride_bytes, void* stream);
+int fw_table3_apply_u8(const uint8_t* src, int64_t src_stride_bytes, int n, int height, int width, const uint8_t* tables /* [3][256] */,
+                       uint8_t* dst, int64_t dst_stride_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

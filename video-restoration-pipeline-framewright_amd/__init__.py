@@ -9,3 +9,5 @@ __version__ = "0.1.0"
 
 from .dedup import (DeduplicationConfig, DeduplicationResult, DeviceFrameDeduplicator, analyze_hashes,  # noqa: E402,F401
                     deduplicate_and_enhance, detect_duplicate_frames)
+from .color_grade import (LUT, DeviceColorGrader, LUTType, combine_luts, create_contrast_lut,  # noqa: E402,F401
+                          create_film_emulation_lut, create_identity_lut, create_seasonal_lut, read_cube, write_cube)

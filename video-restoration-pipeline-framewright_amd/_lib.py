@@ -50,6 +50,7 @@ EXPORTS = [
     "fw_bgr_to_lab_u8", "fw_lab_to_bgr_u8", "fw_lab_l_sums_u8", "fw_deflicker_lab_u8", "fw_gamma_lab_tables",
     "fw_scene_ssim_workspace_bytes", "fw_scene_ssim_u8", "fw_hist64x3_u8",
     "fw_pil_lanczos_taps", "fw_pil_thumb_workspace_bytes", "fw_pil_thumb_u8", "fw_dhash_pack_u8",
+    "fw_lut3d_apply_u8", "fw_lut3d_apply_u16", "fw_table3_apply_u8",
 ]
 
 
@@ -339,6 +340,12 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_pil_thumb_u8.argtypes = [vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.fw_dhash_pack_u8.restype = i32
     lib.fw_dhash_pack_u8.argtypes = [vp, i32, i32, vp, vp]
+    lib.fw_lut3d_apply_u8.restype = i32
+    lib.fw_lut3d_apply_u8.argtypes = [vp, C.c_int64, i32, i32, i32, vp, i32, i32, vp, C.c_int64, vp]
+    lib.fw_lut3d_apply_u16.restype = i32
+    lib.fw_lut3d_apply_u16.argtypes = [vp, C.c_int64, i32, i32, i32, vp, i32, i32, vp, C.c_int64, vp]
+    lib.fw_table3_apply_u8.restype = i32
+    lib.fw_table3_apply_u8.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp, C.c_int64, vp]
 
 
 def load() -> C.CDLL:

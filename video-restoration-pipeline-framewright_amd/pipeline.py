@@ -24,13 +24,17 @@ class DeviceRestorationPipeline:
     ``deduplicator`` (a `dedup.DeviceFrameDeduplicator`; opt-in) analyses the clip that enters the upscale stage, as the reference
     deduplicates what its enhancer reads: only unique frames are upscaled, the sequence is rebuilt by repetition before the
     interpolation, and the analysis is kept as ``last_dedup_result``.  `run_device` / `run` only.
+
+    ``color_grader`` (a `color_grade.DeviceColorGrader`; opt-in) grades every output frame behind the interpolation, where the
+    reference has its seasonal grade (step 7c), into new tensors; it is elementwise, so the streaming forms have it too.
     """
 
-    def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None):
+    def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
         self.last_dedup_result = None
+        self.color_grader = color_grader
 
     @classmethod
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
@@ -46,6 +50,8 @@ class DeviceRestorationPipeline:
                 dev = torch.device("cuda", e.device_id)
         if dev is None and self.denoiser is not None:
             dev = torch.device("cuda", self.denoiser.config.gpu_id)
+        if dev is None and self.color_grader is not None:
+            dev = torch.device("cuda", self.color_grader.device_id)
         if dev is None:
             raise ValueError("DeviceRestorationPipeline: no stage configured")
 
@@ -69,6 +75,8 @@ class DeviceRestorationPipeline:
                         if i + 1 < len(cur):
                             nxt.append(self.interpolator.interpolate_device(f, cur[i + 1]))
                     cur = nxt
+            if self.color_grader is not None:
+                cur = self.color_grader.apply_device(cur)      # new tensors: a repeated frame may be one tensor several times
         return cur
 
     def run(self, frames: Sequence) -> List[np.ndarray]:
@@ -85,6 +93,8 @@ class DeviceRestorationPipeline:
                 return torch.device("cuda", e.device_id)
         if self.denoiser is not None:
             return torch.device("cuda", self.denoiser.config.gpu_id)
+        if self.color_grader is not None:
+            return torch.device("cuda", self.color_grader.device_id)
         raise ValueError("DeviceRestorationPipeline: no stage configured")
 
     def _gen_denoise(self, frames: Iterator, block: int):
@@ -163,6 +173,8 @@ class DeviceRestorationPipeline:
             if self.interpolator is not None:
                 for _ in range(self.interp_passes):
                     g = self._gen_interp(g)
+            if self.color_grader is not None:
+                g = (self.color_grader.apply_device([f])[0] for f in g)
             yield from g
 
     def run_stream(self, frames: Iterable, writer, block: int = 8, slots: int = 3) -> int:
