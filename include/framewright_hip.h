@@ -751,6 +751,42 @@ int fw_lut3d_apply_u16(const uint16_t* src, int64_t src_stride_bytes, int n, int
 int fw_table3_apply_u8(const uint8_t* src, int64_t src_stride_bytes, int n, int height, int width, const uint8_t* tables /* [3][256] */,
                        uint8_t* dst, int64_t dst_stride_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Deinterlacing and interlace analysis (csrc/deinterlace.hip): the frame path of the reference's `Deinterlacer`
+ * (processors/format/interlace.py) on uint8 frames in DEVICE memory, gray (H x W) or BGR (H x W x 3), without row padding.  Every
+ * output is an integer function of the input bytes; tests/deinterlace_ref.py is the contract, held byte for byte against the
+ * reference's own functions on the CPU.  Explicit stream; the calls enqueue and never wait or allocate.
+ *   fw_deinterlace_u8 : one frame of `rows` rows of `row_bytes` = W * C bytes.  parity 1 (top field first) rebuilds odd rows, 0 even
+ *     rows; every other row is copied.
+ *       FW_DEINTERLACE_YADIF  1 <= y <= rows-2: dst[y] = (cur[y-1] + cur[y+1]) >> 1; prev and next are not read (may be NULL)
+ *       FW_DEINTERLACE_BWDIF  2 <= y <= rows-3: num = 3 * (9 * (cur[y-1] + cur[y+1]) - (cur[y-2] + cur[y+2])) + 4 * (prev[y] + next[y]),
+ *                             dst[y] = clamp(num, 0, 255 * 64) >> 6; at the ends of a clip prev or next is cur itself
+ *       FW_DEINTERLACE_BOB    dst = cv2.resize(cur[parity::2], (W, rows)) with the 8-bit INTER_LINEAR arithmetic of
+ *                             fw_resize_linear_u8, the field read in place; prev and next are not read
+ *     Frames may start at any byte; 16-byte accesses are used when every pointer and row_bytes are multiples of 16, 4-byte ones
+ *     when row_bytes is a multiple of 4 and all pointers agree modulo 4.  Nothing outside the frames is read or written.
+ *   fw_deinterlace_batch_u8 : n frames; `frames` is a HOST table of n x 4 device pointers {cur, prev, next, dst}; one launch per
+ *     32 frames.
+ *   fw_interlace_stats_u8 : `frames` is a HOST table of n device pointers; stats (device, int64 [n][4]) = {n_comb, s_field, s_odd,
+ *     s_even} of each frame's gray image g (channels 3: (1868 B + 9617 G + 4899 R + 8192) >> 14; channels 1: the bytes), R = height / 2:
+ *     n_comb = #{r < R : sum_x |g[2r+1] - g[2r]| > 30 * width}, s_field = sum_{r < R} |g[2r+1] - g[2r]|,
+ *     s_odd = sum_{r < R-1} |g[2r+3] - g[2r+1]|, s_even = sum_{r < R-1} |g[2r+2] - g[2r]|.  Exact integers, equal in every run.
+ *   fw_frame_absdiff_sum_u8 : sums (device, int64 [n]) = sum |g(a[i]) - g(b[i])| over the frame; a and b are HOST tables.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers or tables, n < 1, rows / height / width outside
+ * 1 .. 16384, row_bytes outside 1 .. 65536, an unknown mode, a parity other than 0 or 1, BOB with rows < 2, channels other than 1
+ * or 3, a dst that overlaps cur (or, for BWDIF, prev or next) of any frame of the call: rebuilt rows are read as neighbours. */
+#define FW_DEINTERLACE_YADIF 0
+#define FW_DEINTERLACE_BWDIF 1
+#define FW_DEINTERLACE_BOB 2
+int fw_deinterlace_u8(const uint8_t* cur, const uint8_t* prev, const uint8_t* next, uint8_t* dst, int rows, int64_t row_bytes, int mode,
+                      int parity, void* stream);
+int fw_deinterlace_batch_u8(const void* const* frames /* host [n][4] */, int n, int rows, int64_t row_bytes, int mode, int parity,
+                            void* stream);
+int fw_interlace_stats_u8(const void* const* frames /* host [n] */, int n, int height, int width, int channels,
+                          int64_t* stats /* device [n][4] */, void* stream);
+int fw_frame_absdiff_sum_u8(const void* const* a /* host [n] */, const void* const* b /* host [n] */, int n, int height, int width,
+                            int channels, int64_t* sums /* device [n] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ EXPORTS = [
     "fw_scene_ssim_workspace_bytes", "fw_scene_ssim_u8", "fw_hist64x3_u8",
     "fw_pil_lanczos_taps", "fw_pil_thumb_workspace_bytes", "fw_pil_thumb_u8", "fw_dhash_pack_u8",
     "fw_lut3d_apply_u8", "fw_lut3d_apply_u16", "fw_table3_apply_u8",
+    "fw_deinterlace_u8", "fw_deinterlace_batch_u8", "fw_interlace_stats_u8", "fw_frame_absdiff_sum_u8",
 ]
 
 
@@ -346,6 +347,14 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_lut3d_apply_u16.argtypes = [vp, C.c_int64, i32, i32, i32, vp, i32, i32, vp, C.c_int64, vp]
     lib.fw_table3_apply_u8.restype = i32
     lib.fw_table3_apply_u8.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp, C.c_int64, vp]
+    lib.fw_deinterlace_u8.restype = i32
+    lib.fw_deinterlace_u8.argtypes = [vp, vp, vp, vp, i32, C.c_int64, i32, i32, vp]
+    lib.fw_deinterlace_batch_u8.restype = i32
+    lib.fw_deinterlace_batch_u8.argtypes = [vp, i32, i32, C.c_int64, i32, i32, vp]
+    lib.fw_interlace_stats_u8.restype = i32
+    lib.fw_interlace_stats_u8.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.fw_frame_absdiff_sum_u8.restype = i32
+    lib.fw_frame_absdiff_sum_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
 
 
 def load() -> C.CDLL:

@@ -27,14 +27,21 @@ class DeviceRestorationPipeline:
 
     ``color_grader`` (a `color_grade.DeviceColorGrader`; opt-in) grades every output frame behind the interpolation, where the
     reference has its seasonal grade (step 7c), into new tensors; it is elementwise, so the streaming forms have it too.
+
+    ``deinterlacer`` (a `deinterlace.DeviceDeinterlacer`; opt-in) deinterlaces the input frames in front of every other stage with
+    its configured method and field order (BOB doubles the frame count downstream).  The streaming forms keep one frame of
+    lookahead for BWDIF and refuse `FieldOrder.AUTO` (a stream has no "first 20 frames"); with an explicit order they equal
+    `run_device`.
     """
 
-    def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None):
+    def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
+                 deinterlacer=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
         self.last_dedup_result = None
         self.color_grader = color_grader
+        self.deinterlacer = deinterlacer
 
     @classmethod
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
@@ -52,6 +59,8 @@ class DeviceRestorationPipeline:
             dev = torch.device("cuda", self.denoiser.config.gpu_id)
         if dev is None and self.color_grader is not None:
             dev = torch.device("cuda", self.color_grader.device_id)
+        if dev is None and self.deinterlacer is not None:
+            dev = torch.device("cuda", self.deinterlacer.device_id)
         if dev is None:
             raise ValueError("DeviceRestorationPipeline: no stage configured")
 
@@ -60,6 +69,8 @@ class DeviceRestorationPipeline:
 
         with torch.cuda.device(dev):
             cur = [up(f) for f in frames]
+            if self.deinterlacer is not None:
+                cur = list(self.deinterlacer.deinterlace(cur))
             if self.denoiser is not None:
                 cur = self.denoiser.denoise_clip_device(cur)
             if self.upscaler is not None and self.deduplicator is not None and cur:
@@ -95,6 +106,8 @@ class DeviceRestorationPipeline:
             return torch.device("cuda", self.denoiser.config.gpu_id)
         if self.color_grader is not None:
             return torch.device("cuda", self.color_grader.device_id)
+        if self.deinterlacer is not None:
+            return torch.device("cuda", self.deinterlacer.device_id)
         raise ValueError("DeviceRestorationPipeline: no stage configured")
 
     def _gen_denoise(self, frames: Iterator, block: int):
@@ -147,6 +160,8 @@ class DeviceRestorationPipeline:
         dev = self._device()
         if block < 1:
             raise ValueError("block must be >= 1")
+        if self.deinterlacer is not None and self.deinterlacer.config.field_order.value == "auto":
+            raise ValueError("FieldOrder.AUTO needs the clip's first 20 frames: give the streaming forms an explicit field order")
         upload = torch.cuda.Stream(device=dev)
 
         def gen_up():
@@ -166,6 +181,8 @@ class DeviceRestorationPipeline:
 
         with torch.cuda.device(dev):
             g = gen_up()
+            if self.deinterlacer is not None:
+                g = self.deinterlacer.stream(g, block=block)
             if self.denoiser is not None:
                 g = self._gen_denoise(g, block)
             if self.upscaler is not None:
