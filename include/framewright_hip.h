@@ -787,6 +787,65 @@ int fw_interlace_stats_u8(const void* const* frames /* host [n] */, int n, int h
 int fw_frame_absdiff_sum_u8(const void* const* a /* host [n] */, const void* const* b /* host [n] */, int n, int height, int width,
                             int channels, int64_t* sums /* device [n] */, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * VHS artifact repair and analysis (csrc/vhs.hip): the frame path of the reference's `VHSProcessor` (processors/format/vhs.py) on
+ * uint8 frames in DEVICE memory, gray (H x W) or BGR (H x W x 3), without row padding.  tests/vhs_ref.py is the contract, held byte
+ * for byte against the reference's own functions on the CPU.  The device forms exact integer statistics and rewrites frames; the
+ * decisions between the two are the caller's (vhs.py: the reference's NumPy steps on a few values per frame).  Explicit stream; the
+ * calls enqueue and never wait or allocate.  Gray g is the bytes (channels 1) or (1868 B + 9617 G + 4899 R + 8192) >> 14.  A blend
+ * fa * a + fb * b is float32: two rounded products, a rounded sum, never an FMA; the cast to uint8 truncates.  `frames`, `src`, `dst`,
+ * `sources`, `results` are HOST tables of device pointers; tables of rows, boxes and samples are in DEVICE memory, and the kernels skip
+ * every entry of them that does not lie inside a frame, so nothing outside a frame is read or written whatever they hold.
+ *   fw_vhs_gray_stats_u8 : any of (NULL = not wanted) row_sums int64 [n][H] = sum_x |g[y][x+1] - g[y][x]|; bottom uint8 [n][30][W] = the
+ *     last 30 rows of g; runs int32 [run_capacity][4] = {frame, x, y, length} of every maximal run of g > 250 or of g < 5 in a row with
+ *     length >= min_length, in no particular order, and *run_count = how many there are (also when that is more than the capacity:
+ *     the caller then calls again with a larger list).  One launch per 32 frames.
+ *   fw_vhs_blend_rows_u8 : for each of m table rows {frame, y, y1, y2} / {fa, fb}: dst[frame][y] = fa * ((src[y1] + src[y2]) / 2) + fb *
+ *     src[y] byte by byte.  Other rows of dst are not written (the caller copies the frame first).  n <= 32.
+ *   fw_vhs_rainbow_u8 : BGR; r = 0.5 c + 0.125 (the four diagonal neighbours) inside, r = c on the border rows and columns, formed as
+ *     an integer sum of eighths (exact), then dst = clamp(fa * r + fb * c, 0, 255) for EVERY byte, the borders included.  n <= 32.
+ *   fw_vhs_box_gray_sums_u8 : tasks int32 [m][5] = {frame, x, y, w, h}; sums[e] = sum of g over the box, -1 for an entry not inside a
+ *     frame.  n <= 64.
+ *   fw_vhs_dropout_repair_u8 : boxes int32 [m][8] = {mode, result frame, source frame, x, y, w, h, 0}, rewritten in place in
+ *     results[.]: mode 0 res = float32(s) * src + float32(1 - s) * res over the box; mode 1 (needs x > 0 and x + w < W), per column xi:
+ *     t = (xi - x + 1) / (w + 1), res = s * ((1 - t) * res[x - 1] + t * res[x + w]) + double(float32(1 - s) * float32(res)) in float64.
+ *     The boxes of one call that share a result frame must be disjoint, the two flank columns of a mode 1 box included (the caller
+ *     splits a frame's list into such groups and calls once per group, in order).  n_sources <= 64, n_results <= 32.
+ *   fw_vhs_edge_counts_u8 : BGR; counts int32 [n][H] = #{x < W - 1 : |Y[x+1] - Y[x]| > 30} with Y = float32(0.299 R + 0.587 G + 0.114 B),
+ *     the sum in float64 from left to right.
+ *   fw_vhs_chroma_samples_u8 : samples int32 [m][3] = {frame, row, k}: x = the k-th such edge of the row; offsets int32 [m][2] = for R and
+ *     for B |x0 + argmax - x| of the channel's |step| over [x0, x1) = [max(0, x - 5), min(W - 2, x + 5)), first maximum, -1 when the
+ *     window is empty or the maximum is not above 20, -2 when the entry names no edge.  n <= 64, m <= 6400.
+ *   fw_vhs_chroma_shift_u8 : BGR; dst.R[x] = src.R[x - shift] for x >= shift, dst.B[x] = src.B[x + shift] for x < W - shift, every other
+ *     byte copied; shifts is a HOST table of n values in 0 .. 2.  n <= 32.
+ *   fw_vhs_column_sums_u8 : BGR; sums int64 [W - 1] = sum_y | |R - B|[y][x+1] - |R - B|[y][x] |.
+ *   fw_vhs_jitter_shifts_u8 : shifts int32 [(H + 2) / 5]: for rows y = 1, 6, 11 ... the first maximum over j of the exact int32
+ *     correlation sum_n g[y][n + j - W / 2] * g[y - 1][n], less W / 2 (numpy.correlate(..., "same") on integers).
+ *   fw_vhs_saturation_f64 : BGR; saturation float64 [H][W] = max > 0 ? (max - min) / (max + 1e-6) : 0.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers or tables, frame counts outside the limits above, height
+ * or width outside 1 .. 16384, channels other than 1 or 3, table lengths outside 1 .. 2^24, nothing asked of fw_vhs_gray_stats_u8,
+ * bottom rows of a frame of fewer than 30 rows, a strength outside (0, 1], a shift outside 0 .. 2, fewer than two columns (column
+ * sums) or three rows (jitter), a dst or result that overlaps a source frame of the call or another dst of the call. */
+int fw_vhs_gray_stats_u8(const void* const* frames /* host [n] */, int n, int height, int width, int channels, int min_length,
+                         int64_t* row_sums, uint8_t* bottom, int32_t* runs, int run_capacity, int32_t* run_count, void* stream);
+int fw_vhs_blend_rows_u8(const void* const* src /* host [n] */, void* const* dst /* host [n] */, int n, int rows, int64_t row_bytes,
+                         const int32_t* spec_rows /* device [m][4] */, const float* spec_factors /* device [m][2] */, int m, void* stream);
+int fw_vhs_rainbow_u8(const void* const* src /* host [n] */, void* const* dst /* host [n] */, int n, int height, int width, float fa, float fb,
+                      void* stream);
+int fw_vhs_box_gray_sums_u8(const void* const* frames /* host [n] */, int n, int height, int width, int channels,
+                            const int32_t* tasks /* device [m][5] */, int m, int64_t* sums /* device [m] */, void* stream);
+int fw_vhs_dropout_repair_u8(const void* const* sources /* host */, int n_sources, void* const* results /* host */, int n_results, int height,
+                             int width, int channels, const int32_t* boxes /* device [m][8] */, int m, double strength, void* stream);
+int fw_vhs_edge_counts_u8(const void* const* frames /* host [n] */, int n, int height, int width, int32_t* counts /* device [n][H] */,
+                          void* stream);
+int fw_vhs_chroma_samples_u8(const void* const* frames /* host [n] */, int n, int height, int width, const int32_t* samples /* device [m][3] */,
+                             int m, int32_t* offsets /* device [m][2] */, void* stream);
+int fw_vhs_chroma_shift_u8(const void* const* src /* host [n] */, void* const* dst /* host [n] */, const int32_t* shifts /* host [n] */, int n,
+                           int height, int width, void* stream);
+int fw_vhs_column_sums_u8(const uint8_t* frame, int height, int width, int64_t* sums /* device [W - 1] */, void* stream);
+int fw_vhs_jitter_shifts_u8(const uint8_t* frame, int height, int width, int channels, int32_t* shifts, void* stream);
+int fw_vhs_saturation_f64(const uint8_t* frame, int height, int width, double* saturation /* device [H][W] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

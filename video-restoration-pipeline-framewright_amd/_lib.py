@@ -52,6 +52,9 @@ EXPORTS = [
     "fw_pil_lanczos_taps", "fw_pil_thumb_workspace_bytes", "fw_pil_thumb_u8", "fw_dhash_pack_u8",
     "fw_lut3d_apply_u8", "fw_lut3d_apply_u16", "fw_table3_apply_u8",
     "fw_deinterlace_u8", "fw_deinterlace_batch_u8", "fw_interlace_stats_u8", "fw_frame_absdiff_sum_u8",
+    "fw_vhs_gray_stats_u8", "fw_vhs_blend_rows_u8", "fw_vhs_rainbow_u8", "fw_vhs_box_gray_sums_u8", "fw_vhs_dropout_repair_u8",
+    "fw_vhs_edge_counts_u8", "fw_vhs_chroma_samples_u8", "fw_vhs_chroma_shift_u8", "fw_vhs_column_sums_u8", "fw_vhs_jitter_shifts_u8",
+    "fw_vhs_saturation_f64",
 ]
 
 
@@ -355,6 +358,28 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_interlace_stats_u8.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.fw_frame_absdiff_sum_u8.restype = i32
     lib.fw_frame_absdiff_sum_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.fw_vhs_gray_stats_u8.restype = i32
+    lib.fw_vhs_gray_stats_u8.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
+    lib.fw_vhs_blend_rows_u8.restype = i32
+    lib.fw_vhs_blend_rows_u8.argtypes = [vp, vp, i32, i32, C.c_int64, vp, vp, i32, vp]
+    lib.fw_vhs_rainbow_u8.restype = i32
+    lib.fw_vhs_rainbow_u8.argtypes = [vp, vp, i32, i32, i32, f32, f32, vp]
+    lib.fw_vhs_box_gray_sums_u8.restype = i32
+    lib.fw_vhs_box_gray_sums_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp]
+    lib.fw_vhs_dropout_repair_u8.restype = i32
+    lib.fw_vhs_dropout_repair_u8.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, i32, C.c_double, vp]
+    lib.fw_vhs_edge_counts_u8.restype = i32
+    lib.fw_vhs_edge_counts_u8.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.fw_vhs_chroma_samples_u8.restype = i32
+    lib.fw_vhs_chroma_samples_u8.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
+    lib.fw_vhs_chroma_shift_u8.restype = i32
+    lib.fw_vhs_chroma_shift_u8.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    lib.fw_vhs_column_sums_u8.restype = i32
+    lib.fw_vhs_column_sums_u8.argtypes = [vp, i32, i32, vp, vp]
+    lib.fw_vhs_jitter_shifts_u8.restype = i32
+    lib.fw_vhs_jitter_shifts_u8.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.fw_vhs_saturation_f64.restype = i32
+    lib.fw_vhs_saturation_f64.argtypes = [vp, i32, i32, vp, vp]
 
 
 def load() -> C.CDLL:

@@ -32,16 +32,21 @@ class DeviceRestorationPipeline:
     its configured method and field order (BOB doubles the frame count downstream).  The streaming forms keep one frame of
     lookahead for BWDIF and refuse `FieldOrder.AUTO` (a stream has no "first 20 frames"); with an explicit order they equal
     `run_device`.
+
+    ``vhs_processor`` (a `vhs.DeviceVHSProcessor`; opt-in) runs its `process` on the input frames behind the deinterlacer and in front
+    of every other stage; the streaming forms use its `stream`, which keeps `temporal_radius` frames on both sides for the dropout
+    repair and equals `run_device`.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
-                 deinterlacer=None):
+                 deinterlacer=None, vhs_processor=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
         self.last_dedup_result = None
         self.color_grader = color_grader
         self.deinterlacer = deinterlacer
+        self.vhs_processor = vhs_processor
 
     @classmethod
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
@@ -61,6 +66,8 @@ class DeviceRestorationPipeline:
             dev = torch.device("cuda", self.color_grader.device_id)
         if dev is None and self.deinterlacer is not None:
             dev = torch.device("cuda", self.deinterlacer.device_id)
+        if dev is None and self.vhs_processor is not None:
+            dev = torch.device("cuda", self.vhs_processor.device_id)
         if dev is None:
             raise ValueError("DeviceRestorationPipeline: no stage configured")
 
@@ -71,6 +78,8 @@ class DeviceRestorationPipeline:
             cur = [up(f) for f in frames]
             if self.deinterlacer is not None:
                 cur = list(self.deinterlacer.deinterlace(cur))
+            if self.vhs_processor is not None:
+                cur = list(self.vhs_processor.process(cur))
             if self.denoiser is not None:
                 cur = self.denoiser.denoise_clip_device(cur)
             if self.upscaler is not None and self.deduplicator is not None and cur:
@@ -108,6 +117,8 @@ class DeviceRestorationPipeline:
             return torch.device("cuda", self.color_grader.device_id)
         if self.deinterlacer is not None:
             return torch.device("cuda", self.deinterlacer.device_id)
+        if self.vhs_processor is not None:
+            return torch.device("cuda", self.vhs_processor.device_id)
         raise ValueError("DeviceRestorationPipeline: no stage configured")
 
     def _gen_denoise(self, frames: Iterator, block: int):
@@ -183,6 +194,8 @@ class DeviceRestorationPipeline:
             g = gen_up()
             if self.deinterlacer is not None:
                 g = self.deinterlacer.stream(g, block=block)
+            if self.vhs_processor is not None:
+                g = self.vhs_processor.stream(g, block=block)
             if self.denoiser is not None:
                 g = self._gen_denoise(g, block)
             if self.upscaler is not None:
