@@ -467,6 +467,23 @@ def on_tensor_device(fn):
     return wrapped
 
 
+def ptr(t) -> C.c_void_p:
+    """The device address of a tensor as a pointer argument of the C-ABI."""
+    return C.c_void_p(t.data_ptr())
+
+
+def ptr_table(tensors) -> C.Array:
+    """A host table of the tensors' device addresses (a ``const void* const*`` argument), in the order given."""
+    tensors = list(tensors)
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def stream_ptr(dev) -> C.c_void_p:
+    """torch's current stream on ``dev`` as the stream argument of the C-ABI."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
 def empty_like_many(frames) -> list:
     """Output buffers for a batch of frames: ONE allocation cut into views when the frames agree in shape (the usual clip), else one
     per frame.  A hipMalloc is a device-wide synchronisation: a hundred of them in front of a hundred forwards that are meant to

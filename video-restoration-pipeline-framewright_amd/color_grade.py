@@ -372,15 +372,15 @@ class DeviceColorGrader:
     # ---- one launch ------------------------------------------------------------------------------------------------------------
     def _launch(self, src_ptr: int, src_stride: int, n: int, h: int, w: int, wide: bool, dst_ptr: int, dst_stride: int, dev) -> None:
         import torch
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.stream_ptr(dev)
         if self.size:
             fn = self._lib.fw_lut3d_apply_u16 if wide else self._lib.fw_lut3d_apply_u8
-            _lib.check(fn(C.c_void_p(src_ptr), src_stride, n, h, w, C.c_void_p(self._table.data_ptr()), self.size, int(self.bgr),
+            _lib.check(fn(C.c_void_p(src_ptr), src_stride, n, h, w, _lib.ptr(self._table), self.size, int(self.bgr),
                           C.c_void_p(dst_ptr), dst_stride, st))
         else:
             if wide:
                 raise ValueError("a 1D LUT grades 8-bit frames only")
-            _lib.check(self._lib.fw_table3_apply_u8(C.c_void_p(src_ptr), src_stride, n, h, w, C.c_void_p(self._table.data_ptr()),
+            _lib.check(self._lib.fw_table3_apply_u8(C.c_void_p(src_ptr), src_stride, n, h, w, _lib.ptr(self._table),
                                                     C.c_void_p(dst_ptr), dst_stride, st))
 
     @staticmethod

@@ -23,8 +23,7 @@
 // as one load (at the last plane, where hi == lo, the pair one step back is loaded and its upper entry serves as both).
 // The 8-bit s values are a 256-entry table in LDS, one division per entry and workgroup; 16-bit samples are divided as they come.
 // No atomics, no scratch; a frame's result depends on its bytes and the table alone, not on the run, the batch or its address.
-#include "framewright_hip.h"
-#include "fw_internal.h"
+#include "stage_common.h"
 
 #include <algorithm>
 
@@ -42,16 +41,6 @@ constexpr int CL_BLOCKS_LDS = 512, CL_BLOCKS = 2048;                  // workgro
 struct __attribute__((packed, aligned(4))) Corner2 {                  // table[r][g][b] and table[r][g][b + 1]
     float v[6];
 };
-
-// The aligned word at `p`, of which only the bytes inside [lo, hi) are read: one load when the word lies inside, else its bytes.
-__device__ __forceinline__ uint32_t load_word_inside(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
-    if (p >= lo && p + 4 <= hi) return *reinterpret_cast<const uint32_t*>(p);
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (p + k >= lo && p + k < hi) v |= (uint32_t)p[k] << (8 * k);
-    return v;
-}
 
 // Four pixels per lane and turn: op(v, o) maps the 12 samples v (stored order) of pixels 4 g .. 4 g + 3 to the 12 samples o.
 // Samples behind the frame's last pixel read as 0 and are not written.
@@ -189,19 +178,14 @@ __global__ __launch_bounds__(CL_NT) void table3_kernel(const uint8_t* src, long 
     });
 }
 
-int cl_fail(const char* fn, const std::string& m) {
-    last_error_ref() = std::string(fn) + ": " + m;
-    return FW_ERR_INVALID;
-}
-
 // 0 when the frame arguments are usable, else the status of the refusal (message set)
 int cl_check_frames(const char* fn, const void* src, int64_t src_stride, int n, int H, int W, const void* dst, int64_t dst_stride, int bytes) {
-    if (!src || !dst) return cl_fail(fn, "null pointer");
+    if (!src || !dst) return invalid(fn, "null pointer");
     if (n < 1 || n > 65535 || H < 1 || W < 1 || H > CL_MAX_SIDE || W > CL_MAX_SIDE)
-        return cl_fail(fn, "1 .. 65535 frames of 1 .. 16384 pixels a side expected");
-    if (src_stride < 0 || dst_stride < 0 || (n > 1 && (src_stride == 0 || dst_stride == 0))) return cl_fail(fn, "bad frame stride");
+        return invalid(fn, "1 .. 65535 frames of 1 .. 16384 pixels a side expected");
+    if (src_stride < 0 || dst_stride < 0 || (n > 1 && (src_stride == 0 || dst_stride == 0))) return invalid(fn, "bad frame stride");
     if (bytes == 2 && (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)src_stride | (uintptr_t)dst_stride) & 1))
-        return cl_fail(fn, "16-bit frames start on even addresses");
+        return invalid(fn, "16-bit frames start on even addresses");
     return FW_OK;
 }
 
@@ -215,8 +199,8 @@ template <typename T>
 int lut3d_apply(const char* fn, const void* src, int64_t src_stride, int n, int H, int W, const float* lut, int size, int bgr, void* dst,
                 int64_t dst_stride, void* stream) {
     if (const int st = cl_check_frames(fn, src, src_stride, n, H, W, dst, dst_stride, (int)sizeof(T))) return st;
-    if (!lut) return cl_fail(fn, "null pointer");
-    if (size < CL_MIN_SIZE || size > CL_MAX_SIZE) return cl_fail(fn, "a table size of 2 .. 65 expected");
+    if (!lut) return invalid(fn, "null pointer");
+    if (size < CL_MIN_SIZE || size > CL_MAX_SIZE) return invalid(fn, "a table size of 2 .. 65 expected");
     const long npix = (long)H * W;
     const long ss = n > 1 ? (long)src_stride : 0, ds = n > 1 ? (long)dst_stride : 0;
     hipStream_t st = (hipStream_t)stream;
@@ -228,12 +212,7 @@ int lut3d_apply(const char* fn, const void* src, int64_t src_stride, int n, int 
         hipLaunchKernelGGL((lut3d_kernel<T, false>), cl_grid(npix, n, CL_BLOCKS), dim3(CL_NT), 0, st, (const uint8_t*)src, ss, npix, lut, size,
                            bgr ? 1 : 0, (uint8_t*)dst, ds);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        last_error_ref() = std::string(fn) + ": HIP error: " + hipGetErrorString(e);
-        return FW_ERR_HIP;
-    }
-    return FW_OK;
+    return hip_status(fn, hipGetLastError());
 }
 
 }  // namespace
@@ -257,16 +236,11 @@ int fw_table3_apply_u8(const uint8_t* src, int64_t src_stride_bytes, int n, int 
                        int64_t dst_stride_bytes, void* stream) {
     const char* fn = "fw_table3_apply_u8";
     if (const int st = cl_check_frames(fn, src, src_stride_bytes, n, height, width, dst, dst_stride_bytes, 1)) return st;
-    if (!tables) return cl_fail(fn, "null pointer");
+    if (!tables) return invalid(fn, "null pointer");
     const long npix = (long)height * width;
     const long ss = n > 1 ? (long)src_stride_bytes : 0, ds = n > 1 ? (long)dst_stride_bytes : 0;
     hipLaunchKernelGGL(table3_kernel, cl_grid(npix, n, CL_BLOCKS), dim3(CL_NT), 0, (hipStream_t)stream, src, ss, npix, tables, dst, ds);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        last_error_ref() = std::string(fn) + ": HIP error: " + hipGetErrorString(e);
-        return FW_ERR_HIP;
-    }
-    return FW_OK;
+    return hip_status(fn, hipGetLastError());
 }
 
 }  // extern "C"

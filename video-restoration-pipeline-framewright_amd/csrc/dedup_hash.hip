@@ -18,8 +18,7 @@
 //
 // Every sum is uint32 with wrap-around, so any order of the additions gives Pillow's int32 result; no atomics anywhere.  A frame's
 // thumbnail depends on its bytes and the sizes alone, not on the run, the batch it is in or where the frame lies.
-#include "framewright_hip.h"
-#include "fw_internal.h"
+#include "stage_common.h"
 
 #include <math.h>
 
@@ -95,22 +94,6 @@ constexpr int PT_MAX_OUT = 65, PT_MAX_SIDE = 16384;
 constexpr size_t PT_LDS_BUDGET = 60 * 1024;                           // dynamic LDS of the horizontal kernel
 constexpr int PT_ROW_BLOCKS = 1024;                                   // workgroups of one horizontal launch, about
 
-// The aligned word at `p`, of which only the bytes inside [lo, hi) are read: one load when the word lies inside, else its bytes.
-__device__ __forceinline__ uint32_t load_word_inside(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
-    if (p >= lo && p + 4 <= hi) return *reinterpret_cast<const uint32_t*>(p);
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (p + k >= lo && p + k < hi) v |= (uint32_t)p[k] << (8 * k);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += (uint32_t)__shfl_down((int)v, d, 64);
-    return v;                                                         // lane 0 holds the sum
-}
-
 __device__ __forceinline__ uint32_t pil_clip8(uint32_t sum) {
     const int v = (int)(sum + (1u << (PIL_PRECISION_BITS - 1))) >> PIL_PRECISION_BITS;
     return (uint32_t)min(max(v, 0), 255);
@@ -183,7 +166,7 @@ __global__ __launch_bounds__(PT_NT) void pil_hpass_kernel(const uint8_t* __restr
             const int32_t* tp = taps + (size_t)xx * ksize;
             uint32_t s = 0;
             for (int k = lane; k < cnt; k += 64) s += (uint32_t)px[k] * (uint32_t)tp[k];
-            s = wave_sum_u32(s);
+            s = wave_sum(s);
             if (lane == 0) out[((size_t)c * H + y) * out_w + xx] = (uint8_t)pil_clip8(s);
         }
     }
@@ -207,7 +190,7 @@ __global__ __launch_bounds__(PT_NT) void pil_vpass_kernel(const uint8_t* __restr
         }
         uint32_t s = 0;
         for (int k = lane; k < cnt; k += 64) s += (uint32_t)p[(size_t)k * out_w] * (uint32_t)tp[k];
-        s = wave_sum_u32(s);
+        s = wave_sum(s);
         if (lane == 0) s_res[item] = (uint8_t)pil_clip8(s);
     }
     __syncthreads();
@@ -236,23 +219,6 @@ __global__ __launch_bounds__(PT_NT) void dhash_pack_kernel(const uint8_t* __rest
         v = (v << 1) | bit;
     }
     bits[i] = (uint8_t)v;
-}
-
-int dd_fail(int code, const std::string& m) {
-    last_error_ref() = m;
-    return code;
-}
-
-template <typename F>
-int dd_guard(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return dd_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return dd_fail(FW_ERR_INTERNAL, e.what());
-    }
 }
 
 std::mutex g_mutex;
@@ -304,11 +270,11 @@ size_t fw_pil_thumb_workspace_bytes(int n, int height, int width, int out_w, int
 
 int fw_pil_thumb_u8(const uint8_t* frames_bgr, int64_t frame_stride_bytes, int n, int height, int width, int out_w, int out_h,
                     int gray_first, uint8_t* thumbs, void* workspace, void* stream) {
-    if (!frames_bgr || !thumbs || !workspace) return dd_fail(FW_ERR_INVALID, "fw_pil_thumb_u8: null pointer");
+    if (!frames_bgr || !thumbs || !workspace) return fail(FW_ERR_INVALID, "fw_pil_thumb_u8: null pointer");
     if (!thumb_args_ok(n, height, width, out_w, out_h))
-        return dd_fail(FW_ERR_INVALID, "fw_pil_thumb_u8: 1 .. 65535 frames of 1 .. 16384 pixels a side and thumbnails of 1 .. 65 a side expected");
-    if (frame_stride_bytes < 0 || (n > 1 && frame_stride_bytes == 0)) return dd_fail(FW_ERR_INVALID, "fw_pil_thumb_u8: bad frame stride");
-    return dd_guard([&] {
+        return fail(FW_ERR_INVALID, "fw_pil_thumb_u8: 1 .. 65535 frames of 1 .. 16384 pixels a side and thumbnails of 1 .. 65 a side expected");
+    if (frame_stride_bytes < 0 || (n > 1 && frame_stride_bytes == 0)) return fail(FW_ERR_INVALID, "fw_pil_thumb_u8: bad frame stride");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const int C = gray_first ? 1 : 3;
         const int32_t* ht = width != out_w ? device_table(width, out_w) : nullptr;
@@ -333,10 +299,10 @@ int fw_pil_thumb_u8(const uint8_t* frames_bgr, int64_t frame_stride_bytes, int n
 }
 
 int fw_dhash_pack_u8(const uint8_t* thumbs, int n, int hash_size, uint8_t* bits, void* stream) {
-    if (!thumbs || !bits) return dd_fail(FW_ERR_INVALID, "fw_dhash_pack_u8: null pointer");
+    if (!thumbs || !bits) return fail(FW_ERR_INVALID, "fw_dhash_pack_u8: null pointer");
     if (n < 1 || n > 65535 || hash_size < 2 || hash_size > 64)
-        return dd_fail(FW_ERR_INVALID, "fw_dhash_pack_u8: 1 .. 65535 thumbnails and a hash size of 2 .. 64 expected");
-    return dd_guard([&] {
+        return fail(FW_ERR_INVALID, "fw_dhash_pack_u8: 1 .. 65535 thumbnails and a hash size of 2 .. 64 expected");
+    return guarded([&] {
         const long total = (long)n * ((hash_size * hash_size + 7) / 8);
         hipLaunchKernelGGL(dhash_pack_kernel, dim3((unsigned)((total + PT_NT - 1) / PT_NT)), dim3(PT_NT), 0, (hipStream_t)stream, thumbs, n,
                            hash_size, bits);

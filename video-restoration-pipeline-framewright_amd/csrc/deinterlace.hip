@@ -24,12 +24,7 @@
 // The statistics are integer sums, so their order is free: a wave takes a row pair, reduces its three sums with cross-lane shuffles
 // and adds them to the frame's four int64 with 64-bit atomic adds from vector memory instructions (global_atomic_add_x2) on a
 // buffer the entry zeroes on the same stream; the result is the same in every run.
-#include "framewright_hip.h"
-#include "fw_internal.h"
-
-#include <algorithm>
-#include <utility>
-#include <vector>
+#include "stage_common.h"
 
 #pragma clang fp contract(off)
 
@@ -38,7 +33,7 @@ namespace {
 
 constexpr int DI_NT = 256;
 constexpr int DI_BATCH = 32;                                          // frames of one launch (4 x 32 pointers by value)
-constexpr int DI_MAX_ROWS = 16384;
+constexpr int DI_MAX_ROWS = MAX_FRAME_SIDE;
 constexpr long DI_MAX_ROW_BYTES = 4L * 16384;
 constexpr int DI_BLOCKS = 4096;                                       // workgroups of one launch, all frames together, about
 
@@ -181,24 +176,6 @@ __global__ __launch_bounds__(DI_NT) void deinterlace_kernel(const DiTasks tasks,
 }
 
 // ---- statistics -------------------------------------------------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ int gray_at(const uint8_t* p) {
-    if constexpr (C == 1) return p[0];
-    else return (p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // one wave per row pair r: rows 2r, 2r+1 and, for r < R-1, 2r+2, 2r+3; out[f] = {n_comb, s_field, s_odd, s_even}
 template <int C>
 __global__ __launch_bounds__(DI_NT) void interlace_stats_kernel(const DiTasks tasks, int H, int W, unsigned long long* out) {
@@ -213,10 +190,10 @@ __global__ __launch_bounds__(DI_NT) void interlace_stats_kernel(const DiTasks ta
         const bool more = r < R - 1;
         uint32_t sf = 0, so = 0, se = 0;                              // a row's sum is at most 255 * 16384
         for (int x = lane; x < W; x += 64) {
-            const int g0 = gray_at<C>(r0 + (long)x * C), g1 = gray_at<C>(r0 + rb + (long)x * C);
+            const int g0 = gray_bgr<C>(r0 + (long)x * C), g1 = gray_bgr<C>(r0 + rb + (long)x * C);
             sf += (uint32_t)abs(g1 - g0);
             if (more) {
-                const int g2 = gray_at<C>(r0 + 2 * rb + (long)x * C), g3 = gray_at<C>(r0 + 3 * rb + (long)x * C);
+                const int g2 = gray_bgr<C>(r0 + 2 * rb + (long)x * C), g3 = gray_bgr<C>(r0 + 3 * rb + (long)x * C);
                 se += (uint32_t)abs(g2 - g0);
                 so += (uint32_t)abs(g3 - g1);
             }
@@ -242,61 +219,36 @@ __global__ __launch_bounds__(DI_NT) void absdiff_sum_kernel(const DiTasks tasks,
     const uint8_t* b = tasks.prev[f];
     unsigned long long s = 0;
     for (long i = (long)blockIdx.x * DI_NT + threadIdx.x; i < npix; i += (long)gridDim.x * DI_NT)
-        s += (unsigned long long)abs(gray_at<C>(a + i * C) - gray_at<C>(b + i * C));
-    s = wave_sum64(s);
+        s += (unsigned long long)abs(gray_bgr<C>(a + i * C) - gray_bgr<C>(b + i * C));
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out + f, s);
 }
 
-int di_fail(const char* fn, const std::string& m) {
-    last_error_ref() = std::string(fn) + ": " + m;
-    return FW_ERR_INVALID;
-}
-
-int di_hip(const char* fn, hipError_t e) {
-    if (e == hipSuccess) return FW_OK;
-    (void)hipGetLastError();
-    last_error_ref() = std::string(fn) + ": HIP error: " + hipGetErrorString(e);
-    return FW_ERR_HIP;
-}
-
-// true when a destination of the call overlaps a source of the call, of its own frame or of another: all frames are `bytes` long,
-// so after sorting the start addresses a destination overlaps a source exactly when one follows the other within `bytes`
-bool any_overlap(std::vector<std::pair<uintptr_t, int>>& marks, size_t bytes) {
-    std::sort(marks.begin(), marks.end());
-    uintptr_t last[2] = {0, 0};                                      // the latest start seen of a destination (0) / a source (1)
-    bool seen[2] = {false, false};
-    for (const auto& m : marks) {
-        const int other = 1 - m.second;
-        if (seen[other] && m.first - last[other] < bytes) return true;
-        last[m.second] = m.first, seen[m.second] = true;
-    }
-    return false;
-}
-
-// tasks: n x {cur, prev, next, dst}; everything is checked before the first launch
+// tasks: n x {cur, prev, next, dst}; everything is checked before the first launch (prev and next may be null unless the mode reads
+// them, so the table is checked here and not by check_pointer_table)
 int deinterlace_run(const char* fn, const void* const* table, int n, int rows, int64_t row_bytes, int mode, int parity, hipStream_t st) {
-    if (!table) return di_fail(fn, "null pointer");
-    if (n < 1) return di_fail(fn, "at least one frame expected");
+    if (!table) return invalid(fn, "null pointer");
+    if (n < 1) return invalid(fn, "at least one frame expected");
     if (rows < 1 || rows > DI_MAX_ROWS || row_bytes < 1 || row_bytes > DI_MAX_ROW_BYTES)
-        return di_fail(fn, "1 .. 16384 rows of 1 .. 65536 bytes expected");
-    if (mode != FW_DEINTERLACE_YADIF && mode != FW_DEINTERLACE_BWDIF && mode != FW_DEINTERLACE_BOB) return di_fail(fn, "unknown mode");
-    if (parity != 0 && parity != 1) return di_fail(fn, "parity is 0 (even rows) or 1 (odd rows)");
-    if (mode == FW_DEINTERLACE_BOB && rows < 2) return di_fail(fn, "BOB needs two rows: the odd field of one row is empty");
+        return invalid(fn, "1 .. 16384 rows of 1 .. 65536 bytes expected");
+    if (mode != FW_DEINTERLACE_YADIF && mode != FW_DEINTERLACE_BWDIF && mode != FW_DEINTERLACE_BOB) return invalid(fn, "unknown mode");
+    if (parity != 0 && parity != 1) return invalid(fn, "parity is 0 (even rows) or 1 (odd rows)");
+    if (mode == FW_DEINTERLACE_BOB && rows < 2) return invalid(fn, "BOB needs two rows: the odd field of one row is empty");
     const bool temporal = mode == FW_DEINTERLACE_BWDIF;
     const size_t bytes = (size_t)rows * (size_t)row_bytes;
-    std::vector<std::pair<uintptr_t, int>> marks;
+    FrameMarks marks;
     marks.reserve(4 * (size_t)n);
     for (int i = 0; i < n; ++i) {
         const void* cur = table[4 * i];
         const void* prev = table[4 * i + 1];
         const void* next = table[4 * i + 2];
         const void* dst = table[4 * i + 3];
-        if (!cur || !dst || (temporal && (!prev || !next))) return di_fail(fn, "null pointer");
+        if (!cur || !dst || (temporal && (!prev || !next))) return invalid(fn, "null pointer");
         marks.emplace_back((uintptr_t)dst, 0);
         marks.emplace_back((uintptr_t)cur, 1);
         if (temporal) marks.emplace_back((uintptr_t)prev, 1), marks.emplace_back((uintptr_t)next, 1);
     }
-    if (any_overlap(marks, bytes)) return di_fail(fn, "a dst overlaps a source frame of the call (rebuilt rows are read as neighbours)");
+    if (frames_overlap(marks, bytes)) return invalid(fn, "a dst overlaps a source frame of the call (rebuilt rows are read as neighbours)");
     const int field_rows = (rows + 1 - parity) >> 1;
     const double bob_scale = 1.0 / ((double)rows / (double)field_rows);
     for (int base = 0; base < n; base += DI_BATCH) {
@@ -323,19 +275,17 @@ int deinterlace_run(const char* fn, const void* const* table, int n, int rows, i
         if (V == 16) hipLaunchKernelGGL(deinterlace_kernel<16>, grid, dim3(DI_NT), 0, st, t, rows, (int)row_bytes, mode, parity, bob_scale);
         else if (V == 4) hipLaunchKernelGGL(deinterlace_kernel<4>, grid, dim3(DI_NT), 0, st, t, rows, (int)row_bytes, mode, parity, bob_scale);
         else hipLaunchKernelGGL(deinterlace_kernel<1>, grid, dim3(DI_NT), 0, st, t, rows, (int)row_bytes, mode, parity, bob_scale);
-        if (const int s = di_hip(fn, hipGetLastError())) return s;
+        if (const int s = hip_status(fn, hipGetLastError())) return s;
     }
     return FW_OK;
 }
 
 int stats_check(const char* fn, const void* const* a, const void* const* b, bool pairs, int n, int H, int W, int C, const void* out) {
-    if (!a || !out || (pairs && !b)) return di_fail(fn, "null pointer");
-    if (n < 1) return di_fail(fn, "at least one frame expected");
-    if (H < 1 || H > DI_MAX_ROWS || W < 1 || W > DI_MAX_ROWS) return di_fail(fn, "1 .. 16384 pixels a side expected");
-    if (C != 1 && C != 3) return di_fail(fn, "1 (gray) or 3 (BGR) channels expected");
-    for (int i = 0; i < n; ++i)
-        if (!a[i] || (pairs && !b[i])) return di_fail(fn, "null pointer");
-    return FW_OK;
+    if (!out) return invalid(fn, "null pointer");
+    if (const int s = check_pointer_table(fn, a, n, 0)) return s;
+    if (pairs)
+        if (const int s = check_pointer_table(fn, b, n, 0)) return s;
+    return check_side_and_channels(fn, H, W, C);
 }
 
 }  // namespace
@@ -359,7 +309,7 @@ int fw_interlace_stats_u8(const void* const* frames, int n, int height, int widt
     const char* fn = "fw_interlace_stats_u8";
     if (const int s = stats_check(fn, frames, nullptr, false, n, height, width, channels, stats)) return s;
     hipStream_t st = (hipStream_t)stream;
-    if (const int s = di_hip(fn, hipMemsetAsync(stats, 0, (size_t)n * 4 * sizeof(int64_t), st))) return s;
+    if (const int s = hip_status(fn, hipMemsetAsync(stats, 0, (size_t)n * 4 * sizeof(int64_t), st))) return s;
     const int R = height / 2;
     for (int base = 0; base < n; base += DI_BATCH) {
         const int m = std::min(DI_BATCH, n - base);
@@ -370,7 +320,7 @@ int fw_interlace_stats_u8(const void* const* frames, int n, int height, int widt
         unsigned long long* out = reinterpret_cast<unsigned long long*>(stats) + 4L * base;
         if (channels == 3) hipLaunchKernelGGL(interlace_stats_kernel<3>, grid, dim3(DI_NT), 0, st, t, height, width, out);
         else hipLaunchKernelGGL(interlace_stats_kernel<1>, grid, dim3(DI_NT), 0, st, t, height, width, out);
-        if (const int s = di_hip(fn, hipGetLastError())) return s;
+        if (const int s = hip_status(fn, hipGetLastError())) return s;
     }
     return FW_OK;
 }
@@ -380,7 +330,7 @@ int fw_frame_absdiff_sum_u8(const void* const* a, const void* const* b, int n, i
     const char* fn = "fw_frame_absdiff_sum_u8";
     if (const int s = stats_check(fn, a, b, true, n, height, width, channels, sums)) return s;
     hipStream_t st = (hipStream_t)stream;
-    if (const int s = di_hip(fn, hipMemsetAsync(sums, 0, (size_t)n * sizeof(int64_t), st))) return s;
+    if (const int s = hip_status(fn, hipMemsetAsync(sums, 0, (size_t)n * sizeof(int64_t), st))) return s;
     const long npix = (long)height * width;
     for (int base = 0; base < n; base += DI_BATCH) {
         const int m = std::min(DI_BATCH, n - base);
@@ -394,7 +344,7 @@ int fw_frame_absdiff_sum_u8(const void* const* a, const void* const* b, int n, i
         unsigned long long* out = reinterpret_cast<unsigned long long*>(sums) + base;
         if (channels == 3) hipLaunchKernelGGL(absdiff_sum_kernel<3>, grid, dim3(DI_NT), 0, st, t, npix, out);
         else hipLaunchKernelGGL(absdiff_sum_kernel<1>, grid, dim3(DI_NT), 0, st, t, npix, out);
-        if (const int s = di_hip(fn, hipGetLastError())) return s;
+        if (const int s = hip_status(fn, hipGetLastError())) return s;
     }
     return FW_OK;
 }

@@ -1,13 +1,12 @@
 // Host-side scaffolding shared by the six network sequencers (rrdbnet, nafnet, ifnet, restormer, srvgg, aesrgan .hip): device
-// buffers, the workspace, the status / last-error mapping of the C-ABI and the hipGraph cache.  The lifetime and ordering rules of
-// the library's host layer live here, once.  Included by those six files only; no device code.
+// buffers, the workspace and the hipGraph cache.  The lifetime and ordering rules of the library's host layer live here, once.
+// The status / last-error mapping of the C-ABI (fail, guarded) is fw_status.h, which the frame-stage files share through
+// stage_common.h.  No device code.
 #pragma once
 #include <array>
-#include <new>
 #include <string>
 #include <vector>
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "fw_status.h"
 
 namespace fw {
 
@@ -40,26 +39,6 @@ struct Arena {
         return base + at;   // plan mode: base == nullptr, the pointer is never dereferenced or launched on
     }
 };
-
-// ---- C-ABI status: a code for the caller, the message for fw_last_error() -------------------------------------------------------
-inline int fail(int code, const std::string& msg) {
-    last_error_ref() = msg;
-    return code;
-}
-
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        return fail(FW_ERR_OOM, "host out of memory");
-    } catch (const std::exception& e) {
-        return fail(FW_ERR_INTERNAL, e.what());
-    }
-}
 
 // ---- hipGraph replay of a forward -----------------------------------------------------------------------------------------------
 // One executable graph per key.  The key is everything a captured launch sequence bakes in - frame size, sample format, scalar

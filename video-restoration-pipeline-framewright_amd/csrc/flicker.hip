@@ -17,8 +17,7 @@
 // (address & 3) pixels and its last (n - head) % 4 go byte by byte.  Every lane reads its pixels before it writes them and no
 // other lane touches those bytes, so dst may alias src.  The small tables (decode, fy / Y / a / b, thresholds, the frame's LUT:
 // 5.4 KiB) are copied to LDS per workgroup; the 65281-entry f(t) table (255 KiB) is gathered from global memory, where it stays in L2.
-#include "fw_internal.h"
-#include "framewright_hip.h"
+#include "stage_common.h"
 #include "lab_tables.h"
 
 #include <cmath>
@@ -83,11 +82,6 @@ __device__ __forceinline__ uint32_t bgr_to_lab_px(uint32_t p, const SmallTables&
     return (uint32_t)l_of_fy(k, fy) | (uint32_t)a << 8 | (uint32_t)b << 16;
 }
 
-__device__ __forceinline__ long long inv_g(long long t, const LabInv& k) {
-    if (t > k.thr) return (t * t * t + (1ll << (2 * F_BITS - 1))) >> (2 * F_BITS);
-    return ((t - k.c16) * k.kinv + (1ll << (F_BITS - 1))) >> F_BITS;
-}
-
 // the number of thresholds <= v: the contract's encode[v]
 __device__ __forceinline__ uint32_t srgb_encode(const uint16_t* thr, int v) {
     int n = 0;
@@ -100,7 +94,7 @@ __device__ __forceinline__ uint32_t srgb_encode(const uint16_t* thr, int v) {
 __device__ __forceinline__ uint32_t lab_to_bgr_px(uint32_t p, const SmallTables& s, const LabInv& k) {
     const int L = p & 255u, a = (p >> 8) & 255u, b = (p >> 16) & 255u;
     const long long fy = s.t256[L];
-    const long long v[3] = {inv_g(fy + s.t256[512 + a], k), (long long)s.t256[256 + L], inv_g(fy - s.t256[768 + b], k)};
+    const long long v[3] = {lab_inv_g(fy + s.t256[512 + a], k), (long long)s.t256[256 + L], lab_inv_g(fy - s.t256[768 + b], k)};
     uint32_t out = 0;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(FK_NT) void l_sums_kernel(const uint8_t* __restrict
         const long p = i < sl.head ? i : sl.tail0 + (i - sl.head);
         sum += l_of_px(load_px(sp + 3 * p), dec, kf, cbrt_tab);
     }
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0 && sum != 0) atomicAdd(&l_sums[f], sum);
 }
 
@@ -251,23 +245,6 @@ int* device_small() {
     return d;
 }
 
-int fk_fail(int code, const std::string& m) {
-    last_error_ref() = m;
-    return code;
-}
-
-template <typename F>
-int fk_guard(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return fk_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fk_fail(FW_ERR_INTERNAL, e.what());
-    }
-}
-
 constexpr long MAX_PIXELS = 1L << 30;
 
 // workgroups per frame: a lane takes four pixels per step, and a workgroup stays long enough to pay for its copy of the tables
@@ -302,22 +279,22 @@ using namespace fw;
 extern "C" {
 
 int fw_bgr_to_lab_u8(const uint8_t* src_bgr, int64_t n_pixels, uint8_t* dst_lab, void* stream) {
-    if (!src_bgr || !dst_lab) return fk_fail(FW_ERR_INVALID, "fw_bgr_to_lab_u8: null pointer");
-    if (n_pixels < 1 || n_pixels > MAX_PIXELS) return fk_fail(FW_ERR_INVALID, "fw_bgr_to_lab_u8: 1 .. 2^30 pixels expected");
-    return fk_guard([&] { launch_map<MODE_FWD>(src_bgr, dst_lab, 1, (long)n_pixels, nullptr, (hipStream_t)stream); });
+    if (!src_bgr || !dst_lab) return fail(FW_ERR_INVALID, "fw_bgr_to_lab_u8: null pointer");
+    if (n_pixels < 1 || n_pixels > MAX_PIXELS) return fail(FW_ERR_INVALID, "fw_bgr_to_lab_u8: 1 .. 2^30 pixels expected");
+    return guarded([&] { launch_map<MODE_FWD>(src_bgr, dst_lab, 1, (long)n_pixels, nullptr, (hipStream_t)stream); });
 }
 
 int fw_lab_to_bgr_u8(const uint8_t* src_lab, int64_t n_pixels, uint8_t* dst_bgr, void* stream) {
-    if (!src_lab || !dst_bgr) return fk_fail(FW_ERR_INVALID, "fw_lab_to_bgr_u8: null pointer");
-    if (n_pixels < 1 || n_pixels > MAX_PIXELS) return fk_fail(FW_ERR_INVALID, "fw_lab_to_bgr_u8: 1 .. 2^30 pixels expected");
-    return fk_guard([&] { launch_map<MODE_INV>(src_lab, dst_bgr, 1, (long)n_pixels, nullptr, (hipStream_t)stream); });
+    if (!src_lab || !dst_bgr) return fail(FW_ERR_INVALID, "fw_lab_to_bgr_u8: null pointer");
+    if (n_pixels < 1 || n_pixels > MAX_PIXELS) return fail(FW_ERR_INVALID, "fw_lab_to_bgr_u8: 1 .. 2^30 pixels expected");
+    return guarded([&] { launch_map<MODE_INV>(src_lab, dst_bgr, 1, (long)n_pixels, nullptr, (hipStream_t)stream); });
 }
 
 int fw_lab_l_sums_u8(const uint8_t* frames_bgr, int count, int height, int width, int64_t* l_sums, void* stream) {
-    if (!frames_bgr || !l_sums) return fk_fail(FW_ERR_INVALID, "fw_lab_l_sums_u8: null pointer");
+    if (!frames_bgr || !l_sums) return fail(FW_ERR_INVALID, "fw_lab_l_sums_u8: null pointer");
     const std::string bad = check_frames("fw_lab_l_sums_u8", count, height, width);
-    if (!bad.empty()) return fk_fail(FW_ERR_INVALID, bad);
-    return fk_guard([&] {
+    if (!bad.empty()) return fail(FW_ERR_INVALID, bad);
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const LabTables& t = lab_tables();
         const DeviceLab lab = device_lab();
@@ -331,10 +308,10 @@ int fw_lab_l_sums_u8(const uint8_t* frames_bgr, int count, int height, int width
 }
 
 int fw_deflicker_lab_u8(const uint8_t* frames_bgr, int count, int height, int width, const uint8_t* l_luts, uint8_t* dst_bgr, void* stream) {
-    if (!frames_bgr || !l_luts || !dst_bgr) return fk_fail(FW_ERR_INVALID, "fw_deflicker_lab_u8: null pointer");
+    if (!frames_bgr || !l_luts || !dst_bgr) return fail(FW_ERR_INVALID, "fw_deflicker_lab_u8: null pointer");
     const std::string bad = check_frames("fw_deflicker_lab_u8", count, height, width);
-    if (!bad.empty()) return fk_fail(FW_ERR_INVALID, bad);
-    return fk_guard([&] { launch_map<MODE_DEFLICKER>(frames_bgr, dst_bgr, count, (long)height * width, l_luts, (hipStream_t)stream); });
+    if (!bad.empty()) return fail(FW_ERR_INVALID, bad);
+    return guarded([&] { launch_map<MODE_DEFLICKER>(frames_bgr, dst_bgr, count, (long)height * width, l_luts, (hipStream_t)stream); });
 }
 
 int fw_gamma_lab_tables(int which, int32_t* out, int capacity) {

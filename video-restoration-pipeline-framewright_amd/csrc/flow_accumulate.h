@@ -6,16 +6,9 @@
 // coefficients, (sum + 2^14) >> 15); cv2 parity is unpinned, oracle/temporal_ref.py is the contract.
 // Both translation units are compiled with -ffp-contract=off: value * weight rounds before it is added.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "stage_common.h"
 
 namespace fw {
-
-__device__ __forceinline__ int reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - p - 2;
-    return p;
-}
 
 // One grid-stride pass over the H x W pixels; weight(i) is the float64 weight of pixel i.  fx == NULL: the frame as it is.
 template <typename WeightFn>

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 #include "fw_internal.h"
+#include "stage_common.h"   // gray_bgr, reflect101
 #include "flow_accumulate.h"
 
 // The blend kernels below restate float32 numpy arithmetic bit for bit: a*b+c must round twice, so this translation
@@ -760,15 +761,13 @@ struct GrainKernel {
     int k[19];
 };
 
-__device__ __forceinline__ int gray_of(const uint8_t* px) { return (px[0] * 1868 + px[1] * 9617 + px[2] * 4899 + (1 << 13)) >> 14; }
-
 __global__ __launch_bounds__(256) void grain_hblur_kernel(const uint8_t* __restrict__ bgr, int H, int W, uint16_t* hbuf, GrainKernel gk) {
     const long n = (long)H * W;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int y = (int)(i / W), x = (int)(i - (long)y * W);
         int acc = 0;
 #pragma unroll
-        for (int j = 0; j < 19; ++j) acc += gk.k[j] * gray_of(bgr + ((long)y * W + reflect101(x + j - 9, W)) * 3);
+        for (int j = 0; j < 19; ++j) acc += gk.k[j] * gray_bgr<3>(bgr + ((long)y * W + reflect101(x + j - 9, W)) * 3);
         hbuf[i] = (uint16_t)acc;   // <= 255 * 256
     }
 }
@@ -784,7 +783,7 @@ __global__ __launch_bounds__(256) void grain_add_kernel(const uint8_t* __restric
         for (int j = 0; j < 19; ++j) acc += gk.k[j] * (int)hbuf[(long)reflect101(y + j - 9, H) * W + x];
         int blurred = (acc + (1 << 15)) >> 16;
         blurred = blurred > 255 ? 255 : blurred;
-        int grain = gray_of(orig + i * 3) - blurred;
+        int grain = gray_bgr<3>(orig + i * 3) - blurred;
         grain = grain < 0 ? 0 : grain;
         const int add = (int)(uint8_t)(long)((double)grain * factor);   // float64 product, astype(uint8)
 #pragma unroll
@@ -840,8 +839,7 @@ void launch_grain_addback(const uint8_t* orig, const uint8_t* den, int H, int W,
 __device__ __forceinline__ int pe_gray(const uint8_t* __restrict__ bgr, int H, int W, int y, int x) {
     y = min(max(y, 0), H - 1);   // BORDER_REPLICATE of the Sobel
     x = min(max(x, 0), W - 1);
-    const uint8_t* p = bgr + ((long)y * W + x) * 3;
-    return (p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14;
+    return gray_bgr<3>(bgr + ((long)y * W + x) * 3);
 }
 
 // dx, dy (int16) and the L1 magnitude of every pixel

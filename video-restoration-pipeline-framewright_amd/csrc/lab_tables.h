@@ -2,7 +2,12 @@
 // nlmeans.hip (linear BGR: COLOR_LBGR2Lab / COLOR_Lab2LBGR, contract tests/nlmeans_ref.py) and flicker.hip (sRGB BGR: COLOR_BGR2LAB /
 // COLOR_LAB2BGR, contract tests/flicker_ref.py, which puts a decode table in front of the same matrix and an encode behind the same
 // inverse).  lab_tables() and device_lab() are defined in nlmeans.hip.
+// The per-pixel bodies stay in the two files: they are not the same arithmetic.  nlmeans.hip multiplies the bytes themselves (32-bit
+// sums, index = sum >> 12) and clamps the inverse to 0 .. 255; flicker.hip multiplies decoded 16-bit values (64-bit sums, index =
+// sum >> 20) and keeps the inverse at 16 bits for the sRGB encode.  What they share is the tables and g^-1 below.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <vector>
 
 namespace fw {
@@ -33,5 +38,11 @@ struct DeviceLab {
     int* t256 = nullptr;
 };
 DeviceLab device_lab();
+
+// g^-1 of the Lab inverse, 16 fractional bits in and out: t^3 above the threshold, the linear branch below
+__device__ __forceinline__ long long lab_inv_g(long long t, const LabInv& k) {
+    if (t > k.thr) return (t * t * t + (1ll << (2 * F_BITS - 1))) >> (2 * F_BITS);
+    return ((t - k.c16) * k.kinv + (1ll << (F_BITS - 1))) >> F_BITS;
+}
 
 }  // namespace fw

@@ -11,8 +11,7 @@
 // permutes (s3 = left + own + right, s7 = s3 two to the left + own + s3 two to the right), the vertical one as a running sum over
 // the last `template` rows held in registers, one table look-up, C multiply-adds into uint32 accumulators.  No barrier inside the
 // offset loop; HBM traffic is one read and one write per plane.
-#include "fw_internal.h"
-#include "framewright_hip.h"
+#include "stage_common.h"
 #include "lab_tables.h"
 
 #include <cmath>
@@ -31,14 +30,6 @@ constexpr int NLM_MAX_SH = 20;                     // search window <= 41
 constexpr int NLM_COLS = 64 + 2 * NLM_MAX_SH;      // LDS row stride in dwords: a constant, so row steps are immediate offsets
 constexpr int NLM_MAX_TH = 3;                      // template window 3, 5 or 7
 constexpr size_t NLM_MAX_LDS = 64 * 1024;
-
-// BORDER_REFLECT_101, reflected as often as it takes (sides shorter than the border); n >= 2
-__device__ __forceinline__ int reflect101(int i, int n) {
-    const int p = 2 * (n - 1);
-    int m = i % p;
-    if (m < 0) m += p;
-    return m < n ? m : p - m;
-}
 
 template <int C, int TH>
 __global__ __launch_bounds__(NLM_NT) void nlmeans_kernel(const uint8_t* __restrict__ src, int H, int W, int sh, int shift,
@@ -160,11 +151,6 @@ __global__ __launch_bounds__(256) void bgr_to_lab_kernel(const uint8_t* __restri
     abp[2 * i + 1] = (uint8_t)min(max(bb, 0), 255);
 }
 
-__device__ __forceinline__ long long lab_inv_g(long long t, const LabInv& k) {
-    if (t > k.thr) return (t * t * t + (1ll << (2 * F_BITS - 1))) >> (2 * F_BITS);
-    return ((t - k.c16) * k.kinv + (1ll << (F_BITS - 1))) >> F_BITS;
-}
-
 __global__ __launch_bounds__(256) void lab_to_bgr_kernel(const uint8_t* __restrict__ Lp, const uint8_t* __restrict__ abp, long n, LabInv k,
                                                          const int* __restrict__ t256 /* fy, yl, ax, bz */, uint8_t* __restrict__ bgr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -247,11 +233,6 @@ DeviceTable device_weight_table(double h, int channels, int template_window, int
     d.ptr = upload(t);
     g_tables[key] = d;
     return d;
-}
-
-int nlm_fail(int code, const std::string& m) {
-    last_error_ref() = m;
-    return code;
 }
 
 size_t plane_bytes(size_t n) { return (n + 255) / 256 * 256; }
@@ -433,29 +414,24 @@ int fw_nlmeans_lab_tables(int which, int32_t* out, int capacity) {
 int fw_nlmeans_u8(const uint8_t* src, int channels, int height, int width, double h, int template_window, int search_window, void* scratch,
                   uint8_t* dst, void* stream) {
     (void)scratch;                                             // the whole neighbourhood lives in LDS: the core needs none
-    if (!src || !dst) return nlm_fail(FW_ERR_INVALID, "fw_nlmeans_u8: null pointer");
-    if (src == dst) return nlm_fail(FW_ERR_INVALID, "fw_nlmeans_u8: src and dst must differ (every output reads a 27 x 27 neighbourhood)");
+    if (!src || !dst) return fail(FW_ERR_INVALID, "fw_nlmeans_u8: null pointer");
+    if (src == dst) return fail(FW_ERR_INVALID, "fw_nlmeans_u8: src and dst must differ (every output reads a 27 x 27 neighbourhood)");
     const std::string bad = check_args("fw_nlmeans_u8", channels, height, width, h, template_window, search_window);
-    if (!bad.empty()) return nlm_fail(FW_ERR_INVALID, bad);
-    try {
+    if (!bad.empty()) return fail(FW_ERR_INVALID, bad);
+    return guarded([&] {
         const CorePlan p = plan_core("fw_nlmeans_u8", channels, h, template_window, search_window);
         run_core(p, src, channels, height, width, dst, (hipStream_t)stream);
         FW_HIP_CHECK(hipGetLastError());
-    } catch (const fw::Error& e) {
-        return nlm_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return nlm_fail(FW_ERR_INTERNAL, e.what());
-    }
-    return FW_OK;
+    });
 }
 
 int fw_nlmeans_colored_u8(const uint8_t* src_bgr, int height, int width, double h, double h_color, int template_window, int search_window,
                           void* scratch, uint8_t* dst_bgr, void* stream) {
-    if (!src_bgr || !dst_bgr || !scratch) return nlm_fail(FW_ERR_INVALID, "fw_nlmeans_colored_u8: null pointer");
+    if (!src_bgr || !dst_bgr || !scratch) return fail(FW_ERR_INVALID, "fw_nlmeans_colored_u8: null pointer");
     std::string bad = check_args("fw_nlmeans_colored_u8", 1, height, width, h, template_window, search_window);
     if (bad.empty()) bad = check_args("fw_nlmeans_colored_u8", 2, height, width, h_color, template_window, search_window);
-    if (!bad.empty()) return nlm_fail(FW_ERR_INVALID, bad);
-    try {
+    if (!bad.empty()) return fail(FW_ERR_INVALID, bad);
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const CorePlan pl = plan_core("fw_nlmeans_colored_u8", 1, h, template_window, search_window);
         const CorePlan pc = plan_core("fw_nlmeans_colored_u8", 2, h_color, template_window, search_window);
@@ -473,12 +449,7 @@ int fw_nlmeans_colored_u8(const uint8_t* src_bgr, int height, int width, double 
         run_core(pc, ab, 2, height, width, abd, st);
         hipLaunchKernelGGL(lab_to_bgr_kernel, grid, dim3(256), 0, st, Ld, abd, (long)n, t.inv, lab.t256, dst_bgr);
         FW_HIP_CHECK(hipGetLastError());
-    } catch (const fw::Error& e) {
-        return nlm_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return nlm_fail(FW_ERR_INTERNAL, e.what());
-    }
-    return FW_OK;
+    });
 }
 
 }  // extern "C"

@@ -20,8 +20,7 @@
 
 #include <vector>
 
-#include "framewright_hip.h"
-#include "fw_internal.h"
+#include "stage_common.h"
 
 namespace fw {
 namespace {
@@ -31,18 +30,12 @@ constexpr int MAX_BLUR_R = 9;    // 19 taps: scale 1/8 of the pyramid (sigma 3.5
 constexpr int POLY_N = 5;
 constexpr int MAX_BOX_M = 15;    // winsize <= 31
 
-__device__ __forceinline__ int of_reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - p - 2;
-    return p;
-}
 __device__ __forceinline__ int of_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// cv2.cvtColor(BGR2GRAY) on uint8, 14-bit weights (the form frame_ops.hip uses for the Canny mask)
+// cv2.cvtColor(BGR2GRAY) on uint8 as float32
 __device__ __forceinline__ float of_gray(const uint8_t* __restrict__ img, int channels, int W, int y, int x) {
     if (channels == 1) return (float)img[(size_t)y * W + x];
-    const uint8_t* p = img + ((size_t)y * W + x) * 3;
-    return (float)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14);
+    return (float)gray_bgr<3>(img + ((size_t)y * W + x) * 3);
 }
 
 struct BlurTaps {
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(NT) void of_blur_u8_kernel(const uint8_t* __restric
     const int r = bt.r, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, iw = TW + 2 * r, ih = TH + 2 * r;
     for (int i = threadIdx.x; i < ih * iw; i += NT) {
         const int ly = i / iw, lx = i - ly * iw;
-        s_in[i] = of_gray(img, channels, W, of_reflect101(y0 - r + ly, H), of_reflect101(x0 - r + lx, W));
+        s_in[i] = of_gray(img, channels, W, reflect101(y0 - r + ly, H), reflect101(x0 - r + lx, W));
     }
     __syncthreads();
     for (int i = threadIdx.x; i < ih * TW; i += NT) {
@@ -317,12 +310,12 @@ __global__ __launch_bounds__(NT) void of_flow_stats_kernel(const float* __restri
     const float kf = (float)(1.0 / 25.0);
     for (int i = threadIdx.x; i < DH * DW; i += NT) {
         const int ly = i / DW, lx = i - ly * DW;
-        const int py = of_reflect101(y0 - 2 + ly, H), px = of_reflect101(x0 - 2 + lx, W);
+        const int py = reflect101(y0 - 2 + ly, H), px = reflect101(x0 - 2 + lx, W);
         float ax = 0.0f, ay = 0.0f;
         for (int dy = -2; dy <= 2; ++dy) {
-            const int qy = of_reflect101(py + dy, H) - oy;
+            const int qy = reflect101(py + dy, H) - oy;
             for (int dx = -2; dx <= 2; ++dx) {
-                const int q = qy * IW + of_reflect101(px + dx, W) - ox;
+                const int q = qy * IW + reflect101(px + dx, W) - ox;
                 ax = ax + kf * s_f[0][q];
                 ay = ay + kf * s_f[1][q];
             }
@@ -480,11 +473,6 @@ PolyTaps of_poly_taps(double sigma) {
 constexpr int SCRATCH_PLANES = 27;   // blurred image 1, level images 2, expansions 2 x 5, matrices 2 x 5, coarser flows 2 x 2
 size_t of_plane_bytes(int H, int W) { return (((size_t)H * W * sizeof(float)) + 255) / 256 * 256; }
 
-int of_fail(int code, const std::string& m) {
-    last_error_ref() = m;
-    return code;
-}
-
 }  // namespace
 }  // namespace fw
 
@@ -500,22 +488,22 @@ size_t fw_farneback_scratch_bytes(int height, int width, int levels) {
 int fw_farneback_flow_u8(const uint8_t* prev, const uint8_t* next, int channels, int height, int width, double pyr_scale, int levels,
                          int winsize, int iterations, int poly_n, double poly_sigma, int flags, void* scratch, float* flow_x,
                          float* flow_y, void* stream) {
-    if (!prev || !next || !scratch || !flow_x || !flow_y) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: null pointer");
-    if (channels != 1 && channels != 3) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: channels must be 1 (gray) or 3 (BGR)");
-    if (height < 1 || width < 1 || (long)height * width > (1L << 30)) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: bad frame size");
-    if (poly_n != 5) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: poly_n must be 5 (the only expansion the kernels implement)");
+    if (!prev || !next || !scratch || !flow_x || !flow_y) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: null pointer");
+    if (channels != 1 && channels != 3) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: channels must be 1 (gray) or 3 (BGR)");
+    if (height < 1 || width < 1 || (long)height * width > (1L << 30)) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: bad frame size");
+    if (poly_n != 5) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: poly_n must be 5 (the only expansion the kernels implement)");
     if (flags != 0)
-        return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: flags must be 0 (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not implemented)");
+        return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: flags must be 0 (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not implemented)");
     if (winsize < 3 || winsize > 2 * MAX_BOX_M + 1 || (winsize & 1) == 0)
-        return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: winsize must be odd, 3 .. 31");
-    if (iterations < 1 || levels < 0 || levels > 16) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: iterations >= 1 and 0 <= levels <= 16 expected");
-    if (!(pyr_scale > 0.0) || !(pyr_scale < 1.0)) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: 0 < pyr_scale < 1 expected");
-    if (!(poly_sigma >= 0.0) || poly_sigma > 100.0) return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: bad poly_sigma");
+        return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: winsize must be odd, 3 .. 31");
+    if (iterations < 1 || levels < 0 || levels > 16) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: iterations >= 1 and 0 <= levels <= 16 expected");
+    if (!(pyr_scale > 0.0) || !(pyr_scale < 1.0)) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: 0 < pyr_scale < 1 expected");
+    if (!(poly_sigma >= 0.0) || poly_sigma > 100.0) return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: bad poly_sigma");
     const std::vector<Level> plan = of_plan(height, width, levels, pyr_scale);
     for (const Level& l : plan)
         if (l.ksize / 2 > MAX_BLUR_R || l.h < 1 || l.w < 1)
-            return of_fail(FW_ERR_INVALID, "fw_farneback_flow_u8: pyramid level needs a smoothing kernel of more than 19 taps (scale below 1/8): not implemented");
-    try {
+            return fail(FW_ERR_INVALID, "fw_farneback_flow_u8: pyramid level needs a smoothing kernel of more than 19 taps (scale below 1/8): not implemented");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const size_t pb = of_plane_bytes(height, width);
         char* base = (char*)(((uintptr_t)scratch + 255) / 256 * 256);
@@ -561,34 +549,29 @@ int fw_farneback_flow_u8(const uint8_t* prev, const uint8_t* next, int channels,
             pw = l.w;
         }
         FW_HIP_CHECK(hipGetLastError());
-    } catch (const fw::Error& e) {
-        return of_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return of_fail(FW_ERR_INTERNAL, e.what());
-    }
-    return FW_OK;
+    });
 }
 
 int fw_flow_stats_f32(const float* flow_x, const float* flow_y, int height, int width, float* magnitude, float* variance, void* stream) {
-    if (!flow_x || !flow_y || !variance || height < 1 || width < 1) return of_fail(FW_ERR_INVALID, "fw_flow_stats_f32: bad argument");
+    if (!flow_x || !flow_y || !variance || height < 1 || width < 1) return fail(FW_ERR_INVALID, "fw_flow_stats_f32: bad argument");
     hipLaunchKernelGGL(of_flow_stats_kernel, dim3((width + TW - 1) / TW, (height + TH - 1) / TH), dim3(NT), 0, (hipStream_t)stream, flow_x,
                        flow_y, height, width, magnitude, variance);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return of_fail(FW_ERR_HIP, std::string("fw_flow_stats_f32: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(FW_ERR_HIP, std::string("fw_flow_stats_f32: ") + hipGetErrorString(e));
     return FW_OK;
 }
 
 int fw_flow_confidence_f32(const float* variance, const float* variance_p95, const float* magnitude, const float* motion_threshold,
                            int height, int width, float* confidence, float* weight_map, void* stream) {
     if (!variance || !variance_p95 || height < 1 || width < 1 || (!confidence && !weight_map))
-        return of_fail(FW_ERR_INVALID, "fw_flow_confidence_f32: bad argument");
+        return fail(FW_ERR_INVALID, "fw_flow_confidence_f32: bad argument");
     if (weight_map && (!magnitude || !motion_threshold))
-        return of_fail(FW_ERR_INVALID, "fw_flow_confidence_f32: weight_map needs magnitude and motion_threshold");
+        return fail(FW_ERR_INVALID, "fw_flow_confidence_f32: weight_map needs magnitude and motion_threshold");
     const long n = (long)height * width;
     hipLaunchKernelGGL(of_confidence_kernel, dim3(of_blocks(n)), dim3(NT), 0, (hipStream_t)stream, variance, variance_p95, magnitude,
                        motion_threshold, n, confidence, weight_map);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return of_fail(FW_ERR_HIP, std::string("fw_flow_confidence_f32: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(FW_ERR_HIP, std::string("fw_flow_confidence_f32: ") + hipGetErrorString(e));
     return FW_OK;
 }
 

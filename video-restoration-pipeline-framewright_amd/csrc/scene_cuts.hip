@@ -26,8 +26,7 @@
 //
 // Histograms.  A workgroup takes 8192 pixels of one frame (frame = grid.y), each wave bumps a private 3 x 64 LDS table, and the
 // workgroup ends with at most 192 32-bit integer vector atomics.  Integer atomics commute: the counts are exact.
-#include "framewright_hip.h"
-#include "fw_internal.h"
+#include "stage_common.h"
 
 namespace fw {
 namespace {
@@ -41,22 +40,6 @@ constexpr int HS_NT = 256, HS_WAVES = HS_NT / 64, HS_PIX = 8192;      // pixels 
 
 constexpr double SC_C1 = (0.01 * 255.0) * (0.01 * 255.0), SC_C2 = (0.03 * 255.0) * (0.03 * 255.0);
 constexpr double SC_K1 = SC_C1 * 2401.0, SC_K2 = SC_C2 * 2352.0;
-
-// The aligned word at `p`, of which only the bytes inside [lo, hi) are read: one load when the word lies inside, else its bytes.
-__device__ __forceinline__ uint32_t load_word_inside(const uint8_t* p, const uint8_t* lo, const uint8_t* hi) {
-    if (p >= lo && p + 4 <= hi) return *reinterpret_cast<const uint32_t*>(p);
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (p + k >= lo && p + k < hi) v |= (uint32_t)p[k] << (8 * k);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                         // lane 0 holds the sum
-}
 
 __global__ __launch_bounds__(SC_NT) void scene_ssim_tile_kernel(const uint8_t* __restrict__ frames_a, const uint8_t* __restrict__ frames_b,
                                                                 long stride, int H, int W, double* __restrict__ partial) {
@@ -142,7 +125,7 @@ __global__ __launch_bounds__(SC_NT) void scene_ssim_tile_kernel(const uint8_t* _
             }
         }
     }
-    acc = wave_sum(acc);
+    acc = wave_sum(acc);                                              // only lane 0 of a wave stores its sum
     if (col == 0) s_part[wv] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -158,7 +141,7 @@ __global__ __launch_bounds__(64) void scene_ssim_finish_kernel(const double* __r
     const double* p = partial + (size_t)blockIdx.x * tiles;
     double t = 0.0;
     for (int i = threadIdx.x; i < tiles; i += 64) t += p[i];
-    t = wave_sum(t);
+    t = wave_sum(t);                                                  // only lane 0 stores
     if (threadIdx.x == 0) ssim[blockIdx.x] = t / n;
 }
 
@@ -198,23 +181,6 @@ __global__ __launch_bounds__(HS_NT) void hist64x3_kernel(const uint8_t* __restri
     }
 }
 
-int sc_fail(int code, const std::string& m) {
-    last_error_ref() = m;
-    return code;
-}
-
-template <typename F>
-int sc_guard(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return sc_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return sc_fail(FW_ERR_INTERNAL, e.what());
-    }
-}
-
 // tiles of one pair's map, 0 for a size the kernel does not take
 size_t sc_tiles(int pairs, int H, int W) {
     if (pairs < 1 || pairs > 65535 || H < 7 || W < 7 || (long)H * W > (1L << 30)) return 0;
@@ -235,15 +201,15 @@ size_t fw_scene_ssim_workspace_bytes(int pairs, int height, int width) {
 
 int fw_scene_ssim_u8(const uint8_t* frames_a, const uint8_t* frames_b, int64_t frame_stride_bytes, int pairs, int height, int width,
                      double* ssim, void* workspace, void* stream) {
-    if (!frames_a || !frames_b || !ssim || !workspace) return sc_fail(FW_ERR_INVALID, "fw_scene_ssim_u8: null pointer");
-    if (pairs < 1 || pairs > 65535) return sc_fail(FW_ERR_INVALID, "fw_scene_ssim_u8: 1 .. 65535 pairs per call expected");
+    if (!frames_a || !frames_b || !ssim || !workspace) return fail(FW_ERR_INVALID, "fw_scene_ssim_u8: null pointer");
+    if (pairs < 1 || pairs > 65535) return fail(FW_ERR_INVALID, "fw_scene_ssim_u8: 1 .. 65535 pairs per call expected");
     if (height < 7 || width < 7)
-        return sc_fail(FW_ERR_INVALID, "fw_scene_ssim_u8: the 7 x 7 window exceeds the image (the caller falls back to the histogram test)");
+        return fail(FW_ERR_INVALID, "fw_scene_ssim_u8: the 7 x 7 window exceeds the image (the caller falls back to the histogram test)");
     const size_t tiles = sc_tiles(pairs, height, width);
-    if (tiles == 0) return sc_fail(FW_ERR_INVALID, "fw_scene_ssim_u8: bad frame size");
+    if (tiles == 0) return fail(FW_ERR_INVALID, "fw_scene_ssim_u8: bad frame size");
     if (frame_stride_bytes < 0 || (pairs > 1 && frame_stride_bytes == 0))
-        return sc_fail(FW_ERR_INVALID, "fw_scene_ssim_u8: bad frame stride");
-    return sc_guard([&] {
+        return fail(FW_ERR_INVALID, "fw_scene_ssim_u8: bad frame stride");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const dim3 grid((width - 6 + SC_TW - 1) / SC_TW, (height - 6 + SC_TH - 1) / SC_TH, pairs);
         hipLaunchKernelGGL(scene_ssim_tile_kernel, grid, dim3(SC_NT), 0, st, frames_a, frames_b, (long)frame_stride_bytes, height, width,
@@ -256,10 +222,10 @@ int fw_scene_ssim_u8(const uint8_t* frames_a, const uint8_t* frames_b, int64_t f
 }
 
 int fw_hist64x3_u8(const uint8_t* frames, int count, int height, int width, uint32_t* hist, void* stream) {
-    if (!frames || !hist) return sc_fail(FW_ERR_INVALID, "fw_hist64x3_u8: null pointer");
-    if (count < 1 || count > 65535) return sc_fail(FW_ERR_INVALID, "fw_hist64x3_u8: 1 .. 65535 frames per call expected");
-    if (height < 1 || width < 1 || (long)height * width > (1L << 30)) return sc_fail(FW_ERR_INVALID, "fw_hist64x3_u8: bad frame size");
-    return sc_guard([&] {
+    if (!frames || !hist) return fail(FW_ERR_INVALID, "fw_hist64x3_u8: null pointer");
+    if (count < 1 || count > 65535) return fail(FW_ERR_INVALID, "fw_hist64x3_u8: 1 .. 65535 frames per call expected");
+    if (height < 1 || width < 1 || (long)height * width > (1L << 30)) return fail(FW_ERR_INVALID, "fw_hist64x3_u8: bad frame size");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const long n_pix = (long)height * width;
         FW_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)count * 192 * sizeof(uint32_t), st));

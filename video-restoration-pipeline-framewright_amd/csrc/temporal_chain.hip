@@ -20,8 +20,7 @@
 // most 256 32-bit and 8 64-bit vector atomics.  Integer atomics commute: the result does not depend on scheduling.
 #include <math.h>
 
-#include "framewright_hip.h"
-#include "fw_internal.h"
+#include "stage_common.h"
 #include "flow_accumulate.h"
 
 namespace fw {
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(ST_NT) void frame_stats_kernel(const uint8_t* __res
         uint8_t g = 0;
         if (ry <= H && rx <= W) {
             const uint8_t* p = frame + ((size_t)reflect101(ry, H) * W + reflect101(rx, W)) * 3;
-            g = (uint8_t)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14);
+            g = (uint8_t)gray_bgr<3>(p);
         }
         s_g[i] = g;
     }
@@ -61,11 +60,7 @@ __global__ __launch_bounds__(ST_NT) void frame_stats_kernel(const uint8_t* __res
             atomicAdd(&my_hist[g], 1u);
         }
     }
-    long long t1 = s1, t2 = s2;
-    for (int d = 32; d > 0; d >>= 1) {
-        t1 += __shfl_down(t1, d, 64);
-        t2 += __shfl_down(t2, d, 64);
-    }
+    const long long t1 = wave_sum((long long)s1), t2 = wave_sum((long long)s2);
     if ((tid & 63) == 0 && (t1 != 0 || t2 != 0)) {
         atomicAdd(&lap_sums[(size_t)f * 2], (unsigned long long)t1);       // two's complement: the signed sum
         atomicAdd(&lap_sums[(size_t)f * 2 + 1], (unsigned long long)t2);
@@ -104,23 +99,6 @@ __global__ __launch_bounds__(256) void add_weighted_kernel(const uint8_t* a, flo
     for (size_t i = words * 4 + t0; i < n; i += step) out[i] = (uint8_t)aw_byte(a[i], alpha, b[i], beta);
 }
 
-int tc_fail(int code, const std::string& m) {
-    last_error_ref() = m;
-    return code;
-}
-
-template <typename F>
-int tc_guard(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return tc_fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return tc_fail(FW_ERR_INTERNAL, e.what());
-    }
-}
-
 int tc_blocks(size_t n) {
     const size_t b = (n + 255) / 256;
     return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
@@ -134,11 +112,11 @@ using namespace fw;
 extern "C" {
 
 int fw_frame_stats_u8(const uint8_t* frames_bgr, int count, int height, int width, uint32_t* hist, int64_t* lap_sums, void* stream) {
-    if (!frames_bgr || !hist || !lap_sums) return tc_fail(FW_ERR_INVALID, "fw_frame_stats_u8: null pointer");
-    if (count < 1 || count > 65535) return tc_fail(FW_ERR_INVALID, "fw_frame_stats_u8: 1 .. 65535 frames per call expected");
+    if (!frames_bgr || !hist || !lap_sums) return fail(FW_ERR_INVALID, "fw_frame_stats_u8: null pointer");
+    if (count < 1 || count > 65535) return fail(FW_ERR_INVALID, "fw_frame_stats_u8: 1 .. 65535 frames per call expected");
     if (height < 1 || width < 1 || (long)height * width > (1L << 30) || (height + ST_TH - 1) / ST_TH > 65535)
-        return tc_fail(FW_ERR_INVALID, "fw_frame_stats_u8: bad frame size");
-    return tc_guard([&] {
+        return fail(FW_ERR_INVALID, "fw_frame_stats_u8: bad frame size");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         FW_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)count * 256 * sizeof(uint32_t), st));
         FW_HIP_CHECK(hipMemsetAsync(lap_sums, 0, (size_t)count * 2 * sizeof(int64_t), st));
@@ -153,8 +131,8 @@ int fw_flow_accumulate_affine_u8(const uint8_t* frame_bgr, const float* flow_x, 
                                  double* weight_sum, void* stream) {
     if (!frame_bgr || !accumulated || !weight_sum || height < 1 || width < 1 || (flow_x == nullptr) != (flow_y == nullptr) ||
         (long)height * width > (1L << 30))
-        return tc_fail(FW_ERR_INVALID, "fw_flow_accumulate_affine_u8: bad argument");
-    return tc_guard([&] {
+        return fail(FW_ERR_INVALID, "fw_flow_accumulate_affine_u8: bad argument");
+    return guarded([&] {
         hipLaunchKernelGGL(flow_accumulate_affine_kernel, dim3(tc_blocks((size_t)height * width)), dim3(256), 0, (hipStream_t)stream,
                            frame_bgr, flow_x, flow_y, confidence, w_const, w_conf, inverse, height, width, accumulated, weight_sum);
         FW_HIP_CHECK(hipGetLastError());
@@ -162,9 +140,9 @@ int fw_flow_accumulate_affine_u8(const uint8_t* frame_bgr, const float* flow_x, 
 }
 
 int fw_add_weighted_u8(const uint8_t* a, double alpha, const uint8_t* b, double beta, size_t nbytes, uint8_t* out, void* stream) {
-    if (!a || !b || !out || !std::isfinite(alpha) || !std::isfinite(beta)) return tc_fail(FW_ERR_INVALID, "fw_add_weighted_u8: bad argument");
+    if (!a || !b || !out || !std::isfinite(alpha) || !std::isfinite(beta)) return fail(FW_ERR_INVALID, "fw_add_weighted_u8: bad argument");
     if (nbytes == 0) return FW_OK;
-    return tc_guard([&] {
+    return guarded([&] {
         const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 3) == 0;
         const size_t words = aligned ? nbytes / 4 : 0;
         hipLaunchKernelGGL(add_weighted_kernel, dim3(tc_blocks(aligned ? (nbytes + 3) / 4 : nbytes)), dim3(256), 0, (hipStream_t)stream, a,

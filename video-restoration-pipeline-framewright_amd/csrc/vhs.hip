@@ -29,12 +29,7 @@
 // them, so every kernel checks each table entry against the frame itself and skips what does not lie inside: nothing outside a frame
 // is read or written whatever a table holds.  No scratch; LDS only in the jitter kernel (two gray rows).  Row and box sums are
 // integers reduced across a wave with shuffles and written by one lane: the same in every run.
-#include "framewright_hip.h"
-#include "fw_internal.h"
-
-#include <algorithm>
-#include <utility>
-#include <vector>
+#include "stage_common.h"
 
 #pragma clang fp contract(off)
 
@@ -45,7 +40,7 @@ constexpr int VH_NT = 256;
 constexpr int VH_WAVES = VH_NT / 64;
 constexpr int VH_BATCH = 32;                                          // frames of one launch that writes frames
 constexpr int VH_TABLE = 64;                                          // frames a box table may refer to (a batch and its neighbours)
-constexpr int VH_MAX_SIDE = 16384;
+constexpr int VH_MAX_SIDE = MAX_FRAME_SIDE;
 constexpr int VH_MAX_ENTRIES = 1 << 24;
 constexpr int VH_BLOCKS = 4096;
 constexpr int VH_BOTTOM = 30;
@@ -63,30 +58,6 @@ struct VhPairs {
 struct VhOuts {
     uint8_t* p[VH_BATCH];
 };
-
-template <int C>
-__device__ __forceinline__ int vh_gray(const uint8_t* p) {
-    if constexpr (C == 1) return p[0];
-    else return (p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + (1 << 13)) >> 14;
-}
-
-__device__ __forceinline__ uint32_t vh_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long vh_wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ int vh_wave_max(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
-    return v;
-}
 
 __device__ __forceinline__ uint8_t vh_blend(float fa, float a, float fb, float b) {
     return (uint8_t)(int)__fadd_rn(__fmul_rn(fa, a), __fmul_rn(fb, b));   // in [0, 255.0001]: fa + fb is 1 to an ulp
@@ -113,16 +84,16 @@ __global__ __launch_bounds__(VH_NT) void vh_gray_stats_kernel(const VhFrames fra
         for (int x0 = 0; x0 < W; x0 += 64) {
             const int x = x0 + lane;
             if (x < W) {
-                const int g = vh_gray<C>(row + (long)x * C);
-                if (x + 1 < W) s += (uint32_t)abs(vh_gray<C>(row + (long)(x + 1) * C) - g);
+                const int g = gray_bgr<C>(row + (long)x * C);
+                if (x + 1 < W) s += (uint32_t)abs(gray_bgr<C>(row + (long)(x + 1) * C) - g);
                 if (bottom && y >= H - VH_BOTTOM) bottom[((long)(frame0 + f) * VH_BOTTOM + (y - (H - VH_BOTTOM))) * W + x] = (uint8_t)g;
                 if (runs) {
-                    const int gp = x > 0 ? vh_gray<C>(row + (long)(x - 1) * C) : 128;     // 128: neither bright nor dark
+                    const int gp = x > 0 ? gray_bgr<C>(row + (long)(x - 1) * C) : 128;     // 128: neither bright nor dark
                     const bool bright = g > 250 && !(gp > 250), dark = g < 5 && !(gp < 5);
                     if (bright || dark) {                             // this pixel starts a run: its lane walks to the end
                         int len = 1;
                         while (x + len < W) {
-                            const int gn = vh_gray<C>(row + (long)(x + len) * C);
+                            const int gn = gray_bgr<C>(row + (long)(x + len) * C);
                             if (!(bright ? gn > 250 : gn < 5)) break;
                             ++len;
                         }
@@ -138,7 +109,7 @@ __global__ __launch_bounds__(VH_NT) void vh_gray_stats_kernel(const VhFrames fra
             }
         }
         if (row_sums) {
-            s = vh_wave_sum(s);
+            s = wave_sum(s);
             if (lane == 0) row_sums[(long)(frame0 + f) * H + y] = (long long)s;
         }
     }
@@ -235,10 +206,10 @@ __global__ __launch_bounds__(VH_NT) void vh_box_sums_kernel(const VhFrames frame
             const long np = (long)w * h;
             for (long i = lane; i < np; i += 64) {
                 const long yy = y + i / w, xx = x + i % w;
-                s += (unsigned long long)vh_gray<C>(img + (yy * W + xx) * C);
+                s += (unsigned long long)gray_bgr<C>(img + (yy * W + xx) * C);
             }
         }
-        s = vh_wave_sum64(s);
+        s = wave_sum(s);
         if (lane == 0) sums[e] = ok ? (long long)s : -1LL;
     }
 }
@@ -283,7 +254,7 @@ __global__ __launch_bounds__(VH_NT) void vh_edge_counts_kernel(const VhFrames fr
         const uint8_t* row = img + (long)y * W * 3;
         uint32_t c = 0;
         for (int x = lane; x < W - 1; x += 64) c += vh_edge(row, x) ? 1u : 0u;
-        c = vh_wave_sum(c);
+        c = wave_sum(c);
         if (lane == 0) counts[(long)(frame0 + f) * H + y] = (int)c;
     }
 }
@@ -318,7 +289,7 @@ __global__ __launch_bounds__(VH_NT) void vh_chroma_samples_kernel(const VhFrames
                     kr = (abs((int)p[5] - (int)p[2]) << 8) | (255 - lane);
                     kb = (abs((int)p[3] - (int)p[0]) << 8) | (255 - lane);
                 }
-                kr = vh_wave_max(kr), kb = vh_wave_max(kb);
+                kr = wave_max(kr), kb = wave_max(kb);
                 if (lane == 0) {
                     out[2L * e] = kr >= 0 && (kr >> 8) > 20 ? abs(xs + (255 - (kr & 255)) - found) : -1;
                     out[2L * e + 1] = kb >= 0 && (kb >> 8) > 20 ? abs(xs + (255 - (kb & 255)) - found) : -1;
@@ -363,8 +334,8 @@ __global__ __launch_bounds__(VH_NT) void vh_jitter_kernel(const uint8_t* img, in
     uint8_t* prev = vh_lds + W;
     const int y = 1 + 5 * blockIdx.x;
     for (int x = threadIdx.x; x < W; x += VH_NT) {
-        cur[x] = (uint8_t)vh_gray<C>(img + ((long)y * W + x) * C);
-        prev[x] = (uint8_t)vh_gray<C>(img + ((long)(y - 1) * W + x) * C);
+        cur[x] = (uint8_t)gray_bgr<C>(img + ((long)y * W + x) * C);
+        prev[x] = (uint8_t)gray_bgr<C>(img + ((long)(y - 1) * W + x) * C);
     }
     __syncthreads();
     unsigned long long mine = 0;                                      // (sum << 32) | (2^32 - 1 - j): the largest sum, first position
@@ -394,46 +365,12 @@ __global__ __launch_bounds__(VH_NT) void vh_saturation_kernel(const uint8_t* img
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-int vh_fail(const char* fn, const std::string& m) {
-    last_error_ref() = std::string(fn) + ": " + m;
-    return FW_ERR_INVALID;
-}
-
-int vh_hip(const char* fn, hipError_t e) {
-    if (e == hipSuccess) return FW_OK;
-    (void)hipGetLastError();
-    last_error_ref() = std::string(fn) + ": HIP error: " + hipGetErrorString(e);
-    return FW_ERR_HIP;
-}
-
-int vh_check_size(const char* fn, int H, int W, int C) {
-    if (H < 1 || H > VH_MAX_SIDE || W < 1 || W > VH_MAX_SIDE) return vh_fail(fn, "1 .. 16384 pixels a side expected");
-    if (C != 1 && C != 3) return vh_fail(fn, "1 (gray) or 3 (BGR) channels expected");
-    return FW_OK;
-}
-
-int vh_check_table(const char* fn, const void* const* t, int n, int cap) {
-    if (!t) return vh_fail(fn, "null pointer");
-    if (n < 1 || n > cap) return vh_fail(fn, "1 .. " + std::to_string(cap) + " frames a call expected");
-    for (int i = 0; i < n; ++i)
-        if (!t[i]) return vh_fail(fn, "null pointer");
-    return FW_OK;
-}
-
 // true when a destination (kind 0) of the call overlaps a source (kind 1): all frames are `bytes` long
 bool vh_overlap(const void* const* dst, int nd, const void* const* src, int ns, size_t bytes) {
-    std::vector<std::pair<uintptr_t, int>> marks;
+    FrameMarks marks;
     for (int i = 0; i < nd; ++i) marks.emplace_back((uintptr_t)dst[i], 0);
     for (int i = 0; i < ns; ++i) marks.emplace_back((uintptr_t)src[i], 1);
-    std::sort(marks.begin(), marks.end());
-    uintptr_t last[2] = {0, 0};
-    bool seen[2] = {false, false};
-    for (const auto& m : marks) {
-        const int other = 1 - m.second;
-        if (seen[other] && m.first - last[other] < bytes) return true;
-        last[m.second] = m.first, seen[m.second] = true;
-    }
-    return false;
+    return frames_overlap(marks, bytes);
 }
 
 // destinations must not overlap each other either (two frames of a batch written at once)
@@ -447,10 +384,10 @@ bool vh_self_overlap(const void* const* dst, int n, size_t bytes) {
 }
 
 int vh_fill_pairs(const char* fn, const void* const* src, void* const* dst, int n, size_t bytes, VhPairs& t) {
-    if (const int s = vh_check_table(fn, src, n, VH_BATCH)) return s;
-    if (const int s = vh_check_table(fn, (const void* const*)dst, n, VH_BATCH)) return s;
-    if (vh_overlap((const void* const*)dst, n, src, n, bytes)) return vh_fail(fn, "a dst overlaps a source frame of the call");
-    if (vh_self_overlap((const void* const*)dst, n, bytes)) return vh_fail(fn, "two dst frames of the call overlap");
+    if (const int s = check_pointer_table(fn, src, n, VH_BATCH)) return s;
+    if (const int s = check_pointer_table(fn, (const void* const*)dst, n, VH_BATCH)) return s;
+    if (vh_overlap((const void* const*)dst, n, src, n, bytes)) return invalid(fn, "a dst overlaps a source frame of the call");
+    if (vh_self_overlap((const void* const*)dst, n, bytes)) return invalid(fn, "two dst frames of the call overlap");
     for (int i = 0; i < n; ++i) t.src[i] = (const uint8_t*)src[i], t.dst[i] = (uint8_t*)dst[i], t.shift[i] = 0;
     return FW_OK;
 }
@@ -470,18 +407,15 @@ extern "C" {
 int fw_vhs_gray_stats_u8(const void* const* frames, int n, int height, int width, int channels, int min_length, int64_t* row_sums,
                          uint8_t* bottom, int32_t* runs, int run_capacity, int32_t* run_count, void* stream) {
     const char* fn = "fw_vhs_gray_stats_u8";
-    if (const int s = vh_check_size(fn, height, width, channels)) return s;
-    if (!frames) return vh_fail(fn, "null pointer");
-    if (n < 1 || n > VH_MAX_ENTRIES) return vh_fail(fn, "at least one frame expected");
-    for (int i = 0; i < n; ++i)
-        if (!frames[i]) return vh_fail(fn, "null pointer");
-    if (!row_sums && !bottom && !runs) return vh_fail(fn, "nothing asked for");
-    if (bottom && height < VH_BOTTOM) return vh_fail(fn, "the bottom rows need a frame of at least 30 rows");
+    if (const int s = check_side_and_channels(fn, height, width, channels)) return s;
+    if (const int s = check_pointer_table(fn, frames, n <= VH_MAX_ENTRIES ? n : 0, 0)) return s;   // more than 2^24: refused as none
+    if (!row_sums && !bottom && !runs) return invalid(fn, "nothing asked for");
+    if (bottom && height < VH_BOTTOM) return invalid(fn, "the bottom rows need a frame of at least 30 rows");
     if (runs && (!run_count || run_capacity < 1 || run_capacity > VH_MAX_ENTRIES || min_length < 1))
-        return vh_fail(fn, "a run list needs a counter, a capacity of 1 .. 2^24 and a minimum length of at least 1");
+        return invalid(fn, "a run list needs a counter, a capacity of 1 .. 2^24 and a minimum length of at least 1");
     hipStream_t st = (hipStream_t)stream;
     if (runs)
-        if (const int s = vh_hip(fn, hipMemsetAsync(run_count, 0, sizeof(int32_t), st))) return s;
+        if (const int s = hip_status(fn, hipMemsetAsync(run_count, 0, sizeof(int32_t), st))) return s;
     for (int base = 0; base < n; base += VH_BATCH) {
         const int m = std::min(VH_BATCH, n - base);
         VhFrames t{};
@@ -493,7 +427,7 @@ int fw_vhs_gray_stats_u8(const void* const* frames, int n, int height, int width
         else
             hipLaunchKernelGGL(vh_gray_stats_kernel<1>, grid, dim3(VH_NT), 0, st, t, base, height, width, min_length, (long long*)row_sums, bottom,
                                runs, run_capacity, run_count);
-        if (const int s = vh_hip(fn, hipGetLastError())) return s;
+        if (const int s = hip_status(fn, hipGetLastError())) return s;
     }
     return FW_OK;
 }
@@ -501,20 +435,20 @@ int fw_vhs_gray_stats_u8(const void* const* frames, int n, int height, int width
 int fw_vhs_blend_rows_u8(const void* const* src, void* const* dst, int n, int rows, int64_t row_bytes, const int32_t* spec_rows,
                          const float* spec_factors, int m, void* stream) {
     const char* fn = "fw_vhs_blend_rows_u8";
-    if (rows < 1 || rows > VH_MAX_SIDE || row_bytes < 1 || row_bytes > 4L * VH_MAX_SIDE) return vh_fail(fn, "1 .. 16384 rows of 1 .. 65536 bytes expected");
-    if (!spec_rows || !spec_factors) return vh_fail(fn, "null pointer");
-    if (m < 1 || m > VH_MAX_ENTRIES) return vh_fail(fn, "1 .. 2^24 rows expected");
+    if (rows < 1 || rows > VH_MAX_SIDE || row_bytes < 1 || row_bytes > 4L * VH_MAX_SIDE) return invalid(fn, "1 .. 16384 rows of 1 .. 65536 bytes expected");
+    if (!spec_rows || !spec_factors) return invalid(fn, "null pointer");
+    if (m < 1 || m > VH_MAX_ENTRIES) return invalid(fn, "1 .. 2^24 rows expected");
     VhPairs t{};
     // dst[y] is written while src[y1], src[y2] of other table rows are read: dst may equal nothing of the sources
     if (const int s = vh_fill_pairs(fn, src, dst, n, (size_t)rows * (size_t)row_bytes, t)) return s;
     hipLaunchKernelGGL(vh_blend_rows_kernel, dim3((unsigned)std::min(m, VH_BLOCKS)), dim3(VH_NT), 0, (hipStream_t)stream, t, n, rows, (int)row_bytes,
                        spec_rows, spec_factors, m);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_rainbow_u8(const void* const* src, void* const* dst, int n, int height, int width, float fa, float fb, void* stream) {
     const char* fn = "fw_vhs_rainbow_u8";
-    if (const int s = vh_check_size(fn, height, width, 3)) return s;
+    if (const int s = check_side_and_channels(fn, height, width, 3)) return s;
     VhPairs t{};
     if (const int s = vh_fill_pairs(fn, src, dst, n, (size_t)height * width * 3, t)) return s;
     const long total = (long)height * width * 3;                      // <= 3 * 2^28
@@ -527,36 +461,36 @@ int fw_vhs_rainbow_u8(const void* const* src, void* const* dst, int n, int heigh
         const dim3 grid(vh_grid((total + VH_NT - 1) / VH_NT, n), (unsigned)n);
         hipLaunchKernelGGL(vh_rainbow_kernel, grid, dim3(VH_NT), 0, (hipStream_t)stream, t, height, width, fa, fb);
     }
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_box_gray_sums_u8(const void* const* frames, int n, int height, int width, int channels, const int32_t* tasks, int m, int64_t* sums,
                             void* stream) {
     const char* fn = "fw_vhs_box_gray_sums_u8";
-    if (const int s = vh_check_size(fn, height, width, channels)) return s;
-    if (const int s = vh_check_table(fn, frames, n, VH_TABLE)) return s;
-    if (!tasks || !sums) return vh_fail(fn, "null pointer");
-    if (m < 1 || m > VH_MAX_ENTRIES) return vh_fail(fn, "1 .. 2^24 boxes expected");
+    if (const int s = check_side_and_channels(fn, height, width, channels)) return s;
+    if (const int s = check_pointer_table(fn, frames, n, VH_TABLE)) return s;
+    if (!tasks || !sums) return invalid(fn, "null pointer");
+    if (m < 1 || m > VH_MAX_ENTRIES) return invalid(fn, "1 .. 2^24 boxes expected");
     VhFrames t{};
     for (int i = 0; i < n; ++i) t.p[i] = (const uint8_t*)frames[i];
     const dim3 grid((unsigned)std::min((m + VH_WAVES - 1) / VH_WAVES, VH_BLOCKS));
     if (channels == 3) hipLaunchKernelGGL(vh_box_sums_kernel<3>, grid, dim3(VH_NT), 0, (hipStream_t)stream, t, n, height, width, tasks, m, (long long*)sums);
     else hipLaunchKernelGGL(vh_box_sums_kernel<1>, grid, dim3(VH_NT), 0, (hipStream_t)stream, t, n, height, width, tasks, m, (long long*)sums);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_dropout_repair_u8(const void* const* sources, int n_sources, void* const* results, int n_results, int height, int width, int channels,
                              const int32_t* boxes, int m, double strength, void* stream) {
     const char* fn = "fw_vhs_dropout_repair_u8";
-    if (const int s = vh_check_size(fn, height, width, channels)) return s;
-    if (const int s = vh_check_table(fn, sources, n_sources, VH_TABLE)) return s;
-    if (const int s = vh_check_table(fn, (const void* const*)results, n_results, VH_BATCH)) return s;
-    if (!boxes) return vh_fail(fn, "null pointer");
-    if (m < 1 || m > VH_MAX_ENTRIES) return vh_fail(fn, "1 .. 2^24 boxes expected");
-    if (!(strength > 0.0 && strength <= 1.0)) return vh_fail(fn, "a strength in (0, 1] expected");
+    if (const int s = check_side_and_channels(fn, height, width, channels)) return s;
+    if (const int s = check_pointer_table(fn, sources, n_sources, VH_TABLE)) return s;
+    if (const int s = check_pointer_table(fn, (const void* const*)results, n_results, VH_BATCH)) return s;
+    if (!boxes) return invalid(fn, "null pointer");
+    if (m < 1 || m > VH_MAX_ENTRIES) return invalid(fn, "1 .. 2^24 boxes expected");
+    if (!(strength > 0.0 && strength <= 1.0)) return invalid(fn, "a strength in (0, 1] expected");
     const size_t bytes = (size_t)height * width * channels;
-    if (vh_overlap((const void* const*)results, n_results, sources, n_sources, bytes)) return vh_fail(fn, "a result frame overlaps a source frame of the call");
-    if (vh_self_overlap((const void* const*)results, n_results, bytes)) return vh_fail(fn, "two result frames of the call overlap");
+    if (vh_overlap((const void* const*)results, n_results, sources, n_sources, bytes)) return invalid(fn, "a result frame overlaps a source frame of the call");
+    if (vh_self_overlap((const void* const*)results, n_results, bytes)) return invalid(fn, "two result frames of the call overlap");
     VhFrames s{};
     VhOuts r{};
     for (int i = 0; i < n_sources; ++i) s.p[i] = (const uint8_t*)sources[i];
@@ -567,85 +501,83 @@ int fw_vhs_dropout_repair_u8(const void* const* sources, int n_sources, void* co
         hipLaunchKernelGGL(vh_repair_kernel<3>, grid, dim3(VH_NT), 0, (hipStream_t)stream, s, n_sources, r, n_results, height, width, boxes, m, fa, fb, strength);
     else
         hipLaunchKernelGGL(vh_repair_kernel<1>, grid, dim3(VH_NT), 0, (hipStream_t)stream, s, n_sources, r, n_results, height, width, boxes, m, fa, fb, strength);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_edge_counts_u8(const void* const* frames, int n, int height, int width, int32_t* counts, void* stream) {
     const char* fn = "fw_vhs_edge_counts_u8";
-    if (const int s = vh_check_size(fn, height, width, 3)) return s;
-    if (!frames || !counts) return vh_fail(fn, "null pointer");
-    if (n < 1 || n > VH_MAX_ENTRIES) return vh_fail(fn, "at least one frame expected");
-    for (int i = 0; i < n; ++i)
-        if (!frames[i]) return vh_fail(fn, "null pointer");
+    if (const int s = check_side_and_channels(fn, height, width, 3)) return s;
+    if (!counts) return invalid(fn, "null pointer");
+    if (const int s = check_pointer_table(fn, frames, n <= VH_MAX_ENTRIES ? n : 0, 0)) return s;
     for (int base = 0; base < n; base += VH_BATCH) {
         const int m = std::min(VH_BATCH, n - base);
         VhFrames t{};
         for (int i = 0; i < m; ++i) t.p[i] = (const uint8_t*)frames[base + i];
         const dim3 grid(vh_grid((height + VH_WAVES - 1) / VH_WAVES, m), (unsigned)m);
         hipLaunchKernelGGL(vh_edge_counts_kernel, grid, dim3(VH_NT), 0, (hipStream_t)stream, t, base, height, width, counts);
-        if (const int s = vh_hip(fn, hipGetLastError())) return s;
+        if (const int s = hip_status(fn, hipGetLastError())) return s;
     }
     return FW_OK;
 }
 
 int fw_vhs_chroma_samples_u8(const void* const* frames, int n, int height, int width, const int32_t* samples, int m, int32_t* offsets, void* stream) {
     const char* fn = "fw_vhs_chroma_samples_u8";
-    if (const int s = vh_check_size(fn, height, width, 3)) return s;
-    if (const int s = vh_check_table(fn, frames, n, VH_TABLE)) return s;
-    if (!samples || !offsets) return vh_fail(fn, "null pointer");
-    if (m < 1 || m > 100 * VH_TABLE) return vh_fail(fn, "1 .. 6400 samples expected (at most 100 a frame)");
+    if (const int s = check_side_and_channels(fn, height, width, 3)) return s;
+    if (const int s = check_pointer_table(fn, frames, n, VH_TABLE)) return s;
+    if (!samples || !offsets) return invalid(fn, "null pointer");
+    if (m < 1 || m > 100 * VH_TABLE) return invalid(fn, "1 .. 6400 samples expected (at most 100 a frame)");
     VhFrames t{};
     for (int i = 0; i < n; ++i) t.p[i] = (const uint8_t*)frames[i];
     const dim3 grid((unsigned)std::min((m + VH_WAVES - 1) / VH_WAVES, VH_BLOCKS));
     hipLaunchKernelGGL(vh_chroma_samples_kernel, grid, dim3(VH_NT), 0, (hipStream_t)stream, t, n, height, width, samples, m, offsets);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_chroma_shift_u8(const void* const* src, void* const* dst, const int32_t* shifts, int n, int height, int width, void* stream) {
     const char* fn = "fw_vhs_chroma_shift_u8";
-    if (const int s = vh_check_size(fn, height, width, 3)) return s;
-    if (!shifts) return vh_fail(fn, "null pointer");
+    if (const int s = check_side_and_channels(fn, height, width, 3)) return s;
+    if (!shifts) return invalid(fn, "null pointer");
     VhPairs t{};
     if (const int s = vh_fill_pairs(fn, src, dst, n, (size_t)height * width * 3, t)) return s;
     for (int i = 0; i < n; ++i) {
-        if (shifts[i] < 0 || shifts[i] > 2) return vh_fail(fn, "a shift of 0 .. 2 columns expected");
+        if (shifts[i] < 0 || shifts[i] > 2) return invalid(fn, "a shift of 0 .. 2 columns expected");
         t.shift[i] = shifts[i];
     }
     const long npix = (long)height * width;
     const dim3 grid(vh_grid((npix + VH_NT - 1) / VH_NT, n), (unsigned)n);
     hipLaunchKernelGGL(vh_chroma_shift_kernel, grid, dim3(VH_NT), 0, (hipStream_t)stream, t, height, width);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_column_sums_u8(const uint8_t* frame, int height, int width, int64_t* sums, void* stream) {
     const char* fn = "fw_vhs_column_sums_u8";
-    if (const int s = vh_check_size(fn, height, width, 3)) return s;
-    if (!frame || !sums) return vh_fail(fn, "null pointer");
-    if (width < 2) return vh_fail(fn, "at least two columns expected");
+    if (const int s = check_side_and_channels(fn, height, width, 3)) return s;
+    if (!frame || !sums) return invalid(fn, "null pointer");
+    if (width < 2) return invalid(fn, "at least two columns expected");
     hipLaunchKernelGGL(vh_column_sums_kernel, dim3((unsigned)((width - 1 + VH_NT - 1) / VH_NT)), dim3(VH_NT), 0, (hipStream_t)stream, frame, height, width,
                        (long long*)sums);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_jitter_shifts_u8(const uint8_t* frame, int height, int width, int channels, int32_t* shifts, void* stream) {
     const char* fn = "fw_vhs_jitter_shifts_u8";
-    if (const int s = vh_check_size(fn, height, width, channels)) return s;
-    if (!frame || !shifts) return vh_fail(fn, "null pointer");
-    if (height < 3) return vh_fail(fn, "at least three rows expected");
+    if (const int s = check_side_and_channels(fn, height, width, channels)) return s;
+    if (!frame || !shifts) return invalid(fn, "null pointer");
+    if (height < 3) return invalid(fn, "at least three rows expected");
     const int rows = (height - 2 + 4) / 5;                            // y = 1, 6, 11 ... <= height - 2
     const size_t lds = 2 * (size_t)width;                             // <= 32 KiB
     if (channels == 3) hipLaunchKernelGGL(vh_jitter_kernel<3>, dim3((unsigned)rows), dim3(VH_NT), lds, (hipStream_t)stream, frame, height, width, shifts);
     else hipLaunchKernelGGL(vh_jitter_kernel<1>, dim3((unsigned)rows), dim3(VH_NT), lds, (hipStream_t)stream, frame, height, width, shifts);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 int fw_vhs_saturation_f64(const uint8_t* frame, int height, int width, double* saturation, void* stream) {
     const char* fn = "fw_vhs_saturation_f64";
-    if (const int s = vh_check_size(fn, height, width, 3)) return s;
-    if (!frame || !saturation) return vh_fail(fn, "null pointer");
+    if (const int s = check_side_and_channels(fn, height, width, 3)) return s;
+    if (!frame || !saturation) return invalid(fn, "null pointer");
     const long npix = (long)height * width;
     hipLaunchKernelGGL(vh_saturation_kernel, dim3(vh_grid((npix + VH_NT - 1) / VH_NT, 1)), dim3(VH_NT), 0, (hipStream_t)stream, frame, npix, saturation);
-    return vh_hip(fn, hipGetLastError());
+    return hip_status(fn, hipGetLastError());
 }
 
 }  // extern "C"

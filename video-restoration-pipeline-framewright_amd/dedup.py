@@ -140,9 +140,8 @@ class DeviceFrameDeduplicator:
         _lib.require_gpu()
         thumbs = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev)
         ws = torch.empty(max(1, self._lib.fw_pil_thumb_workspace_bytes(n, h, w, out_w, out_h, int(gray_first))), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        _lib.check(self._lib.fw_pil_thumb_u8(C.c_void_p(ptr), stride, n, h, w, out_w, out_h, int(gray_first), C.c_void_p(thumbs.data_ptr()),
-                                             C.c_void_p(ws.data_ptr()), C.c_void_p(stream.cuda_stream)))
+        _lib.check(self._lib.fw_pil_thumb_u8(C.c_void_p(ptr), stride, n, h, w, out_w, out_h, int(gray_first), _lib.ptr(thumbs),
+                                             _lib.ptr(ws), _lib.stream_ptr(dev)))
         return thumbs
 
     def _hashes_of_clip(self, clip) -> List[str]:
@@ -154,8 +153,7 @@ class DeviceFrameDeduplicator:
             hs = int(self.config.hash_size)
             thumbs = self._thumbs(clip.data_ptr(), h * w * 3, n, h, w, hs + 1, hs, True, dev)
             bits = torch.empty((n, (hs * hs + 7) // 8), dtype=torch.uint8, device=dev)
-            _lib.check(self._lib.fw_dhash_pack_u8(C.c_void_p(thumbs.data_ptr()), n, hs, C.c_void_p(bits.data_ptr()),
-                                                  C.c_void_p(stream.cuda_stream)))
+            _lib.check(self._lib.fw_dhash_pack_u8(_lib.ptr(thumbs), n, hs, _lib.ptr(bits), C.c_void_p(stream.cuda_stream)))
             stream.synchronize()
             return [_bits_to_hex(row.tobytes(), hs) for row in bits.cpu().numpy()]
         thumbs = self._thumbs(clip.data_ptr(), h * w * 3, n, h, w, PIXEL_THUMB, PIXEL_THUMB, False, dev)

@@ -9,7 +9,6 @@ Not built: `process_video` (ffmpeg) and `processors/interlace_handler.py` (ffmpe
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging
 from dataclasses import dataclass, field
 from enum import Enum
@@ -151,10 +150,6 @@ class DeviceDeinterlacer:
         if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.device != dev or out.numel() != numel or not out.is_contiguous():
             raise ValueError(f"a contiguous int64 tensor of {numel} elements on {dev} expected")
 
-    def _stream(self, dev):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
     @_lib.on_tensor_device
     def interpolate_device(self, frames: Sequence, mode: int, parity: int, prev=None, nxt=None, batched: bool = True,
                            outs: Optional[Sequence] = None) -> List:
@@ -184,17 +179,14 @@ class DeviceDeinterlacer:
         prevs = [frames[i - 1] if i > 0 else (prev if prev is not None else frames[i]) for i in range(n)]
         nexts = [frames[i + 1] if i < n - 1 else (nxt if nxt is not None else frames[i]) for i in range(n)]
         _check_no_overlap(outs, frames + [t for t in (prev, nxt) if t is not None])
-        st = self._stream(frames[0].device)
+        st = _lib.stream_ptr(frames[0].device)
         if batched:
-            table = (C.c_void_p * (4 * n))()
-            for i in range(n):
-                table[4 * i], table[4 * i + 1] = frames[i].data_ptr(), prevs[i].data_ptr()
-                table[4 * i + 2], table[4 * i + 3] = nexts[i].data_ptr(), outs[i].data_ptr()
+            table = _lib.ptr_table([t for task in zip(frames, prevs, nexts, outs) for t in task])   # n x {cur, prev, next, dst}
             _lib.check(self._lib.fw_deinterlace_batch_u8(table, n, h, w * c, mode, parity, st))
         else:
             for i in range(n):
-                _lib.check(self._lib.fw_deinterlace_u8(C.c_void_p(frames[i].data_ptr()), C.c_void_p(prevs[i].data_ptr()),
-                                                       C.c_void_p(nexts[i].data_ptr()), C.c_void_p(outs[i].data_ptr()), h, w * c, mode,
+                _lib.check(self._lib.fw_deinterlace_u8(_lib.ptr(frames[i]), _lib.ptr(prevs[i]),
+                                                       _lib.ptr(nexts[i]), _lib.ptr(outs[i]), h, w * c, mode,
                                                        parity, st))
         return outs
 
@@ -209,8 +201,7 @@ class DeviceDeinterlacer:
         if out is None:
             out = torch.empty((len(frames), 4), dtype=torch.int64, device=frames[0].device)
         self._check_out(out, 4 * len(frames), frames[0].device)
-        table = (C.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
-        _lib.check(self._lib.fw_interlace_stats_u8(table, len(frames), h, w, c, C.c_void_p(out.data_ptr()), self._stream(frames[0].device)))
+        _lib.check(self._lib.fw_interlace_stats_u8(_lib.ptr_table(frames), len(frames), h, w, c, _lib.ptr(out), _lib.stream_ptr(frames[0].device)))
         return out
 
     @_lib.on_tensor_device
@@ -226,9 +217,7 @@ class DeviceDeinterlacer:
         if out is None:
             out = torch.empty((len(a),), dtype=torch.int64, device=a[0].device)
         self._check_out(out, len(a), a[0].device)
-        ta = (C.c_void_p * len(a))(*[f.data_ptr() for f in a])
-        tb = (C.c_void_p * len(b))(*[f.data_ptr() for f in b])
-        _lib.check(self._lib.fw_frame_absdiff_sum_u8(ta, tb, len(a), h, w, c, C.c_void_p(out.data_ptr()), self._stream(a[0].device)))
+        _lib.check(self._lib.fw_frame_absdiff_sum_u8(_lib.ptr_table(a), _lib.ptr_table(b), len(a), h, w, c, _lib.ptr(out), _lib.stream_ptr(a[0].device)))
         return out
 
     def _frame_differences(self, frames: Sequence, pairs: Sequence[tuple]) -> List[float]:

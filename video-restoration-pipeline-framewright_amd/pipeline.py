@@ -56,20 +56,7 @@ class DeviceRestorationPipeline:
         """frames: uint8 BGR H x W x 3, numpy arrays or CUDA tensors.  Returns uint8 CUDA tensors (still on the device; the
         work is queued on torch's current stream)."""
         import torch
-        dev = None
-        for e in (self.upscaler, self.interpolator):
-            if e is not None:
-                dev = torch.device("cuda", e.device_id)
-        if dev is None and self.denoiser is not None:
-            dev = torch.device("cuda", self.denoiser.config.gpu_id)
-        if dev is None and self.color_grader is not None:
-            dev = torch.device("cuda", self.color_grader.device_id)
-        if dev is None and self.deinterlacer is not None:
-            dev = torch.device("cuda", self.deinterlacer.device_id)
-        if dev is None and self.vhs_processor is not None:
-            dev = torch.device("cuda", self.vhs_processor.device_id)
-        if dev is None:
-            raise ValueError("DeviceRestorationPipeline: no stage configured")
+        dev = self._device()
 
         def up(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a.contiguous()
@@ -107,8 +94,11 @@ class DeviceRestorationPipeline:
 
     # ---- streaming form: the codec edge (codec.py) ---------------------------------------------------------------------------
     def _device(self):
+        """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
+        (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
+        the first of denoiser, colour grader, deinterlacer, VHS processor.  A new stage adds its branch here only."""
         import torch
-        for e in (self.upscaler, self.interpolator):
+        for e in (self.interpolator, self.upscaler):
             if e is not None:
                 return torch.device("cuda", e.device_id)
         if self.denoiser is not None:

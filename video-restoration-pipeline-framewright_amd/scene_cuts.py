@@ -41,8 +41,7 @@ class DeviceSceneCutDetector:
         out = torch.empty(pairs, dtype=torch.float64, device=dev)
         ws = torch.empty(max(1, self._lib.fw_scene_ssim_workspace_bytes(pairs, h, w) // 8), dtype=torch.float64, device=dev)
         stream = torch.cuda.current_stream(dev)
-        _lib.check(self._lib.fw_scene_ssim_u8(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), stride, pairs, h, w,
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_void_p(stream.cuda_stream)))
+        _lib.check(self._lib.fw_scene_ssim_u8(_lib.ptr(a), _lib.ptr(b), stride, pairs, h, w, _lib.ptr(out), _lib.ptr(ws), C.c_void_p(stream.cuda_stream)))
         stream.synchronize()
         return out.cpu().tolist()
 
@@ -74,8 +73,7 @@ class DeviceSceneCutDetector:
         dev = frames.device
         hist = torch.empty((n, 3, 64), dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev)
-        _lib.check(self._lib.fw_hist64x3_u8(C.c_void_p(frames.data_ptr()), n, h, w, C.c_void_p(hist.data_ptr()),
-                                            C.c_void_p(stream.cuda_stream)))
+        _lib.check(self._lib.fw_hist64x3_u8(_lib.ptr(frames), n, h, w, _lib.ptr(hist), C.c_void_p(stream.cuda_stream)))
         stream.synchronize()
         return hist.cpu().numpy().view(np.uint32).astype(np.int64)
 

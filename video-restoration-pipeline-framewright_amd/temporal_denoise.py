@@ -174,11 +174,11 @@ class DeviceFlowEstimator:
         scratch = self._scratch_for(h, w, dev)
         fx = torch.empty((h, w), dtype=torch.float32, device=dev)
         fy = torch.empty((h, w), dtype=torch.float32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.fw_farneback_flow_u8(C.c_void_p(t1.data_ptr()), C.c_void_p(t2.data_ptr()), 1 if t1.dim() == 2 else 3, h, w,
+        st = _lib.stream_ptr(dev)
+        _lib.check(self._lib.fw_farneback_flow_u8(_lib.ptr(t1), _lib.ptr(t2), 1 if t1.dim() == 2 else 3, h, w,
                                                   float(p["pyr_scale"]), int(p["levels"]), int(p["winsize"]), int(p["iterations"]),
                                                   int(p["poly_n"]), float(p["poly_sigma"]), int(p["flags"]),
-                                                  C.c_void_p(scratch.data_ptr()), C.c_void_p(fx.data_ptr()), C.c_void_p(fy.data_ptr()), st))
+                                                  _lib.ptr(scratch), _lib.ptr(fx), _lib.ptr(fy), st))
         return fx, fy
 
     @_lib.on_tensor_device
@@ -192,8 +192,8 @@ class DeviceFlowEstimator:
         h, w = int(fx.shape[0]), int(fx.shape[1])
         mag, var, conf = torch.empty_like(fx), torch.empty_like(fx), torch.empty_like(fx)
         wm = torch.empty_like(fx) if weight_map else None
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        st = _lib.stream_ptr(dev)
+        p = lambda t: _lib.ptr(t) if t is not None else None
         _lib.check(self._lib.fw_flow_stats_f32(p(fx), p(fy), h, w, p(mag), p(var), st))
         # the two order statistics are plumbing: a device sort each (torch.quantile refuses inputs of this size), index arithmetic on the host
         p95 = _percentile_sorted(torch.sort(var.reshape(-1)).values, 95)
@@ -265,10 +265,10 @@ class DeviceSpatialDenoiser:
         hh, ww = int(t.shape[0]), int(t.shape[1])
         scratch = self._scratch_for(hh, ww, dev)
         out = torch.empty_like(t)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.fw_nlmeans_colored_u8(C.c_void_p(t.data_ptr()), hh, ww, float(h), float(h if h_color is None else h_color),
-                                                   self.template_window, self.search_window, C.c_void_p(scratch.data_ptr()),
-                                                   C.c_void_p(out.data_ptr()), st))
+        st = _lib.stream_ptr(dev)
+        _lib.check(self._lib.fw_nlmeans_colored_u8(_lib.ptr(t), hh, ww, float(h), float(h if h_color is None else h_color),
+                                                   self.template_window, self.search_window, _lib.ptr(scratch),
+                                                   _lib.ptr(out), st))
         return out
 
     @_lib.on_tensor_device
@@ -281,10 +281,10 @@ class DeviceSpatialDenoiser:
         plane = plane.contiguous()
         dev = plane.device
         out = torch.empty_like(plane)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.fw_nlmeans_u8(C.c_void_p(plane.data_ptr()), 1 if plane.dim() == 2 else int(plane.shape[2]), int(plane.shape[0]),
+        st = _lib.stream_ptr(dev)
+        _lib.check(self._lib.fw_nlmeans_u8(_lib.ptr(plane), 1 if plane.dim() == 2 else int(plane.shape[2]), int(plane.shape[0]),
                                            int(plane.shape[1]), float(h), self.template_window, self.search_window, None,
-                                           C.c_void_p(out.data_ptr()), st))
+                                           _lib.ptr(out), st))
         return out
 
     def denoise(self, frame: np.ndarray, strength: float) -> np.ndarray:
@@ -338,10 +338,10 @@ class DeviceTemporalAccumulator:
         import torch
         dev = acc.device
         h, w = int(acc.shape[0]), int(acc.shape[1])
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.stream_ptr(dev)
         f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
         keep = []
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        p = lambda t: _lib.ptr(t) if t is not None else None
         fx = fy = mg = wm = None
         if flow is not None:
             fx, fy = f32(flow.flow_x), f32(flow.flow_y)
@@ -361,9 +361,9 @@ class DeviceTemporalAccumulator:
         import torch
         h, w = int(acc.shape[0]), int(acc.shape[1])
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=acc.device)
-        st = C.c_void_p(torch.cuda.current_stream(acc.device).cuda_stream)
-        _lib.check(self._lib.fw_flow_accumulate_finish_u8(C.c_void_p(acc.data_ptr()), C.c_void_p(ws.data_ptr()), h, w,
-                                                          C.c_void_p(out.data_ptr()), st))
+        st = _lib.stream_ptr(acc.device)
+        _lib.check(self._lib.fw_flow_accumulate_finish_u8(_lib.ptr(acc), _lib.ptr(ws), h, w,
+                                                          _lib.ptr(out), st))
         torch.cuda.synchronize(acc.device)
         return out.cpu().numpy()
 
@@ -405,8 +405,8 @@ class DeviceTemporalAccumulator:
         h, w = int(center.shape[0]), int(center.shape[1])
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        st = _lib.stream_ptr(dev)
+        p = lambda t: _lib.ptr(t) if t is not None else None
         for local_i, fd in enumerate(frames_dev):
             distance = abs(local_i - center_local_idx)
             fx = fy = wm = None
@@ -497,10 +497,10 @@ class DeviceTemporalAccumulator:
             h, w = int(out.shape[0]), int(out.shape[1])
             scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
             blended = torch.empty_like(out)
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(self._lib.fw_preserve_edges_u8(C.c_void_p(center.data_ptr()), C.c_void_p(out.data_ptr()), h, w,
+            st = _lib.stream_ptr(dev)
+            _lib.check(self._lib.fw_preserve_edges_u8(_lib.ptr(center), _lib.ptr(out), h, w,
                                                       float(edge_threshold), float(edge_threshold * 3),
-                                                      C.c_void_p(scratch.data_ptr()), C.c_void_p(blended.data_ptr()), st))
+                                                      _lib.ptr(scratch), _lib.ptr(blended), st))
             out = blended
         return out
 
@@ -513,14 +513,14 @@ class DeviceTemporalAccumulator:
         h, w = int(frames_dev[0].shape[0]), int(frames_dev[0].shape[1])
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.stream_ptr(dev)
         center_idx = len(frames_dev) // 2
         for i, fd in enumerate(frames_dev):
-            _lib.check(self._lib.fw_flow_accumulate_u8(C.c_void_p(fd.data_ptr()), None, None, None, math.exp(-abs(i - center_idx) * self.decay),
-                                                       None, 0.0, 0, h, w, C.c_void_p(acc.data_ptr()), C.c_void_p(ws.data_ptr()), st))
+            _lib.check(self._lib.fw_flow_accumulate_u8(_lib.ptr(fd), None, None, None, math.exp(-abs(i - center_idx) * self.decay),
+                                                       None, 0.0, 0, h, w, _lib.ptr(acc), _lib.ptr(ws), st))
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
-        _lib.check(self._lib.fw_flow_accumulate_finish_u8(C.c_void_p(acc.data_ptr()), C.c_void_p(ws.data_ptr()), h, w,
-                                                          C.c_void_p(out.data_ptr()), st))
+        _lib.check(self._lib.fw_flow_accumulate_finish_u8(_lib.ptr(acc), _lib.ptr(ws), h, w,
+                                                          _lib.ptr(out), st))
         return out
 
     def preserve_edges(self, original: np.ndarray, denoised: np.ndarray, edge_threshold: int = 30) -> np.ndarray:
@@ -538,10 +538,10 @@ class DeviceTemporalAccumulator:
             d = torch.from_numpy(np.ascontiguousarray(denoised)).to(dev)
             scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
             out = torch.empty_like(o)
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(self._lib.fw_preserve_edges_u8(C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), h, w, float(edge_threshold),
-                                                      float(edge_threshold * 3), C.c_void_p(scratch.data_ptr()),
-                                                      C.c_void_p(out.data_ptr()), st))
+            st = _lib.stream_ptr(dev)
+            _lib.check(self._lib.fw_preserve_edges_u8(_lib.ptr(o), _lib.ptr(d), h, w, float(edge_threshold),
+                                                      float(edge_threshold * 3), _lib.ptr(scratch),
+                                                      _lib.ptr(out), st))
             torch.cuda.synchronize(dev)
         return out.cpu().numpy()
 
@@ -779,8 +779,8 @@ class DeviceClipAnalyzer:
         dev = clip_u8.device
         count, h, w = (int(v) for v in clip_u8.shape[:3])
         buf = torch.empty(count * 130, dtype=torch.int64, device=dev)       # count x 256 uint32, then count x 2 int64
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.fw_frame_stats_u8(C.c_void_p(clip_u8.data_ptr()), count, h, w, C.c_void_p(buf.data_ptr()),
+        st = _lib.stream_ptr(dev)
+        _lib.check(self._lib.fw_frame_stats_u8(_lib.ptr(clip_u8), count, h, w, _lib.ptr(buf),
                                                C.c_void_p(buf.data_ptr() + count * 1024), st))
         torch.cuda.current_stream(dev).synchronize()
         host = buf.cpu().numpy()
@@ -915,12 +915,12 @@ class DeviceFlickerReducer:
         elif out.shape != batch.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
             raise ValueError("flicker reduction: `out` must be a contiguous uint8 device tensor of the batch's shape")
         sums = torch.empty(count, dtype=torch.int64, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._lib.fw_lab_l_sums_u8(C.c_void_p(batch.data_ptr()), count, h, w, C.c_void_p(sums.data_ptr()), st))
+        st = _lib.stream_ptr(dev)
+        _lib.check(self._lib.fw_lab_l_sums_u8(_lib.ptr(batch), count, h, w, _lib.ptr(sums), st))
         torch.cuda.current_stream(dev).synchronize()
         luts = torch.from_numpy(self.l_luts(sums.cpu().numpy().tolist(), h * w, target)).to(dev)
-        _lib.check(self._lib.fw_deflicker_lab_u8(C.c_void_p(batch.data_ptr()), count, h, w, C.c_void_p(luts.data_ptr()),
-                                                 C.c_void_p(out.data_ptr()), st))
+        _lib.check(self._lib.fw_deflicker_lab_u8(_lib.ptr(batch), count, h, w, _lib.ptr(luts),
+                                                 _lib.ptr(out), st))
         # `luts` is freed when this returns; the caching allocator hands the block out again on this stream only, behind the launch
         return out
 
@@ -1003,8 +1003,8 @@ class DeviceTemporalConsistencyFilter:
         h, w = int(center.shape[0]), int(center.shape[1])
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        st = _lib.stream_ptr(dev)
+        p = lambda t: _lib.ptr(t) if t is not None else None
         guided = self.use_optical_flow and hi - lo > 1
         for j in range(lo, hi):
             tw = float(np.exp(-abs(j - i) * 0.5))

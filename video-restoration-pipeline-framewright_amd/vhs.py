@@ -271,14 +271,6 @@ class DeviceVHSProcessor:
     def _contiguous(frames: Sequence) -> List:
         return [f if f.is_contiguous() else f.contiguous() for f in frames]
 
-    def _stream(self, dev):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-    @staticmethod
-    def _table(tensors: Sequence):
-        return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
     @staticmethod
     def _upload(a: np.ndarray, dev):
         import torch
@@ -302,10 +294,10 @@ class DeviceVHSProcessor:
         while True:
             t_runs = torch.empty((1 + 4 * cap,), dtype=torch.int32, device=dev) if runs else None      # [0] is the counter
             _lib.check(self._lib.fw_vhs_gray_stats_u8(
-                self._table(frames), n, h, w, c, int(self.config.dropout_min_length),
-                C.c_void_p(t_sums.data_ptr()) if sums else None, C.c_void_p(t_bottom.data_ptr()) if bottom else None,
-                C.c_void_p(t_runs.data_ptr() + 4) if runs else None, cap, C.c_void_p(t_runs.data_ptr()) if runs else None,
-                self._stream(dev)))
+                _lib.ptr_table(frames), n, h, w, c, int(self.config.dropout_min_length),
+                _lib.ptr(t_sums) if sums else None, _lib.ptr(t_bottom) if bottom else None,
+                C.c_void_p(t_runs.data_ptr() + 4) if runs else None, cap, _lib.ptr(t_runs) if runs else None,
+                _lib.stream_ptr(dev)))
             if not runs:
                 break
             fetched = t_runs.cpu().numpy()                            # the wait of this batch
@@ -328,8 +320,8 @@ class DeviceVHSProcessor:
         dev = srcs[0].device
         rows = self._upload(np.asarray(spec_rows, dtype=np.int32).reshape(-1, 4), dev)
         fac = self._upload(np.asarray(spec_factors, dtype=np.float32).reshape(-1, 2), dev)
-        _lib.check(self._lib.fw_vhs_blend_rows_u8(self._table(srcs), self._table(dsts), len(srcs), h, w * c, C.c_void_p(rows.data_ptr()),
-                                                  C.c_void_p(fac.data_ptr()), int(rows.shape[0]), self._stream(dev)))
+        _lib.check(self._lib.fw_vhs_blend_rows_u8(_lib.ptr_table(srcs), _lib.ptr_table(dsts), len(srcs), h, w * c, _lib.ptr(rows),
+                                                  _lib.ptr(fac), int(rows.shape[0]), _lib.stream_ptr(dev)))
 
     @_lib.on_tensor_device
     def rainbow_device(self, frames: Sequence, strength: float, outs: Optional[Sequence] = None) -> List:
@@ -347,10 +339,10 @@ class DeviceVHSProcessor:
             self._check_frames(frames + outs)
         _check_no_overlap(outs, frames)
         fa, fb = float(np.float32(strength)), float(np.float32(1 - strength))
-        st = self._stream(frames[0].device)
+        st = _lib.stream_ptr(frames[0].device)
         for b in range(0, len(frames), BATCH):
             src, dst = frames[b:b + BATCH], outs[b:b + BATCH]
-            _lib.check(self._lib.fw_vhs_rainbow_u8(self._table(src), self._table(dst), len(src), h, w, fa, fb, st))
+            _lib.check(self._lib.fw_vhs_rainbow_u8(_lib.ptr_table(src), _lib.ptr_table(dst), len(src), h, w, fa, fb, st))
         return list(outs)
 
     @_lib.on_tensor_device
@@ -361,8 +353,8 @@ class DeviceVHSProcessor:
         dev = frames[0].device
         t = self._upload(np.asarray(tasks, dtype=np.int32).reshape(-1, 5), dev)
         sums = torch.empty((int(t.shape[0]),), dtype=torch.int64, device=dev)
-        _lib.check(self._lib.fw_vhs_box_gray_sums_u8(self._table(frames), len(frames), h, w, c, C.c_void_p(t.data_ptr()), int(t.shape[0]),
-                                                     C.c_void_p(sums.data_ptr()), self._stream(dev)))
+        _lib.check(self._lib.fw_vhs_box_gray_sums_u8(_lib.ptr_table(frames), len(frames), h, w, c, _lib.ptr(t), int(t.shape[0]),
+                                                     _lib.ptr(sums), _lib.stream_ptr(dev)))
         return sums.cpu().numpy()
 
     @_lib.on_tensor_device
@@ -372,16 +364,16 @@ class DeviceVHSProcessor:
         _check_no_overlap(results, sources)
         dev = results[0].device
         t = self._upload(np.asarray(boxes, dtype=np.int32).reshape(-1, 8), dev)
-        _lib.check(self._lib.fw_vhs_dropout_repair_u8(self._table(sources), len(sources), self._table(results), len(results), h, w, c,
-                                                      C.c_void_p(t.data_ptr()), int(t.shape[0]), float(strength), self._stream(dev)))
+        _lib.check(self._lib.fw_vhs_dropout_repair_u8(_lib.ptr_table(sources), len(sources), _lib.ptr_table(results), len(results), h, w, c,
+                                                      _lib.ptr(t), int(t.shape[0]), float(strength), _lib.stream_ptr(dev)))
 
     @_lib.on_tensor_device
     def edge_counts_device(self, frames: Sequence) -> np.ndarray:
         import torch
         h, w, c = self._check_frames(frames)
         counts = torch.empty((len(frames), h), dtype=torch.int32, device=frames[0].device)
-        _lib.check(self._lib.fw_vhs_edge_counts_u8(self._table(frames), len(frames), h, w, C.c_void_p(counts.data_ptr()),
-                                                   self._stream(frames[0].device)))
+        _lib.check(self._lib.fw_vhs_edge_counts_u8(_lib.ptr_table(frames), len(frames), h, w, _lib.ptr(counts),
+                                                   _lib.stream_ptr(frames[0].device)))
         return counts.cpu().numpy()
 
     @_lib.on_tensor_device
@@ -391,8 +383,8 @@ class DeviceVHSProcessor:
         dev = frames[0].device
         t = self._upload(np.asarray(samples, dtype=np.int32).reshape(-1, 3), dev)
         out = torch.empty((int(t.shape[0]), 2), dtype=torch.int32, device=dev)
-        _lib.check(self._lib.fw_vhs_chroma_samples_u8(self._table(frames), len(frames), h, w, C.c_void_p(t.data_ptr()), int(t.shape[0]),
-                                                      C.c_void_p(out.data_ptr()), self._stream(dev)))
+        _lib.check(self._lib.fw_vhs_chroma_samples_u8(_lib.ptr_table(frames), len(frames), h, w, _lib.ptr(t), int(t.shape[0]),
+                                                      _lib.ptr(out), _lib.stream_ptr(dev)))
         return out.cpu().numpy()
 
     @_lib.on_tensor_device
@@ -401,7 +393,7 @@ class DeviceVHSProcessor:
         outs = _lib.empty_like_many(frames)
         _check_no_overlap(outs, frames)
         table = (C.c_int32 * len(frames))(*[int(s) for s in shifts])
-        _lib.check(self._lib.fw_vhs_chroma_shift_u8(self._table(frames), self._table(outs), table, len(frames), h, w, self._stream(frames[0].device)))
+        _lib.check(self._lib.fw_vhs_chroma_shift_u8(_lib.ptr_table(frames), _lib.ptr_table(outs), table, len(frames), h, w, _lib.stream_ptr(frames[0].device)))
         return outs
 
     @_lib.on_tensor_device
@@ -411,15 +403,15 @@ class DeviceVHSProcessor:
         come back as float64."""
         import torch
         h, w, c = self._check_frames([frame])
-        dev, st = frame.device, self._stream(frame.device)
+        dev, st = frame.device, _lib.stream_ptr(frame.device)
         out: dict = {}
         shifts = torch.empty(((h + 2) // 5,), dtype=torch.int32, device=dev)
-        _lib.check(self._lib.fw_vhs_jitter_shifts_u8(C.c_void_p(frame.data_ptr()), h, w, c, C.c_void_p(shifts.data_ptr()), st))
+        _lib.check(self._lib.fw_vhs_jitter_shifts_u8(_lib.ptr(frame), h, w, c, _lib.ptr(shifts), st))
         if c == 3:
             sums = torch.empty((w - 1,), dtype=torch.int64, device=dev)
-            _lib.check(self._lib.fw_vhs_column_sums_u8(C.c_void_p(frame.data_ptr()), h, w, C.c_void_p(sums.data_ptr()), st))
+            _lib.check(self._lib.fw_vhs_column_sums_u8(_lib.ptr(frame), h, w, _lib.ptr(sums), st))
             sat = torch.empty((h, w), dtype=torch.float64, device=dev)
-            _lib.check(self._lib.fw_vhs_saturation_f64(C.c_void_p(frame.data_ptr()), h, w, C.c_void_p(sat.data_ptr()), st))
+            _lib.check(self._lib.fw_vhs_saturation_f64(_lib.ptr(frame), h, w, _lib.ptr(sat), st))
             magnitude = torch.abs(torch.fft.fft2(sat))
             pair = torch.stack([magnitude[h // 4:h // 2, w // 4:w // 2].max(), magnitude.mean()]).cpu().numpy()
             out["rainbow"] = (float(pair[0]), float(pair[1]))
