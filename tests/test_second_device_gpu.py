@@ -52,6 +52,10 @@ def test_nafnet_and_tap_driver_on_device_1(hip_lib):
         dn = T.TAPDenoiser(T.TAPDenoiseConfig(model="nafnet", tile_size=0, temporal_window=3, gpu_id=dev.index), engine=e)
         return np.stack([t.cpu().numpy() for t in dn.denoise_clip_device(frames)])
     _both(make, run)
+    e = make(1)                                       # a tensor on another device than the engine's is refused, as by the other engines
+    with pytest.raises(ValueError, match="tensor is on cuda:0, engine on cuda:1"):
+        e.denoise_device(torch.from_numpy(frames[0]).to("cuda:0"))
+    e.close()
 
 
 def test_ifnet_on_device_1(hip_lib):

@@ -448,18 +448,8 @@ def on_tensor_device(fn):
                     dev = t.device
                     break
         if dev is None and args:
-            # no CUDA tensor among the arguments (numpy frames, None placeholders): the owner says where it lives -
-            # an engine's device (`_dev` / `device_id`) or a driver's `config.gpu_id`
-            owner = args[0]
-            cand = getattr(owner, "_dev", None)
-            if cand is None:
-                cand = getattr(owner, "device_id", None)
-            if cand is None:
-                cand = getattr(getattr(owner, "config", None), "gpu_id", None)
-            if isinstance(cand, torch.device):
-                dev = cand if cand.type == "cuda" else None
-            elif isinstance(cand, int) and not isinstance(cand, bool) and cand >= 0 and torch.cuda.is_available():
-                dev = torch.device("cuda", cand)
+            # no CUDA tensor among the arguments (numpy frames, None placeholders): the owner says where it lives
+            dev = owner_device(args[0])
         if dev is None:
             return fn(*args, **kwargs)
         with torch.cuda.device(dev):
@@ -467,9 +457,27 @@ def on_tensor_device(fn):
     return wrapped
 
 
-def ptr(t) -> C.c_void_p:
-    """The device address of a tensor as a pointer argument of the C-ABI."""
-    return C.c_void_p(t.data_ptr())
+def owner_device(obj):
+    """The CUDA device an engine, a stage or a driver lives on, or ``None``: an engine's ``_dev`` / ``device_id``, a driver's
+    ``config.gpu_id``, a stage's ``gpu_id``."""
+    import torch
+    cand = getattr(obj, "_dev", None)
+    if cand is None:
+        cand = getattr(obj, "device_id", None)
+    if cand is None:
+        cand = getattr(getattr(obj, "config", None), "gpu_id", None)
+    if cand is None:
+        cand = getattr(obj, "gpu_id", None)
+    if isinstance(cand, torch.device):
+        return cand if cand.type == "cuda" else None
+    if isinstance(cand, int) and not isinstance(cand, bool) and cand >= 0 and torch.cuda.is_available():
+        return torch.device("cuda", cand)
+    return None
+
+
+def ptr(t) -> Optional[C.c_void_p]:
+    """The device address of a tensor as a pointer argument of the C-ABI; ``None`` (an optional buffer left out) stays ``None``."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def ptr_table(tensors) -> C.Array:

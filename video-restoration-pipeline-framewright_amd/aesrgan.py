@@ -30,37 +30,28 @@ from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import FramewrightHipError
+from ._engine import Engine, to_numpy
 from .synth import aesrgan_attention_positions
 
 logger = logging.getLogger(__name__)
 
 
-def _np(t) -> np.ndarray:
-    return t if isinstance(t, np.ndarray) else t.detach().cpu().float().numpy()
-
-
-class AESRGANEngine:
+class AESRGANEngine(Engine):
     """``AESRGAN(num_in_ch=3, num_out_ch=3, num_feat=64, num_block, scale, num_attention)`` resident on one GPU: thin owner of an
     ``fw_aesrgan*``; the weights, the workspace arena and the launches of a forward live behind the C-ABI."""
 
     def __init__(self, num_block: int = 23, scale: int = 2, num_attention: int = 4, dtype: str = "f16", device_id: int = 0):
-        import torch
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__("fw_aesrgan_create", "fw_aesrgan_destroy", dtype, device_id, num_block=num_block, scale=scale,
+                         num_attention=num_attention)
+        self._mu = threading.Lock()
+        self._loaded = False
+
+    def _configure(self, num_block, scale, num_attention):
         if scale not in (2, 4) or num_block < 1 or num_attention < 1 or num_attention > num_block:
             raise ValueError("AESRGANEngine: scale 2 or 4, 1 <= num_attention <= num_block")
-        if dtype not in _lib.DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPES)}")
         self.num_block, self.scale, self.num_attention = int(num_block), int(scale), int(num_attention)
         self.attn_after = aesrgan_attention_positions(self.num_block, self.num_attention)
-        self.dtype, self.device_id = dtype, int(device_id)
-        self._dev = torch.device("cuda", self.device_id)
-        self._mu = threading.Lock()
-        h = C.c_void_p()
-        _lib.check(self._lib.fw_aesrgan_create(self.device_id, self.num_block, self.scale, self.num_attention, _lib.DTYPES[dtype], C.byref(h)))
-        self._h = h
-        self._loaded = False
+        return self.num_block, self.scale, self.num_attention
 
     def load_state_dict(self, state: Mapping[str, object], attention: Mapping[str, object]) -> None:
         """``state``: the RRDB trunk / tail under BasicSR's key names (``conv_first``, ``body.{i}.rdb{1,2,3}.conv{1..5}``,
@@ -73,14 +64,14 @@ class AESRGANEngine:
         items = []
         for k in names:
             if k + ".weight" not in state or k + ".bias" not in state:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"state dict is missing {k}")
+                raise self.missing_key(k)
             items += [(k + ".weight", state[k + ".weight"]), (k + ".bias", state[k + ".bias"])]
         for i in self.attn_after:
             for name in ("query", "key", "value"):
                 items += [(f"attn.{i}.{name}.weight", attention[f"attn.{i}.{name}.weight"]), (f"attn.{i}.{name}.bias", attention[f"attn.{i}.{name}.bias"])]
             items.append((f"attn.{i}.gamma", attention[f"attn.{i}.gamma"]))
         for key, t in items:
-            a = np.ascontiguousarray(_np(t), dtype=np.float32).reshape(-1)
+            a = np.ascontiguousarray(to_numpy(t), dtype=np.float32).reshape(-1)
             _lib.check(self._lib.fw_aesrgan_set_tensor(self._h, key.encode(), C.c_void_p(a.ctypes.data), a.size))
         _lib.check(self._lib.fw_aesrgan_finalize(self._h))
         self._loaded = True
@@ -91,7 +82,7 @@ class AESRGANEngine:
         ``AESRGAN.forward`` returns for a 1 x 3 x H x W input, NHWC (asynchronous on torch's current stream)."""
         import torch
         if not self._loaded:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "AESRGANEngine: no weights loaded")
+            raise self.no_weights()
         if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 3 or x.shape[2] != 3:
             raise ValueError("forward_rgb expects a float32 CUDA tensor H x W x 3")
         if x.device != self._dev:
@@ -99,8 +90,7 @@ class AESRGANEngine:
         x = x.contiguous()
         H, W = int(x.shape[0]), int(x.shape[1])
         out = torch.empty((H * self.scale, W * self.scale, 3), dtype=torch.float32, device=self._dev)
-        st = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-        _lib.check(self._lib.fw_aesrgan_forward_rgb(self._h, C.c_void_p(x.data_ptr()), H, W, C.c_void_p(out.data_ptr()), st))
+        _lib.check(self._lib.fw_aesrgan_forward_rgb(self._h, _lib.ptr(x), H, W, _lib.ptr(out), _lib.stream_ptr(self._dev)))
         return out
 
     def enhance(self, bgr: np.ndarray) -> np.ndarray:
@@ -118,9 +108,7 @@ class AESRGANEngine:
         return np.ascontiguousarray(out[:, :, ::-1])
 
     def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.fw_aesrgan_destroy(h)
+        super().close()
         self._loaded = False
 
 
@@ -340,7 +328,7 @@ class AESRGANFaceRestorer:
         lib, eng = _lib.load(), self._model
         x1, y1, x2, y2 = region
         th, tw = y2 - y1, x2 - x1
-        st = C.c_void_p(torch.cuda.current_stream(eng._dev).cuda_stream)
+        st = _lib.stream_ptr(eng._dev)
         resized = torch.empty((th, tw, 3), dtype=torch.uint8, device=eng._dev)
         _lib.check(lib.fw_resize_linear_u8(C.c_void_p(enhanced.data_ptr()), int(enhanced.shape[0]), int(enhanced.shape[1]), 3, C.c_void_p(resized.data_ptr()), th, tw, st))
         _lib.check(lib.fw_face_paste_u8(C.c_void_p(d.data_ptr()), int(d.shape[0]), int(d.shape[1]), x1, y1, x2, y2, C.c_void_p(resized.data_ptr()),

@@ -12,7 +12,7 @@ from typing import Iterable, Iterator, List, Optional, Sequence
 
 import numpy as np
 
-from . import policy
+from . import _lib, policy
 
 
 class DeviceRestorationPipeline:
@@ -96,19 +96,12 @@ class DeviceRestorationPipeline:
     def _device(self):
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
-        the first of denoiser, colour grader, deinterlacer, VHS processor.  A new stage adds its branch here only."""
-        import torch
-        for e in (self.interpolator, self.upscaler):
-            if e is not None:
-                return torch.device("cuda", e.device_id)
-        if self.denoiser is not None:
-            return torch.device("cuda", self.denoiser.config.gpu_id)
-        if self.color_grader is not None:
-            return torch.device("cuda", self.color_grader.device_id)
-        if self.deinterlacer is not None:
-            return torch.device("cuda", self.deinterlacer.device_id)
-        if self.vhs_processor is not None:
-            return torch.device("cuda", self.vhs_processor.device_id)
+        the first of denoiser, colour grader, deinterlacer, VHS processor.  Every stage answers through `_lib.owner_device`: a new
+        stage adds its name to the tuple."""
+        for stage in (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor):
+            dev = _lib.owner_device(stage)
+            if dev is not None:
+                return dev
         raise ValueError("DeviceRestorationPipeline: no stage configured")
 
     def _gen_denoise(self, frames: Iterator, block: int):

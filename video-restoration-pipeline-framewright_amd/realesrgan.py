@@ -26,6 +26,7 @@ from typing import Dict, Mapping, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from ._engine import Engine, to_numpy, unwrap_state
 from ._lib import FramewrightHipError, FramewrightOutOfMemory
 from .synth import RRDB_MODELS, rrdbnet_conv_shapes, synthetic_rrdbnet_state
 
@@ -46,24 +47,20 @@ def _np_ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class RRDBNetEngine:
+class RRDBNetEngine(Engine):
     """One RRDBNet resident on one GPU (thin owner of an ``fw_rrdbnet*``)."""
 
     def __init__(self, num_block: int = 23, scale: int = 4, dtype: str = "f16", device_id: int = 0):
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        if dtype not in _lib.DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPES)}")
-        self.num_block, self.scale, self.dtype, self.device_id = int(num_block), int(scale), dtype, int(device_id)
-        h = C.c_void_p()
-        _lib.check(self._lib.fw_rrdbnet_create(self.device_id, self.num_block, self.scale, _lib.DTYPES[dtype],
-                                               C.byref(h)))
-        self._h = h
-        self._loaded = False
         # close() vs. calls in flight: the reference drives one shared upsampler from a thread pool (restorer.py:1830-1973) and
         # its OOM path clears the cache from whichever worker failed - the handle must not be destroyed under a sibling's call
         self._cv = threading.Condition()
         self._in_use = 0
+        super().__init__("fw_rrdbnet_create", "fw_rrdbnet_destroy", dtype, device_id, num_block=num_block, scale=scale)
+        self._loaded = False
+
+    def _configure(self, num_block, scale):
+        self.num_block, self.scale = int(num_block), int(scale)
+        return self.num_block, self.scale
 
     @contextlib.contextmanager
     def _handle(self):
@@ -83,18 +80,15 @@ class RRDBNetEngine:
     def load_state_dict(self, state: Mapping[str, object]) -> None:
         """``state``: BasicSR RRDBNet state-dict (numpy arrays or torch tensors); a checkpoint dict with
         ``params_ema`` / ``params`` is unwrapped like RealESRGANer does."""
-        if "params_ema" in state:
-            state = state["params_ema"]  # type: ignore[assignment]
-        elif "params" in state:
-            state = state["params"]  # type: ignore[assignment]
+        state = unwrap_state(state, ("params_ema", "params"))
         for key, cout, cin in rrdbnet_conv_shapes(self.num_block, self.scale):
             try:
                 w = state[key + ".weight"]
                 b = state[key + ".bias"]
             except KeyError as e:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"state dict is missing {e.args[0]}") from None
-            w = np.ascontiguousarray(_to_numpy(w), dtype=np.float32)
-            b = np.ascontiguousarray(_to_numpy(b), dtype=np.float32)
+                raise self.missing_key(e.args[0]) from None
+            w = np.ascontiguousarray(to_numpy(w), dtype=np.float32)
+            b = np.ascontiguousarray(to_numpy(b), dtype=np.float32)
             if w.shape != (cout, cin, 3, 3) or b.shape != (cout,):
                 raise FramewrightHipError(_lib.FW_ERR_INVALID,
                                           f"{key}: expected weight {(cout, cin, 3, 3)}, got {w.shape}")
@@ -131,26 +125,16 @@ class RRDBNetEngine:
         the un-clamped RGB network output."""
         import torch
 
-        if frame_bgr.dtype != torch.uint8 or not frame_bgr.is_cuda or frame_bgr.dim() != 3 or \
-                frame_bgr.shape[2] != 3 or not frame_bgr.is_contiguous():
-            raise ValueError("upscale_device expects a contiguous uint8 CUDA tensor H x W x 3")
-        if frame_bgr.device.index != self.device_id:
-            raise ValueError(f"tensor is on {frame_bgr.device}, engine on cuda:{self.device_id}")
+        self.check_frame_u8(frame_bgr, "upscale_device")
         h, w = int(frame_bgr.shape[0]), int(frame_bgr.shape[1])
         s = self.scale
         if out is None and out_rgb_f32 is None:
             out = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=frame_bgr.device)
-        for t, dt in ((out, torch.uint8), (out_rgb_f32, torch.float32)):
-            if t is not None and (t.dtype != dt or tuple(t.shape) != (h * s, w * s, 3) or not t.is_contiguous()
-                                  or t.device != frame_bgr.device):
-                raise ValueError("output tensor has the wrong dtype/shape/device")
-        if stream is None:
-            stream = torch.cuda.current_stream(frame_bgr.device).cuda_stream
+        self.check_out(out, out_rgb_f32, (h * s, w * s, 3))
         with self._handle() as hd:
             _lib.check(self._lib.fw_rrdbnet_upscale_u8(
-                hd, C.c_void_p(frame_bgr.data_ptr()), _lib.FW_DEVICE, h, w,
-                C.c_void_p(out.data_ptr()) if out is not None else None, _lib.FW_DEVICE,
-                C.c_void_p(out_rgb_f32.data_ptr()) if out_rgb_f32 is not None else None, C.c_void_p(stream)))
+                hd, _lib.ptr(frame_bgr), _lib.FW_DEVICE, h, w, _lib.ptr(out), _lib.FW_DEVICE, _lib.ptr(out_rgb_f32),
+                _lib.stream_ptr(frame_bgr.device) if stream is None else C.c_void_p(stream)))
         return out if out is not None else out_rgb_f32
 
     def upscale_stream(self, frames, depth: int = 2):
@@ -244,21 +228,7 @@ class RRDBNetEngine:
             while h and self._in_use:
                 cv.wait()
         if h:
-            self._lib.fw_rrdbnet_destroy(h)
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _to_numpy(t) -> np.ndarray:
-    if isinstance(t, np.ndarray):
-        return t
-    if hasattr(t, "detach"):
-        return t.detach().float().cpu().numpy()
-    return np.asarray(t)
+            self._destroy(h)
 
 
 def _check_frame(frame: np.ndarray) -> np.ndarray:
@@ -282,9 +252,8 @@ def resize_lanczos4_u8(img: np.ndarray, dst_w: int, dst_h: int, device_id: int =
         a = np.ascontiguousarray(img)
         src = torch.from_numpy(a.view(np.int16) if wide else a).cuda()          # the bytes only: torch's uint16 support is partial
         dst = torch.empty((dst_h, dst_w) if img.ndim == 2 else (dst_h, dst_w, c), dtype=torch.int16 if wide else torch.uint8, device="cuda")
-        st = torch.cuda.current_stream().cuda_stream
         fn = _lib.load().fw_resize_lanczos4_u16 if wide else _lib.load().fw_resize_lanczos4_u8
-        _lib.check(fn(C.c_void_p(src.data_ptr()), img.shape[0], img.shape[1], c, C.c_void_p(dst.data_ptr()), dst_h, dst_w, C.c_void_p(st)))
+        _lib.check(fn(C.c_void_p(src.data_ptr()), img.shape[0], img.shape[1], c, C.c_void_p(dst.data_ptr()), dst_h, dst_w, _lib.stream_ptr(None)))
         out = dst.cpu().numpy()
         return out.view(np.uint16) if wide else out
 

@@ -16,7 +16,7 @@ from typing import List, Mapping, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import FramewrightHipError
+from ._engine import Engine, unwrap_state
 
 RESTORMER_ARGS = dict(dim=48, num_blocks=(4, 6, 6, 8), num_refinement_blocks=4, heads=(1, 2, 4, 8), ffn_expansion_factor=2.66)
 
@@ -73,20 +73,17 @@ def synthetic_restormer_state(seed: int = 0, **args):
     return sd
 
 
-def _to_numpy(t) -> np.ndarray:
-    return t if isinstance(t, np.ndarray) else t.detach().cpu().float().numpy()
-
-
-class RestormerEngine:
+class RestormerEngine(Engine):
     """Restormer resident on one GPU: thin owner of an ``fw_restormer*`` (csrc/restormer.hip - weight re-layout, workspace arena
     and the ~800 launches of a forward live behind the C-ABI, one mutex per handle).  ``denoise_device`` mirrors NAFNetEngine
     (uint8 BGR in, uint8 BGR out)."""
 
     def __init__(self, dim: int = 48, num_blocks: Sequence[int] = (4, 6, 6, 8), num_refinement_blocks: int = 4,
                  heads: Sequence[int] = (1, 2, 4, 8), ffn_expansion_factor: float = 2.66, dtype: str = "f16", device_id: int = 0):
-        import torch
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__("fw_restormer_create", "fw_restormer_destroy", dtype, device_id, dim=dim, num_blocks=num_blocks,
+                         num_refinement_blocks=num_refinement_blocks, heads=heads, ffn_expansion_factor=ffn_expansion_factor)
+
+    def _configure(self, dim, num_blocks, num_refinement_blocks, heads, ffn_expansion_factor):
         if dim != 48:
             raise ValueError("RestormerEngine: dim must be 48 (per-head width 48 / 96 is what the attention kernels take)")
         self.args = dict(dim=int(dim), num_blocks=tuple(num_blocks), num_refinement_blocks=int(num_refinement_blocks),
@@ -94,35 +91,13 @@ class RestormerEngine:
         for (_, _, c, h) in _stages(dim, num_blocks, num_refinement_blocks, heads):
             if c % h or c // h not in (48, 96):
                 raise ValueError("RestormerEngine: channels per head must be 48 or 96")
-        if dtype not in _lib.DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPES)}")
-        self.dtype, self.device_id = dtype, int(device_id)
-        self._dev = torch.device("cuda", self.device_id)
-        nb = (C.c_int * 4)(*self.args["num_blocks"])
-        hd = (C.c_int * 4)(*self.args["heads"])
-        h = C.c_void_p()
-        _lib.check(self._lib.fw_restormer_create(self.device_id, int(dim), nb, int(num_refinement_blocks), hd,
-                                                 float(ffn_expansion_factor), _lib.DTYPES[dtype], C.byref(h)))
-        self._h = h
-        self._state = None
+        return (int(dim), (C.c_int * 4)(*self.args["num_blocks"]), int(num_refinement_blocks), (C.c_int * 4)(*self.args["heads"]),
+                float(ffn_expansion_factor))
 
     # ---- weights ----------------------------------------------------------------------------------------------------
     def load_state_dict(self, state: Mapping[str, object]) -> None:
-        if "params" in state:
-            state = state["params"]  # type: ignore[assignment]
-        elif "state_dict" in state:
-            state = state["state_dict"]  # type: ignore[assignment]
-        kept = {}
-        for key, shape in restormer_tensor_shapes(**self.args):
-            if key not in state:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"state dict is missing {key}")
-            a = np.ascontiguousarray(_to_numpy(state[key]), dtype=np.float32)
-            if tuple(a.shape) != tuple(shape):
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"{key}: expected shape {shape}, got {a.shape}")
-            _lib.check(self._lib.fw_restormer_set_tensor(self._h, key.encode(), C.c_void_p(a.ctypes.data), a.size))
-            kept[key] = a
-        _lib.check(self._lib.fw_restormer_finalize(self._h))
-        self._state = kept
+        self._state = self.load_tensors(restormer_tensor_shapes(**self.args), unwrap_state(state, ("params", "state_dict")),
+                                        self._lib.fw_restormer_set_tensor, self._lib.fw_restormer_finalize)
 
     # ---- forward ----------------------------------------------------------------------------------------------------
     def denoise_device(self, frame, out=None, out_rgb_f32=None):
@@ -130,51 +105,28 @@ class RestormerEngine:
         shape; asynchronous on torch's current stream of the engine's device."""
         import torch
         if self._state is None:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "RestormerEngine: no weights loaded")
-        if frame.dtype != torch.uint8 or not frame.is_cuda or frame.dim() != 3 or frame.shape[2] != 3 or not frame.is_contiguous():
-            raise ValueError("denoise_device expects a contiguous uint8 CUDA tensor H x W x 3")
-        if frame.device != self._dev:
-            raise ValueError(f"tensor is on {frame.device}, engine on {self._dev}")
+            raise self.no_weights()
+        self.check_frame_u8(frame, "denoise_device")
         H, Wd = int(frame.shape[0]), int(frame.shape[1])
         if H % 8 or Wd % 8:
             raise ValueError(f"Restormer needs frame sizes divisible by 8, got {Wd}x{H}")
         if out is None and out_rgb_f32 is None:
             out = torch.empty_like(frame)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        st = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-        _lib.check(self._lib.fw_restormer_denoise_u8(self._h, p(frame), _lib.FW_DEVICE, H, Wd, p(out), _lib.FW_DEVICE,
-                                                     p(out_rgb_f32), st))
+        _lib.check(self._lib.fw_restormer_denoise_u8(self._h, _lib.ptr(frame), _lib.FW_DEVICE, H, Wd, _lib.ptr(out), _lib.FW_DEVICE,
+                                                     _lib.ptr(out_rgb_f32), _lib.stream_ptr(self._dev)))
         return out if out is not None else out_rgb_f32
 
     def denoise(self, frame_bgr: np.ndarray) -> np.ndarray:
-        f = np.ascontiguousarray(frame_bgr)
-        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-            raise ValueError("expected an H x W x 3 uint8 BGR frame")
+        f = self.check_host_frame_u8(frame_bgr)
         if f.shape[0] % 8 or f.shape[1] % 8:
             raise ValueError(f"Restormer needs frame sizes divisible by 8, got {f.shape[1]}x{f.shape[0]}")
         if self._state is None:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "RestormerEngine: no weights loaded")
+            raise self.no_weights()
         out = np.empty_like(f)
         _lib.check(self._lib.fw_restormer_denoise_u8(self._h, C.c_void_p(f.ctypes.data), _lib.FW_HOST, f.shape[0], f.shape[1],
                                                      C.c_void_p(out.ctypes.data), _lib.FW_HOST, None, None))
         return out
 
-    def clone(self) -> "RestormerEngine":
-        """A second handle with the same weights and its own workspace (the tiled TAP path runs several tiles concurrently)."""
-        if self._state is None:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "RestormerEngine.clone: no weights loaded")
-        e = RestormerEngine(dtype=self.dtype, device_id=self.device_id, **self.args)
-        e.load_state_dict(self._state)
-        return e
-
     def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.fw_restormer_destroy(h)
+        super().close()
         self._state = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -23,8 +23,9 @@ from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Uni
 import numpy as np
 
 from . import _lib, policy
+from ._engine import Engine, StreamPool
 from ._lib import FramewrightHipError
-from .realesrgan import _imread, _imwrite, _to_numpy
+from .realesrgan import _imread, _imwrite
 from .synth import ifnet_tensor_shapes
 
 logger = logging.getLogger(__name__)
@@ -70,87 +71,44 @@ def convtranspose_as_3x3(w: np.ndarray, b: np.ndarray) -> Tuple[np.ndarray, np.n
     return out, np.repeat(b.astype(np.float32), 4)
 
 
-class IFNetEngine:
+class IFNetEngine(Engine):
     """IFNet v4.6 resident on one GPU: thin owner of an ``fw_ifnet*`` (csrc/ifnet.hip).  The weight transforms, the workspace
     and the ~100 launches of a forward live behind the C-ABI (``fw_ifnet_interp_u8``), serialised per handle by its mutex;
     ``stride2_as_unshuffled_3x3`` / ``convtranspose_as_3x3`` above are the numpy statements of the two transforms the C++
     side applies (tests check both against torch convolutions)."""
 
     def __init__(self, dtype: str = "f16", device_id: int = 0):
-        import torch
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        if dtype not in _lib.DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPES)}")
-        self.dtype, self.device_id = dtype, int(device_id)
-        self._dev = torch.device("cuda", self.device_id)
-        h = C.c_void_p()
-        _lib.check(self._lib.fw_ifnet_create(self.device_id, _lib.DTYPES[dtype], C.byref(h)))
-        self._h = h
+        super().__init__("fw_ifnet_create", "fw_ifnet_destroy", dtype, device_id)
         self._loaded = False
+        self._pool = None           # engine clones on side streams, made by the first interpolate_pairs_device
 
     def load_state_dict(self, state: Mapping[str, object]) -> None:
-        kept = {}
-        for key, shape in ifnet_tensor_shapes():
-            if key not in state:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"state dict is missing {key}")
-            a = np.ascontiguousarray(_to_numpy(state[key]), dtype=np.float32)
-            if tuple(a.shape) != tuple(shape):
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"{key}: expected shape {shape}, got {a.shape}")
-            _lib.check(self._lib.fw_ifnet_set_tensor(self._h, key.encode(), C.c_void_p(a.ctypes.data), a.size))
-            kept[key] = a
-        _lib.check(self._lib.fw_ifnet_finalize(self._h))
-        self._loaded = True
-        self._state = kept          # what clone() loads (21 MB of fp32)
+        self._state = self.load_tensors(ifnet_tensor_shapes(), state, self._lib.fw_ifnet_set_tensor, self._lib.fw_ifnet_finalize)
+        self._loaded = True         # _state: what clone() loads (21 MB of fp32)
         self._close_workers()
 
     def clone(self) -> "IFNetEngine":
         """A second engine with the same weights and its own workspace (pairs in flight on their own streams)."""
         if not self._loaded:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "IFNetEngine: no weights loaded")
-        e = IFNetEngine(self.dtype, self.device_id)
-        e.load_state_dict(self._state)
-        return e
-
+            raise self.no_weights()
+        return super().clone()
 
     def _close_workers(self) -> None:
-        for wk in getattr(self, "_workers", None) or []:
-            if wk["engine"] is not self:
-                wk["engine"].close()
-        self._workers = None
+        if getattr(self, "_pool", None) is not None:
+            self._pool.close()
 
     def interpolate_pairs_device(self, pairs: Sequence, timestep: float = 0.5) -> List:
         """Mid frames of independent pairs ``[(img0, img1), ...]`` (uint8 CUDA tensors).  At 1080p a forward is ~100 launches of
         10 - 30 us on feature maps of a few thousand pixels - each fills a fraction of the chip - so up to FW_RIFE_PAIR_STREAMS (default 3) pairs are in
         flight at once, each on its own stream with its own engine clone (= its own workspace).  Every pair goes through the same
         kernels with the same launch geometry as alone: identical frames.  Asynchronous on torch's current stream."""
-        import torch
         pairs = list(pairs)
         k = min(len(pairs), _lib.side_streams("FW_RIFE_PAIR_STREAMS", 3))
         if k <= 1:
             return [self.interpolate_device(a, b, timestep) for a, b in pairs]
-        ws = getattr(self, "_workers", None)
-        if ws is None:
-            ws = self._workers = []
-        while len(ws) < k:
-            ws.append({"engine": self if not ws else self.clone(), "stream": torch.cuda.Stream(device=self._dev)})
-        main = torch.cuda.current_stream(self._dev)
-        outs = _lib.empty_like_many([a for a, _ in pairs])     # one allocation: a hipMalloc per mid frame would serialise the streams
-        start = torch.cuda.Event()
-        start.record(main)          # inputs and output buffers are ready once the caller's stream gets here
-        for i, (a, b) in enumerate(pairs):
-            wk = ws[i % k]
-            if i < k:
-                wk["stream"].wait_event(start)
-            with torch.cuda.stream(wk["stream"]):
-                wk["engine"].interpolate_device(a, b, timestep, out=outs[i])
-            for t in (a, b, outs[i]):
-                t.record_stream(wk["stream"])
-        for wk in ws[:k]:
-            ev = torch.cuda.Event()
-            ev.record(wk["stream"])
-            main.wait_event(ev)
-        return outs
+        if self._pool is None:
+            self._pool = StreamPool(self, self._dev)
+        return self._pool.fan_out(pairs, lambda eng, pair, out: eng.interpolate_device(pair[0], pair[1], timestep, out=out), k)
 
     def flops(self, height: int, width: int) -> float:
         return float(self._lib.fw_ifnet_flops(self._h, height, width))
@@ -160,7 +118,7 @@ class IFNetEngine:
         torch's current stream of that device)."""
         import torch
         if not self._loaded:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "IFNetEngine: no weights loaded")
+            raise self.no_weights()
         for t in (img0, img1):
             if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous():
                 raise ValueError("interpolate_device expects contiguous uint8 CUDA tensors H x W x 3")
@@ -171,13 +129,10 @@ class IFNetEngine:
         H, W = int(img0.shape[0]), int(img0.shape[1])
         if out is None and out_rgb_f32 is None:
             out = torch.empty((H, W, 3), dtype=torch.uint8, device=self._dev)
-        for t, dt in ((out, torch.uint8), (out_rgb_f32, torch.float32)):
-            if t is not None and (t.dtype != dt or tuple(t.shape) != (H, W, 3) or not t.is_contiguous() or t.device != self._dev):
-                raise ValueError("output tensor has the wrong dtype/shape/device")
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        st = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+        self.check_out(out, out_rgb_f32, (H, W, 3))
+        p = _lib.ptr
         _lib.check(self._lib.fw_ifnet_interp_u8(self._h, p(img0), p(img1), _lib.FW_DEVICE, H, W, float(timestep), p(out),
-                                                _lib.FW_DEVICE, p(out_rgb_f32), st))
+                                                _lib.FW_DEVICE, p(out_rgb_f32), _lib.stream_ptr(self._dev)))
         return out if out is not None else out_rgb_f32
 
     def last_flow(self, height: int, width: int):
@@ -189,15 +144,14 @@ class IFNetEngine:
         with torch.cuda.device(self._dev):
             flow = torch.empty((hp, wp, 4), dtype=torch.float32, device=self._dev)
             mask = torch.empty((hp, wp), dtype=torch.float32, device=self._dev)
-            st = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-            _lib.check(self._lib.fw_ifnet_last_flow(self._h, int(height), int(width), C.c_void_p(flow.data_ptr()),
-                                                    C.c_void_p(mask.data_ptr()), st))
+            _lib.check(self._lib.fw_ifnet_last_flow(self._h, int(height), int(width), _lib.ptr(flow), _lib.ptr(mask),
+                                                    _lib.stream_ptr(self._dev)))
         return flow, mask
 
     def interpolate(self, img0: np.ndarray, img1: np.ndarray, timestep: float = 0.5) -> np.ndarray:
         """Host frames in, host frame out (the engine stages them: ``FW_HOST`` buffers through the C-ABI)."""
         if not self._loaded:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "IFNetEngine: no weights loaded")
+            raise self.no_weights()
         a, b = np.ascontiguousarray(img0), np.ascontiguousarray(img1)
         for f in (a, b):
             if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
@@ -212,15 +166,7 @@ class IFNetEngine:
 
     def close(self) -> None:
         self._close_workers()
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.fw_ifnet_destroy(h)
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 # ---- directory-level driver (FrameInterpolator) ---------------------------------------------------------------------
@@ -403,7 +349,7 @@ class FrameInterpolator:
             raise ValueError("expected a contiguous uint8 CUDA tensor H x W x C")
         H, W, Cc = (int(v) for v in frame.shape)
         with torch.cuda.device(frame.device):
-            st = C.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
+            st = _lib.stream_ptr(frame.device)
             a, b, out = torch.empty_like(frame), torch.empty_like(frame), torch.empty_like(frame)
             passes = [(2, int(100 * strength), 3)] + ([(1, int(50 * strength), 2)] if strength > 1.5 else [])
             src = frame

@@ -16,8 +16,9 @@ from typing import List, Mapping, Tuple
 
 import numpy as np
 
-from . import _lib
-from ._lib import FramewrightHipError
+from . import _engine, _lib
+from ._engine import Engine
+from ._lib import FramewrightHipError  # noqa: F401 - callers catch it as srvgg.FramewrightHipError
 
 SRVGG_MODELS = {
     # name: (num_conv, netscale)            (Real-ESRGAN release notes; realesrgan/archs/srvgg_arch.py)
@@ -29,11 +30,7 @@ NUM_FEAT = 64
 
 def unwrap_state(state: Mapping[str, object]) -> Mapping[str, object]:
     """``params_ema`` / ``params`` is unwrapped like RealESRGANer does."""
-    if "params_ema" in state:
-        return state["params_ema"]  # type: ignore[return-value]
-    if "params" in state:
-        return state["params"]  # type: ignore[return-value]
-    return state
+    return _engine.unwrap_state(state, ("params_ema", "params"))
 
 
 def is_srvgg_state_dict(state: Mapping[str, object]) -> bool:
@@ -68,44 +65,24 @@ def synthetic_srvgg_state(num_conv: int, scale: int, seed: int = 0):
     return sd
 
 
-def _to_numpy(t) -> np.ndarray:
-    if isinstance(t, np.ndarray):
-        return t
-    return t.detach().cpu().float().numpy()
-
-
-class SRVGGNetEngine:
+class SRVGGNetEngine(Engine):
     """SRVGGNetCompact resident on one GPU; same surface as RRDBNetEngine (load_state_dict / upscale_device / flops).  Thin owner of
     an ``fw_srvgg*`` (csrc/srvgg.hip): weight packing, the workspace and the launches of a forward live behind the C-ABI
     (``fw_srvgg_upscale_u8``), serialised per handle by its mutex."""
 
     def __init__(self, num_conv: int, scale: int = 4, dtype: str = "f16", device_id: int = 0):
-        import torch
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        if scale not in (1, 2, 3, 4) or 3 * scale * scale > 64:
-            raise ValueError("SRVGGNetEngine: scale must be 1..4")
-        if dtype not in _lib.DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(_lib.DTYPES)}")
-        self.num_conv, self.scale, self.dtype, self.device_id = int(num_conv), int(scale), dtype, int(device_id)
-        self._dev = torch.device("cuda", self.device_id)
-        h = C.c_void_p()
-        _lib.check(self._lib.fw_srvgg_create(self.device_id, NUM_FEAT, self.num_conv, self.scale, _lib.DTYPES[dtype], C.byref(h)))
-        self._h = h
+        super().__init__("fw_srvgg_create", "fw_srvgg_destroy", dtype, device_id, num_conv=num_conv, scale=scale)
         self._loaded = False
 
+    def _configure(self, num_conv, scale):
+        if scale not in (1, 2, 3, 4) or 3 * scale * scale > 64:
+            raise ValueError("SRVGGNetEngine: scale must be 1..4")
+        self.num_conv, self.scale = int(num_conv), int(scale)
+        return NUM_FEAT, self.num_conv, self.scale
+
     def load_state_dict(self, state: Mapping[str, object]) -> None:
-        state = unwrap_state(state)
-        for key, shape in srvgg_tensor_shapes(self.num_conv, self.scale):
-            if key not in state:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"state dict is missing {key}")
-            a = np.ascontiguousarray(_to_numpy(state[key]), dtype=np.float32)
-            if a.ndim == 1 and len(shape) == 1:
-                a = a.reshape(-1)
-            if tuple(a.shape) != tuple(shape):
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"{key}: expected shape {shape}, got {a.shape}")
-            _lib.check(self._lib.fw_srvgg_set_tensor(self._h, key.encode(), C.c_void_p(a.ctypes.data), a.size))
-        _lib.check(self._lib.fw_srvgg_finalize(self._h))
+        self.load_tensors(srvgg_tensor_shapes(self.num_conv, self.scale), unwrap_state(state), self._lib.fw_srvgg_set_tensor,
+                          self._lib.fw_srvgg_finalize)
         self._loaded = True
 
     def flops(self, H: int, W: int) -> float:
@@ -116,22 +93,16 @@ class SRVGGNetEngine:
         """frame_bgr: uint8 CUDA tensor H x W x 3.  Returns the uint8 BGR result (asynchronous on torch's current stream)."""
         import torch
         if not self._loaded:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "SRVGGNetEngine: no weights loaded")
+            raise self.no_weights()
         t = frame_bgr
-        if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous():
-            raise ValueError("upscale_device expects a contiguous uint8 CUDA tensor H x W x 3")
-        if t.device != self._dev:
-            raise ValueError(f"tensor is on {t.device}, engine on {self._dev}")
+        self.check_frame_u8(t, "upscale_device")
         s = self.scale
         H, W = int(t.shape[0]), int(t.shape[1])
         if out is None:
             out = torch.empty((H * s, W * s, 3), dtype=torch.uint8, device=self._dev)
-        for x, dt in ((out, torch.uint8), (out_rgb_f32, torch.float32)):
-            if x is not None and (x.dtype != dt or tuple(x.shape) != (H * s, W * s, 3) or not x.is_contiguous() or x.device != self._dev):
-                raise ValueError("output tensor has the wrong dtype/shape/device")
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        st = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-        _lib.check(self._lib.fw_srvgg_upscale_u8(self._h, p(t), _lib.FW_DEVICE, H, W, p(out), _lib.FW_DEVICE, p(out_rgb_f32), st))
+        self.check_out(out, out_rgb_f32, (H * s, W * s, 3))
+        _lib.check(self._lib.fw_srvgg_upscale_u8(self._h, _lib.ptr(t), _lib.FW_DEVICE, H, W, _lib.ptr(out), _lib.FW_DEVICE,
+                                                 _lib.ptr(out_rgb_f32), _lib.stream_ptr(self._dev)))
         return out
 
     def upscale(self, frame_bgr: np.ndarray) -> np.ndarray:
@@ -142,22 +113,19 @@ class SRVGGNetEngine:
             if frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
                 raise ValueError("expected an H x W x 3 uint16 BGR frame")
             if not self._loaded:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, "SRVGGNetEngine: no weights loaded")
+                raise self.no_weights()
             f16 = np.ascontiguousarray(frame_bgr)
             h, w = f16.shape[:2]
             out16 = np.empty((h * self.scale, w * self.scale, 3), dtype=np.uint16)
             _lib.check(self._lib.fw_srvgg_upscale_u16(self._h, C.c_void_p(f16.ctypes.data), _lib.FW_HOST, h, w, C.c_void_p(out16.ctypes.data),
                                                       _lib.FW_HOST, None, None))
             return out16
-        if not isinstance(frame_bgr, np.ndarray) or frame_bgr.dtype != np.uint8 or frame_bgr.ndim != 3 or frame_bgr.shape[2] != 3:
-            raise ValueError("expected an H x W x 3 uint8 BGR frame")
+        frame_bgr = self.check_host_frame_u8(frame_bgr if isinstance(frame_bgr, np.ndarray) else None)   # arrays only, as RRDBNetEngine
         with torch.cuda.device(self._dev):
-            out = self.upscale_device(torch.from_numpy(np.ascontiguousarray(frame_bgr)).to(self._dev))
+            out = self.upscale_device(torch.from_numpy(frame_bgr).to(self._dev))
             torch.cuda.synchronize(self._dev)
         return out.cpu().numpy()
 
     def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.fw_srvgg_destroy(h)
+        super().close()
         self._loaded = False

@@ -28,8 +28,9 @@ from typing import Callable, Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from ._engine import Engine, StreamPool, unwrap_state
 from ._lib import FramewrightHipError
-from .realesrgan import _imread, _imwrite, _to_numpy
+from .realesrgan import _imread, _imwrite
 from .synth import nafnet_tensor_shapes, synthetic_nafnet_state
 
 logger = logging.getLogger(__name__)
@@ -81,58 +82,30 @@ class TAPDenoiseResult:
     model_used: Optional[str] = None
 
 
-class NAFNetEngine:
+class NAFNetEngine(Engine):
     """One NAFNet resident on one GPU (owner of an ``fw_nafnet*``)."""
 
     def __init__(self, width: int = 64, middle_blk_num: int = 12, enc_blk_nums: Sequence[int] = (2, 2, 4, 8),
                  dec_blk_nums: Sequence[int] = (2, 2, 2, 2), dtype: str = "f16", device_id: int = 0):
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__("fw_nafnet_create", "fw_nafnet_destroy", dtype, device_id, width=width, middle_blk_num=middle_blk_num,
+                         enc_blk_nums=enc_blk_nums, dec_blk_nums=dec_blk_nums)
+
+    def _configure(self, width, middle_blk_num, enc_blk_nums, dec_blk_nums):
         if len(enc_blk_nums) != len(dec_blk_nums):
             raise ValueError("enc_blk_nums and dec_blk_nums must have the same length")
         self.args = dict(width=int(width), middle_blk_num=int(middle_blk_num), enc_blk_nums=tuple(enc_blk_nums),
                          dec_blk_nums=tuple(dec_blk_nums))
-        self.dtype, self.device_id = dtype, int(device_id)
         n = len(enc_blk_nums)
-        enc = (C.c_int * n)(*enc_blk_nums)
-        dec = (C.c_int * n)(*dec_blk_nums)
-        h = C.c_void_p()
-        _lib.check(self._lib.fw_nafnet_create(self.device_id, width, middle_blk_num, enc, dec, n, _lib.DTYPES[dtype],
-                                              C.byref(h)))
-        self._h = h
+        return width, middle_blk_num, (C.c_int * n)(*enc_blk_nums), (C.c_int * n)(*dec_blk_nums), n
 
     def load_state_dict(self, state: Mapping[str, object]) -> None:
         """NAFNet state-dict; a checkpoint dict with ``params`` / ``state_dict`` is unwrapped as the reference does
         (tap_denoise.py:348-355)."""
-        if "params" in state:
-            state = state["params"]  # type: ignore[assignment]
-        elif "state_dict" in state:
-            state = state["state_dict"]  # type: ignore[assignment]
-        kept = {}
-        for key, shape in nafnet_tensor_shapes(**self.args):
-            if key not in state:
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"state dict is missing {key}")
-            a = np.ascontiguousarray(_to_numpy(state[key]), dtype=np.float32)
-            if tuple(a.shape) != tuple(shape):
-                raise FramewrightHipError(_lib.FW_ERR_INVALID, f"{key}: expected shape {shape}, got {a.shape}")
-            _lib.check(self._lib.fw_nafnet_set_tensor(self._h, key.encode(), C.c_void_p(a.ctypes.data), a.size))
-            kept[key] = a
-        _lib.check(self._lib.fw_nafnet_finalize(self._h))
-        self._state = kept
-
-    def clone(self) -> "NAFNetEngine":
-        """A second handle with the same weights and its own workspace, so that two forwards can be in flight on two
-        streams (the tiled TAP path runs several tiles concurrently)."""
-        if getattr(self, "_state", None) is None:
-            raise FramewrightHipError(_lib.FW_ERR_INVALID, "NAFNetEngine.clone: no weights loaded")
-        e = NAFNetEngine(dtype=self.dtype, device_id=self.device_id, **self.args)
-        e.load_state_dict(self._state)
-        return e
+        self._state = self.load_tensors(nafnet_tensor_shapes(**self.args), unwrap_state(state, ("params", "state_dict")),
+                                        self._lib.fw_nafnet_set_tensor, self._lib.fw_nafnet_finalize)
 
     def denoise(self, frame_bgr: np.ndarray) -> np.ndarray:
-        f = np.ascontiguousarray(frame_bgr)
-        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-            raise ValueError("expected an H x W x 3 uint8 BGR frame")
+        f = self.check_host_frame_u8(frame_bgr)
         out = np.empty_like(f)
         _lib.check(self._lib.fw_nafnet_denoise_u8(self._h, C.c_void_p(f.ctypes.data), _lib.FW_HOST, f.shape[0], f.shape[1],
                                                   C.c_void_p(out.ctypes.data), _lib.FW_HOST, None, None))
@@ -142,18 +115,13 @@ class NAFNetEngine:
     def denoise_device(self, frame, out=None, out_rgb_f32=None, stream: Optional[int] = None):
         """torch.uint8 CUDA tensor H x W x 3 -> same shape; asynchronous on torch's current stream."""
         import torch
-        if frame.dtype != torch.uint8 or not frame.is_cuda or frame.dim() != 3 or frame.shape[2] != 3 or \
-                not frame.is_contiguous():
-            raise ValueError("denoise_device expects a contiguous uint8 CUDA tensor H x W x 3")
+        self.check_frame_u8(frame, "denoise_device")
         h, w = int(frame.shape[0]), int(frame.shape[1])
         if out is None and out_rgb_f32 is None:
             out = torch.empty_like(frame)
-        if stream is None:
-            stream = torch.cuda.current_stream(frame.device).cuda_stream
         _lib.check(self._lib.fw_nafnet_denoise_u8(
-            self._h, C.c_void_p(frame.data_ptr()), _lib.FW_DEVICE, h, w,
-            C.c_void_p(out.data_ptr()) if out is not None else None, _lib.FW_DEVICE,
-            C.c_void_p(out_rgb_f32.data_ptr()) if out_rgb_f32 is not None else None, C.c_void_p(stream)))
+            self._h, _lib.ptr(frame), _lib.FW_DEVICE, h, w, _lib.ptr(out), _lib.FW_DEVICE, _lib.ptr(out_rgb_f32),
+            _lib.stream_ptr(frame.device) if stream is None else C.c_void_p(stream)))
         return out if out is not None else out_rgb_f32
 
     # ---- single steps of a forward on the caller's buffers (tests, tools) ----
@@ -170,10 +138,8 @@ class NAFNetEngine:
             raise ValueError(f"run_block: {key!r} does not name a block of {int(stream_f32.shape[2])} channels")
         if sca_out is not None and (sca_out.dtype != torch.float32 or not sca_out.is_cuda or sca_out.numel() < stream_f32.shape[2]):
             raise ValueError("sca_out must be a float32 CUDA tensor of c elements")
-        st = torch.cuda.current_stream(stream_f32.device).cuda_stream
-        _lib.check(self._lib.fw_nafnet_run_block(self._h, key.encode(), C.c_void_p(stream_f32.data_ptr()), int(stream_f32.shape[0]),
-                                                 int(stream_f32.shape[1]), C.c_void_p(sca_out.data_ptr()) if sca_out is not None else None,
-                                                 C.c_void_p(st)))
+        _lib.check(self._lib.fw_nafnet_run_block(self._h, key.encode(), _lib.ptr(stream_f32), int(stream_f32.shape[0]),
+                                                 int(stream_f32.shape[1]), _lib.ptr(sca_out), _lib.stream_ptr(stream_f32.device)))
         return stream_f32
 
     def block_paths(self, key: str) -> int:
@@ -195,24 +161,12 @@ class NAFNetEngine:
         want = ((h, w, 2 * c), (2 * h, 2 * w, c)) if up else ((h, w, c), (h // 2, w // 2, 2 * c))
         if not 0 <= int(level) < len(self.args["enc_blk_nums"]) or (tuple(src_f32.shape), tuple(dst_f32.shape)) != want or (not up and (h | w) & 1):
             raise ValueError(f"run_resample: level {level} {'up' if up else 'down'} needs shapes {want}")
-        st = torch.cuda.current_stream(src_f32.device).cuda_stream
-        _lib.check(self._lib.fw_nafnet_run_resample(self._h, int(level), 1 if up else 0, C.c_void_p(src_f32.data_ptr()), int(src_f32.shape[0]),
-                                                    int(src_f32.shape[1]), C.c_void_p(dst_f32.data_ptr()), C.c_void_p(st)))
+        _lib.check(self._lib.fw_nafnet_run_resample(self._h, int(level), 1 if up else 0, _lib.ptr(src_f32), int(src_f32.shape[0]),
+                                                    int(src_f32.shape[1]), _lib.ptr(dst_f32), _lib.stream_ptr(src_f32.device)))
         return dst_f32
 
     def flops(self, h: int, w: int) -> float:
         return float(self._lib.fw_nafnet_flops(self._h, h, w))
-
-    def close(self) -> None:
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.fw_nafnet_destroy(h)
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- pure host logic of the driver (also used by the multi-GPU sharding) ------------------------------------------
@@ -252,6 +206,7 @@ class TAPDenoiser:
         self.model_dir = Path(model_dir) if model_dir else self.DEFAULT_MODEL_DIR
         self._engine = engine
         self._lib = None
+        self._tile_pool = self._frame_pool = None      # engine clones on side streams: tiles of a frame, whole frames of a clip
 
     # -- availability / model ------------------------------------------------------------------------
     def is_available(self) -> bool:
@@ -292,8 +247,7 @@ class TAPDenoiser:
     # -- device helpers --------------------------------------------------------------------------------
     def _stream(self):
         # every caller runs under on_tensor_device: the current device is the one that owns the frames
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(torch.cuda.current_device()).cuda_stream)
+        return _lib.stream_ptr(None)
 
     @_lib.on_tensor_device
     def _denoise_frame_tiled_device(self, frame):
@@ -317,7 +271,7 @@ class TAPDenoiser:
         k = max(1, min(len(tiles), self.TILE_STREAMS))
         workers = self._tile_workers(k, frame.device, ts)
         main = torch.cuda.current_stream(frame.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         start = torch.cuda.Event()
         start.record(main)           # the frame (and acc / wsum) are ready once the caller's stream gets here
         done = [None] * len(tiles)
@@ -347,23 +301,20 @@ class TAPDenoiser:
 
     def _tile_workers(self, k: int, device, ts: int):
         import torch
-        ws = getattr(self, "_workers", None)
-        if ws is None:
-            ws = self._workers = []
-        while len(ws) < k:
-            eng = self._engine if not ws else self._engine.clone()
-            ws.append({"engine": eng, "stream": torch.cuda.Stream(device=device), "free": None, "tile": None, "out": None})
-        for wk in ws[:k]:
+        if self._tile_pool is None:
+            self._tile_pool = StreamPool(self._engine, device, free=None, tile=None, out=None)
+        workers = self._tile_pool.take(k)
+        for wk in workers:
             if wk["tile"] is None or wk["tile"].shape[0] != ts:
                 wk["tile"] = torch.empty((ts, ts, 3), dtype=torch.uint8, device=device)
                 wk["out"] = torch.empty_like(wk["tile"])
-        return ws[:k]
+        return workers
 
     @staticmethod
     def _blend_tile(lib, main, done_ev, wk, acc, wsum, h, w, origin, ts, ov):
         import torch
         main.wait_event(done_ev)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         _lib.check(lib.fw_tile_blend_accumulate(p(acc), p(wsum), h, w, p(wk["out"]), origin[0], origin[1], ts, ts, ov,
                                                 C.c_void_p(main.cuda_stream)))
         wk["free"] = torch.cuda.Event()
@@ -493,36 +444,9 @@ class TAPDenoiser:
         # a NAFNet forward's time) occupy a fraction of the chip, so FW_TAP_FRAME_STREAMS (default 2) frames are in flight at once, each on its own
         # stream with its own engine clone (= its own workspace).  Every frame goes through the same kernels with the same
         # launch geometry as alone: identical outputs.
-        import torch
-        device = frames[0].device
-        workers = self._frame_workers(k, device)
-        main = torch.cuda.current_stream(device)
-        outs = _lib.empty_like_many(frames)
-        start = torch.cuda.Event()
-        start.record(main)           # the frames and the output buffers are ready once the caller's stream gets here
-        for i, f in enumerate(frames):
-            wk = workers[i % k]
-            if i < k:
-                wk["stream"].wait_event(start)
-            with torch.cuda.stream(wk["stream"]):
-                wk["engine"].denoise_device(f, out=outs[i])
-            f.record_stream(wk["stream"])
-            outs[i].record_stream(wk["stream"])
-        for wk in workers:
-            ev = torch.cuda.Event()
-            ev.record(wk["stream"])
-            main.wait_event(ev)
-        return outs
-
-    def _frame_workers(self, k: int, device):
-        import torch
-        ws = getattr(self, "_fworkers", None)
-        if ws is None:
-            ws = self._fworkers = []
-        while len(ws) < k:
-            eng = self._engine if not ws else self._engine.clone()
-            ws.append({"engine": eng, "stream": torch.cuda.Stream(device=device)})
-        return ws[:k]
+        if self._frame_pool is None:
+            self._frame_pool = StreamPool(self._engine, frames[0].device)
+        return self._frame_pool.fan_out([(f,) for f in frames], lambda eng, item, out: eng.denoise_device(item[0], out=out), k)
 
     def denoise_halo_frames(self, frames: Sequence[np.ndarray], count: int, head: bool) -> List[np.ndarray]:
         """The first/last ``count`` frames of this rank's block, denoised (tiled) but not yet temporally averaged —
@@ -597,11 +521,10 @@ class TAPDenoiser:
         return result
 
     def clear_cache(self) -> None:
-        for wk in (getattr(self, "_workers", None) or []) + (getattr(self, "_fworkers", None) or []):
-            if wk["engine"] is not self._engine:
-                wk["engine"].close()
-        self._workers = None
-        self._fworkers = None
+        for pool in (self._tile_pool, self._frame_pool):
+            if pool is not None:
+                pool.close()
+        self._tile_pool = self._frame_pool = None
         if self._engine is not None:
             self._engine.close()
             self._engine = None
