@@ -23,6 +23,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, check_stack, fetch, upload
 
 logger = logging.getLogger(__name__)
 
@@ -346,32 +347,28 @@ def _read_png_bgr(path: Path) -> Optional[np.ndarray]:
             return None
 
 
-class DeviceColorGrader:
+class DeviceColorGrader(Stage):
     """A LUT held on one GPU and applied to frames there.  3D LUTs of 2 .. 65 entries a side grade uint8 and uint16 frames; a 1D
     LUT grades uint8 frames through three byte tables.  ``bgr`` (default, OpenCV's order) says that channel 0 of a frame is blue."""
 
     def __init__(self, lut: LUT, device_id: int = 0, bgr: bool = True):
-        import torch
         check_finite(lut)
         self.lut = lut
         self.device_id = int(device_id)
         self.bgr = bool(bgr)
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self._dev = torch.device("cuda", self.device_id)
+        super().__init__(self.device_id)
         if lut.lut_type == LUTType.LUT_3D:
             table = lut.table_f32()
             self.size = int(table.shape[0])
             if table.shape != (self.size, self.size, self.size, 3) or not MIN_SIZE <= self.size <= MAX_SIZE:
                 raise ValueError(f"a 3D LUT of {MIN_SIZE} .. {MAX_SIZE} entries a side expected")
-            self._table = torch.from_numpy(table).to(self._dev)
+            self._table = upload(table, self._dev)
         else:
             self.size = 0
-            self._table = torch.from_numpy(byte_tables_1d(lut, self.bgr)).to(self._dev)
+            self._table = upload(byte_tables_1d(lut, self.bgr), self._dev)
 
     # ---- one launch ------------------------------------------------------------------------------------------------------------
     def _launch(self, src_ptr: int, src_stride: int, n: int, h: int, w: int, wide: bool, dst_ptr: int, dst_stride: int, dev) -> None:
-        import torch
         st = _lib.stream_ptr(dev)
         if self.size:
             fn = self._lib.fw_lut3d_apply_u16 if wide else self._lib.fw_lut3d_apply_u8
@@ -386,9 +383,8 @@ class DeviceColorGrader:
     @staticmethod
     def _check(t, dims: int):
         import torch
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != dims or t.shape[-1] != 3 or \
-                t.dtype not in (torch.uint8, torch.uint16, torch.int16):
-            raise ValueError("uint8 or uint16 (or int16 holding those bits) CUDA tensors [n x] H x W x 3 expected")
+        check_stack(t, dims, "uint8 or uint16 (or int16 holding those bits) CUDA tensors [n x] H x W x 3 expected",
+                    dtypes=(torch.uint8, torch.uint16, torch.int16))
         return t.dtype != torch.uint8
 
     def _clip(self, clip, inplace: bool):
@@ -444,15 +440,12 @@ class DeviceColorGrader:
     @_lib.on_tensor_device
     def apply(self, image: np.ndarray) -> np.ndarray:
         """Host in, host out: an H x W x 3 or n x H x W x 3 uint8 / uint16 array."""
-        import torch
         a = np.ascontiguousarray(image)
         if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (3, 4) or a.shape[-1] != 3:
             raise ValueError("apply expects a uint8 or uint16 array [n x] H x W x 3")
         wide = a.dtype == np.uint16
-        t = torch.from_numpy(a.view(np.int16) if wide else a).to(self._dev)          # the bytes only
-        out = self._clip(t if a.ndim == 4 else t.unsqueeze(0), True)
-        torch.cuda.current_stream(self._dev).synchronize()
-        res = out.cpu().numpy().reshape(a.shape)
+        t = upload(a.view(np.int16) if wide else a, self._dev)                        # the bytes only
+        res = fetch(self._dev, self._clip(t if a.ndim == 4 else t.unsqueeze(0), True)).reshape(a.shape)
         return res.view(np.uint16) if wide else res
 
     # ---- the reference's step 7c ---------------------------------------------------------------------------------------------------

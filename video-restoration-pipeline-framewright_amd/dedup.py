@@ -24,6 +24,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, check_stack, fetch, upload
 
 logger = logging.getLogger(__name__)
 
@@ -118,7 +119,7 @@ def _bits_to_hex(row: bytes, hash_size: int) -> str:
     return format(int.from_bytes(row, "big"), "0%dx" % ((hash_size * hash_size + 3) // 4))
 
 
-class DeviceFrameDeduplicator:
+class DeviceFrameDeduplicator(Stage):
     """The reference's `FrameDeduplicator` with the hashes formed on one GPU.  ``imagehash_available`` selects the hash the
     reference would take: None probes the import as the reference does."""
 
@@ -127,7 +128,7 @@ class DeviceFrameDeduplicator:
         self.gpu_id = int(gpu_id)
         self.imagehash_available = _imagehash_importable() if imagehash_available is None else bool(imagehash_available)
         self._hash_cache: Dict[Path, str] = {}
-        self._lib = _lib.load()                # the directory methods that only copy files need no GPU; the hashes do
+        super().__init__(self.gpu_id, needs_gpu=False)     # the directory methods that only copy files need no GPU; the hashes do
 
     @property
     def perceptual(self) -> bool:
@@ -137,7 +138,7 @@ class DeviceFrameDeduplicator:
     def _thumbs(self, ptr: int, stride: int, n: int, h: int, w: int, out_w: int, out_h: int, gray_first: bool, dev):
         """Enqueue the thumbnails of n frames on torch's current stream of `dev`; returns the n x out_h x out_w device tensor."""
         import torch
-        _lib.require_gpu()
+        self.gpu_device()                      # the refusal of a machine without a GPU, put off by the constructor
         thumbs = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev)
         ws = torch.empty(max(1, self._lib.fw_pil_thumb_workspace_bytes(n, h, w, out_w, out_h, int(gray_first))), dtype=torch.uint8, device=dev)
         _lib.check(self._lib.fw_pil_thumb_u8(C.c_void_p(ptr), stride, n, h, w, out_w, out_h, int(gray_first), _lib.ptr(thumbs),
@@ -148,18 +149,15 @@ class DeviceFrameDeduplicator:
         import torch
         n, h, w = (int(v) for v in clip.shape[:3])
         dev = clip.device
-        stream = torch.cuda.current_stream(dev)
         if self.perceptual:
             hs = int(self.config.hash_size)
             thumbs = self._thumbs(clip.data_ptr(), h * w * 3, n, h, w, hs + 1, hs, True, dev)
             bits = torch.empty((n, (hs * hs + 7) // 8), dtype=torch.uint8, device=dev)
-            _lib.check(self._lib.fw_dhash_pack_u8(_lib.ptr(thumbs), n, hs, _lib.ptr(bits), C.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            return [_bits_to_hex(row.tobytes(), hs) for row in bits.cpu().numpy()]
+            _lib.check(self._lib.fw_dhash_pack_u8(_lib.ptr(thumbs), n, hs, _lib.ptr(bits), _lib.stream_ptr(dev)))
+            return [_bits_to_hex(row.tobytes(), hs) for row in fetch(dev, bits)]
         thumbs = self._thumbs(clip.data_ptr(), h * w * 3, n, h, w, PIXEL_THUMB, PIXEL_THUMB, False, dev)
-        stream.synchronize()
         rate = int(self.config.pixel_sample_rate)
-        return [hashlib.md5(t.reshape(-1)[::rate].tobytes()).hexdigest() for t in thumbs.cpu().numpy()]
+        return [hashlib.md5(t.reshape(-1)[::rate].tobytes()).hexdigest() for t in fetch(dev, thumbs)]
 
     @_lib.on_tensor_device
     def hashes_device(self, frames) -> List[str]:
@@ -168,13 +166,11 @@ class DeviceFrameDeduplicator:
         The MD5 of the pixel hash is computed on the host."""
         import torch
         if isinstance(frames, torch.Tensor):
-            if frames.dtype != torch.uint8 or not frames.is_cuda or frames.dim() != 4 or frames.shape[-1] != 3:
-                raise ValueError("hashes_device expects a uint8 CUDA tensor n x H x W x 3")
+            check_stack(frames, 4, "hashes_device expects a uint8 CUDA tensor n x H x W x 3")
             return self._hashes_of_clip(frames.contiguous()) if frames.shape[0] else []
         frames = list(frames)
         for f in frames:
-            if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or not f.is_cuda or f.dim() != 3 or f.shape[-1] != 3:
-                raise ValueError("hashes_device expects uint8 CUDA tensors H x W x 3")
+            check_stack(f, 3, "hashes_device expects uint8 CUDA tensors H x W x 3")
         if not frames:
             return []
         if all(f.shape == frames[0].shape and f.device == frames[0].device for f in frames):
@@ -201,7 +197,6 @@ class DeviceFrameDeduplicator:
                        block: int = 16) -> DeduplicationResult:
         """`frame_*.png` of a directory, sorted: each file is decoded once, 8-bit RGB frames are uploaded and hashed `block` at a
         time, anything else is hashed on the host.  Hashes are kept by path, so a second call decodes nothing."""
-        import torch
         from PIL import Image
         frames_dir = Path(frames_dir)
         files = sorted(frames_dir.glob("frame_*.png"))
@@ -210,7 +205,6 @@ class DeviceFrameDeduplicator:
             logger.warning(f"No frames found in {frames_dir}")
             return DeduplicationResult()
         logger.info(f"Analyzing {total} frames for duplicates...")
-        dev = torch.device("cuda", self.gpu_id)
         pending: List[Tuple[Path, np.ndarray]] = []
 
         def flush():
@@ -218,7 +212,7 @@ class DeviceFrameDeduplicator:
             while pending:
                 shape = pending[0][1].shape
                 run = [p for p in pending if p[1].shape == shape]
-                clip = torch.from_numpy(np.stack([a for _, a in run])).to(dev)
+                clip = upload(np.stack([a for _, a in run]), self._dev)
                 for (path, _), h in zip(run, self.hashes_device(clip)):
                     self._hash_cache[path] = h
                 pending[:] = [p for p in pending if p[1].shape != shape]

@@ -18,10 +18,12 @@ from typing import Any, Callable, Dict, Iterable, Iterator, List, Optional, Sequ
 import numpy as np
 
 from . import _lib
+from ._stage import ANY, Stage, check_frame_list, check_no_overlap, check_out, contiguous
 
 logger = logging.getLogger(__name__)
 
 FW_DEINTERLACE_YADIF, FW_DEINTERLACE_BWDIF, FW_DEINTERLACE_BOB = 0, 1, 2
+_BOUNDS = ((1, ANY, 1, ANY, "empty frames"),)
 
 
 class DeinterlaceMethod(Enum):
@@ -105,50 +107,24 @@ class InterlaceAnalysis:
                 f"Recommended: {self.recommended_method.value.upper()}")
 
 
-def _storage_range(t):
-    """[first byte, last byte + 1) of the storage a uint8 tensor's elements lie in."""
-    span = 1 + sum((int(s) - 1) * int(st) for s, st in zip(t.shape, t.stride())) if t.numel() else 0
-    return t.data_ptr(), t.data_ptr() + span
-
-
-def _check_no_overlap(dsts, srcs) -> None:
-    marks = sorted([(*_storage_range(t), 0) for t in dsts] + [(*_storage_range(t), 1) for t in srcs])
-    end = [0, 0]                                     # furthest end so far of destinations / of sources
-    for lo, hi, kind in marks:
-        if hi > lo and lo < end[1 - kind]:
-            raise ValueError("deinterlace: a destination overlaps a source frame (rebuilt rows are read as neighbours)")
-        end[kind] = max(end[kind], hi)
-
-
-class DeviceDeinterlacer:
+class DeviceDeinterlacer(Stage):
     """The reference's `Deinterlacer` on uint8 CUDA frames of one GPU.  Work is queued on torch's current stream of the frames'
     device; the analysis entries synchronise once per batch of statistics."""
 
     def __init__(self, config: Optional[InterlaceConfig] = None, device_id: int = 0):
         self.config = config or InterlaceConfig()
         self.device_id = int(device_id)
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(self.device_id)
 
     # ---- device entries ----------------------------------------------------------------------------------------------------------
     @staticmethod
     def _check_frames(frames) -> tuple:
-        import torch
-        f0 = frames[0]
-        for f in frames:
-            if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8 or f.dim() not in (2, 3) or \
-                    (f.dim() == 3 and f.shape[2] != 3) or f.shape != f0.shape or f.device != f0.device:
-                raise ValueError("uint8 CUDA tensors H x W x 3 (BGR) or H x W of one shape on one device expected")
-        h, w = int(f0.shape[0]), int(f0.shape[1])
-        if h < 1 or w < 1:
-            raise ValueError("empty frames")
-        return h, w, (3 if f0.dim() == 3 else 1)
+        return check_frame_list(frames, "uint8 CUDA tensors H x W x 3 (BGR) or H x W of one shape on one device expected", _BOUNDS)
 
     @staticmethod
     def _check_out(out, numel: int, dev) -> None:
         import torch
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.device != dev or out.numel() != numel or not out.is_contiguous():
-            raise ValueError(f"a contiguous int64 tensor of {numel} elements on {dev} expected")
+        check_out(out, f"a contiguous int64 tensor of {numel} elements on {dev} expected", torch.int64, dev, numel=numel)
 
     @_lib.on_tensor_device
     def interpolate_device(self, frames: Sequence, mode: int, parity: int, prev=None, nxt=None, batched: bool = True,
@@ -163,7 +139,7 @@ class DeviceDeinterlacer:
         if not frames:
             return []
         h, w, c = self._check_frames(frames + [t for t in (prev, nxt) if t is not None])
-        frames = [f if f.is_contiguous() else f.contiguous() for f in frames]
+        frames = contiguous(frames)
         prev = prev if prev is None or prev.is_contiguous() else prev.contiguous()
         nxt = nxt if nxt is None or nxt.is_contiguous() else nxt.contiguous()
         if mode == FW_DEINTERLACE_BOB and h < 2:
@@ -178,7 +154,7 @@ class DeviceDeinterlacer:
             self._check_frames(frames + outs)
         prevs = [frames[i - 1] if i > 0 else (prev if prev is not None else frames[i]) for i in range(n)]
         nexts = [frames[i + 1] if i < n - 1 else (nxt if nxt is not None else frames[i]) for i in range(n)]
-        _check_no_overlap(outs, frames + [t for t in (prev, nxt) if t is not None])
+        check_no_overlap(outs, frames + [t for t in (prev, nxt) if t is not None], "deinterlace")
         st = _lib.stream_ptr(frames[0].device)
         if batched:
             table = _lib.ptr_table([t for task in zip(frames, prevs, nexts, outs) for t in task])   # n x {cur, prev, next, dst}
@@ -197,7 +173,7 @@ class DeviceDeinterlacer:
         import torch
         frames = list(frames)
         h, w, c = self._check_frames(frames)
-        frames = [f if f.is_contiguous() else f.contiguous() for f in frames]
+        frames = contiguous(frames)
         if out is None:
             out = torch.empty((len(frames), 4), dtype=torch.int64, device=frames[0].device)
         self._check_out(out, 4 * len(frames), frames[0].device)
@@ -212,8 +188,7 @@ class DeviceDeinterlacer:
         if len(a) != len(b):
             raise ValueError("as many frames in a as in b expected")
         h, w, c = self._check_frames(a + b)
-        a = [f if f.is_contiguous() else f.contiguous() for f in a]
-        b = [f if f.is_contiguous() else f.contiguous() for f in b]
+        a, b = contiguous(a), contiguous(b)
         if out is None:
             out = torch.empty((len(a),), dtype=torch.int64, device=a[0].device)
         self._check_out(out, len(a), a[0].device)

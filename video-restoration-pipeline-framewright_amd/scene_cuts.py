@@ -9,30 +9,27 @@ tests/scene_cut_ref.py is the contract of the two kernels.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List
 
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, check_stack, fetch
 
 SSIM_WINDOW = 7
 
 
-class DeviceSceneCutDetector:
+class DeviceSceneCutDetector(Stage):
     """The scene-cut tests of `policy.scene_change` on one GPU.  Every method takes uint8 CUDA tensors (H x W x 3, or n x H x W x 3
     for a clip), enqueues on torch's current stream of the tensors' device, waits for that stream and returns host values."""
 
     def __init__(self, gpu_id: int = 0):
         self.gpu_id = int(gpu_id)
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(self.gpu_id)
 
     @staticmethod
     def _check(t, dims: int, what: str):
-        import torch
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != dims or t.shape[-1] != 3:
-            raise ValueError(f"{what} expects uint8 CUDA tensors {'n x ' if dims == 4 else ''}H x W x 3")
+        check_stack(t, dims, f"{what} expects uint8 CUDA tensors {'n x ' if dims == 4 else ''}H x W x 3")
         return t.contiguous()
 
     def _ssim(self, a, b, stride: int, pairs: int, h: int, w: int) -> List[float]:
@@ -40,10 +37,8 @@ class DeviceSceneCutDetector:
         dev = a.device
         out = torch.empty(pairs, dtype=torch.float64, device=dev)
         ws = torch.empty(max(1, self._lib.fw_scene_ssim_workspace_bytes(pairs, h, w) // 8), dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        _lib.check(self._lib.fw_scene_ssim_u8(_lib.ptr(a), _lib.ptr(b), stride, pairs, h, w, _lib.ptr(out), _lib.ptr(ws), C.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
-        return out.cpu().tolist()
+        _lib.check(self._lib.fw_scene_ssim_u8(_lib.ptr(a), _lib.ptr(b), stride, pairs, h, w, _lib.ptr(out), _lib.ptr(ws), _lib.stream_ptr(dev)))
+        return fetch(dev, out).tolist()
 
     @_lib.on_tensor_device
     def ssim_pairs_device(self, frames) -> List[float]:
@@ -72,10 +67,8 @@ class DeviceSceneCutDetector:
             raise ValueError("histograms_device expects at least one non-empty frame")
         dev = frames.device
         hist = torch.empty((n, 3, 64), dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        _lib.check(self._lib.fw_hist64x3_u8(_lib.ptr(frames), n, h, w, _lib.ptr(hist), C.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
-        return hist.cpu().numpy().view(np.uint32).astype(np.int64)
+        _lib.check(self._lib.fw_hist64x3_u8(_lib.ptr(frames), n, h, w, _lib.ptr(hist), _lib.stream_ptr(dev)))
+        return fetch(dev, hist).view(np.uint32).astype(np.int64)
 
     @staticmethod
     def histogram_decision(h1: np.ndarray, h2: np.ndarray, scene_threshold: float = 0.3) -> bool:

@@ -48,6 +48,7 @@ from typing import Any, Callable, Dict, Iterator, List, Optional, Sequence, Tupl
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, check_out, check_stack, fetch, upload
 
 
 @dataclass
@@ -104,7 +105,7 @@ def _percentile_sorted(srt, q: float):
     return a + d * float(t)
 
 
-class DeviceFlowEstimator:
+class DeviceFlowEstimator(Stage):
     """`OpticalFlowEstimator` (temporal_denoise.py:211-477) on one GPU: Farneback dense optical flow (fw_farneback_flow_u8), magnitude,
     local-variance confidence (fw_flow_stats_f32, fw_flow_confidence_f32).  RAFT and RIFE run Farneback, as the reference's `else`
     branch does (:311-315); DIS and LUCAS_KANADE are not built and raise NotImplementedError.
@@ -134,13 +135,7 @@ class DeviceFlowEstimator:
             raise TypeError(f"unknown Farneback parameter(s): {sorted(unknown)}")
         self.method, self.gpu_id = method, int(gpu_id)
         self.params = {**FARNEBACK_PARAMS, **farneback_params}
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self._scratch = None
-
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.gpu_id)
+        super().__init__(self.gpu_id)
 
     @staticmethod
     def _load(frame) -> np.ndarray:
@@ -153,11 +148,7 @@ class DeviceFlowEstimator:
         return frame
 
     def _scratch_for(self, h: int, w: int, dev):
-        import torch
-        need = int(self._lib.fw_farneback_scratch_bytes(h, w, int(self.params["levels"])))
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._scratch
+        return self.scratch(int(self._lib.fw_farneback_scratch_bytes(h, w, int(self.params["levels"]))), dev)
 
     @_lib.on_tensor_device
     def flow_device(self, t1, t2):
@@ -192,8 +183,7 @@ class DeviceFlowEstimator:
         h, w = int(fx.shape[0]), int(fx.shape[1])
         mag, var, conf = torch.empty_like(fx), torch.empty_like(fx), torch.empty_like(fx)
         wm = torch.empty_like(fx) if weight_map else None
-        st = _lib.stream_ptr(dev)
-        p = lambda t: _lib.ptr(t) if t is not None else None
+        st, p = _lib.stream_ptr(dev), _lib.ptr
         _lib.check(self._lib.fw_flow_stats_f32(p(fx), p(fy), h, w, p(mag), p(var), st))
         # the two order statistics are plumbing: a device sort each (torch.quantile refuses inputs of this size), index arithmetic on the host
         p95 = _percentile_sorted(torch.sort(var.reshape(-1)).values, 95)
@@ -208,13 +198,9 @@ class DeviceFlowEstimator:
     def estimate(self, frame1: Union[np.ndarray, str, Path], frame2: Union[np.ndarray, str, Path]) -> FlowField:
         """`OpticalFlowEstimator.estimate` (:261-332): numpy frames or image paths in, a numpy FlowField (fp32 maps) out - the field by
         which `warp_frame(frame1, .)` brings `frame1` onto `frame2` (`convention="cv2"`: the reference's cv2 call, (frame1, frame2))."""
-        import torch
-        dev = self._dev()
         a, b = self._load(frame1), self._load(frame2)
-        with torch.cuda.device(dev):
-            maps = self.maps_device(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev))
-            torch.cuda.current_stream(dev).synchronize()
-            fx, fy, mag, conf = (m.cpu().numpy() for m in maps)
+        with self.host() as dev:
+            fx, fy, mag, conf = fetch(dev, *self.maps_device(upload(a, dev), upload(b, dev)))
         return FlowField(flow_x=fx, flow_y=fy, magnitude=mag, confidence=conf, frame_idx_from=0, frame_idx_to=1)
 
     def warp_frame(self, frame: np.ndarray, flow: FlowField, inverse: bool = False) -> np.ndarray:
@@ -222,7 +208,7 @@ class DeviceFlowEstimator:
         return DeviceTemporalAccumulator(gpu_id=self.gpu_id).warp_frame(frame, flow, inverse=inverse)
 
 
-class DeviceSpatialDenoiser:
+class DeviceSpatialDenoiser(Stage):
     """`TemporalDenoiser._apply_spatial_denoise` (temporal_denoise.py:1611-1634) on one GPU: non-local means on the Lab planes of a
     BGR frame (fw_nlmeans_colored_u8), and the plain core on a 1-, 2- or 3-channel plane (fw_nlmeans_u8).  The windows are the
     reference's (7, 21); the kernels take a template window of 3, 5 or 7 and an odd search window of 3 .. 41, and even sizes are
@@ -230,13 +216,7 @@ class DeviceSpatialDenoiser:
 
     def __init__(self, gpu_id: int = 0, template_window: int = 7, search_window: int = 21):
         self.gpu_id, self.template_window, self.search_window = int(gpu_id), int(template_window), int(search_window)
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self._scratch = None
-
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.gpu_id)
+        super().__init__(self.gpu_id)
 
     @staticmethod
     def h_for_strength(strength: float) -> int:
@@ -244,13 +224,10 @@ class DeviceSpatialDenoiser:
         return int(3 + strength * 7)
 
     def _scratch_for(self, h: int, w: int, dev):
-        import torch
         need = int(self._lib.fw_nlmeans_scratch_bytes(h, w, self.search_window))
         if need <= 0:
             raise ValueError(f"non-local means: bad frame size {h} x {w} or search window {self.search_window}")
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._scratch
+        return self.scratch(need, dev)
 
     @_lib.on_tensor_device
     def denoise_device(self, t, h: float, h_color: Optional[float] = None):
@@ -258,8 +235,7 @@ class DeviceSpatialDenoiser:
         device tensor; `t` is left untouched, nothing is fetched and nothing waits for the device.  h_color defaults to h, the
         reference's call."""
         import torch
-        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_cuda:
-            raise ValueError("the spatial denoise expects a uint8 BGR (H x W x 3) device frame")
+        check_stack(t, 3, "the spatial denoise expects a uint8 BGR (H x W x 3) device frame", test_type=False)
         t = t.contiguous()
         dev = t.device
         hh, ww = int(t.shape[0]), int(t.shape[1])
@@ -289,18 +265,14 @@ class DeviceSpatialDenoiser:
 
     def denoise(self, frame: np.ndarray, strength: float) -> np.ndarray:
         """`_apply_spatial_denoise(frame, strength)`: numpy uint8 BGR in and out."""
-        import torch
         frame = np.ascontiguousarray(frame)
         if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
             raise ValueError("the spatial denoise expects a uint8 BGR (H x W x 3) frame")
-        dev = self._dev()
-        with torch.cuda.device(dev):
-            out = self.denoise_device(torch.from_numpy(frame).to(dev), self.h_for_strength(strength))
-            torch.cuda.current_stream(dev).synchronize()
-            return out.cpu().numpy()
+        with self.host() as dev:
+            return fetch(dev, self.denoise_device(upload(frame, dev), self.h_for_strength(strength)))
 
 
-class DeviceTemporalAccumulator:
+class DeviceTemporalAccumulator(Stage):
     """The float64 accumulate of `_denoise_with_flow` / `_denoise_simple` on one GPU.
 
     flow_fn: a host estimator, `flow_fn(frame, center) -> FlowField` (e.g. cv2's); its maps are uploaded per neighbour.
@@ -312,25 +284,20 @@ class DeviceTemporalAccumulator:
                  flow_estimator: Optional[DeviceFlowEstimator] = None):
         if flow_fn is not None and flow_estimator is not None:
             raise ValueError("pass flow_fn (a host estimator) or flow_estimator (a DeviceFlowEstimator), not both")
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(gpu_id)
         self.decay, self.gpu_id = float(temporal_weight_decay), int(gpu_id)
         self.flow_fn = flow_fn or _default_flow_fn
         self.flow_estimator = flow_estimator
         self._spatial = None
 
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.gpu_id)
-
     def warp_frame(self, frame: np.ndarray, flow: FlowField, inverse: bool = False) -> np.ndarray:
         """`OpticalFlowEstimator.warp_frame`: cv2.remap(frame, grid +/- flow, INTER_LINEAR, BORDER_REFLECT_101)."""
         import torch
-        dev = self._dev()
+        dev = self._dev
         h, w = frame.shape[:2]
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
-        self._accumulate(torch.from_numpy(np.ascontiguousarray(frame)).to(dev), flow, 1.0, None, None, inverse, acc, ws)
+        self._accumulate(upload(frame, dev), flow, 1.0, None, None, inverse, acc, ws)
         return self._finish(acc, ws)
 
     @_lib.on_tensor_device
@@ -339,9 +306,9 @@ class DeviceTemporalAccumulator:
         dev = acc.device
         h, w = int(acc.shape[0]), int(acc.shape[1])
         st = _lib.stream_ptr(dev)
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        f32 = lambda a: upload(np.asarray(a, dtype=np.float32), dev)
         keep = []
-        p = lambda t: _lib.ptr(t) if t is not None else None
+        p = _lib.ptr
         fx = fy = mg = wm = None
         if flow is not None:
             fx, fy = f32(flow.flow_x), f32(flow.flow_y)
@@ -370,10 +337,10 @@ class DeviceTemporalAccumulator:
     def denoise_with_flow(self, center_local_idx: int, window: Sequence[np.ndarray]) -> np.ndarray:
         """`_denoise_with_flow` (temporal_denoise.py:1521-1580) for the frames of one window."""
         import torch
-        dev = self._dev()
+        dev = self._dev
         if self.flow_estimator is not None:
-            with torch.cuda.device(dev):
-                out = self._window_device(center_local_idx, [torch.from_numpy(np.ascontiguousarray(f)).to(dev) for f in window])
+            with self.host():
+                out = self._window_device(center_local_idx, [upload(f, dev) for f in window])
                 torch.cuda.synchronize(dev)
             return out.cpu().numpy()
         center = window[center_local_idx]
@@ -382,7 +349,7 @@ class DeviceTemporalAccumulator:
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
         for local_i, frame in enumerate(window):
             distance = abs(local_i - center_local_idx)
-            fd = torch.from_numpy(np.ascontiguousarray(frame)).to(dev)
+            fd = upload(frame, dev)
             if distance == 0:
                 self._accumulate(fd, None, 1.0, None, None, False, acc, ws)
                 continue
@@ -405,8 +372,7 @@ class DeviceTemporalAccumulator:
         h, w = int(center.shape[0]), int(center.shape[1])
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
-        st = _lib.stream_ptr(dev)
-        p = lambda t: _lib.ptr(t) if t is not None else None
+        st, p = _lib.stream_ptr(dev), _lib.ptr
         for local_i, fd in enumerate(frames_dev):
             distance = abs(local_i - center_local_idx)
             fx = fy = wm = None
@@ -462,7 +428,7 @@ class DeviceTemporalAccumulator:
         frames = list(frames)
         n = len(frames)
         spatial, cuts = self._check_sequence_args(n, temporal_radius, noise_strength, scene_changes)
-        dev = self._dev()
+        dev = self._dev
         if self.flow_estimator is None:
             for i in range(n):
                 lo, hi = (i, i + 1) if i in cuts else (max(0, i - temporal_radius), min(n, i + temporal_radius + 1))
@@ -471,11 +437,11 @@ class DeviceTemporalAccumulator:
                     out = self._spatial_denoiser().denoise(out, noise_strength)
                 yield self.preserve_edges(frames[i], out, edge_threshold) if preserve_edges else out
             return
-        with torch.cuda.device(dev):
-            devs = [torch.from_numpy(np.ascontiguousarray(f)).to(dev) for f in frames]
+        with self.host():
+            devs = [upload(f, dev) for f in frames]
         for i in range(n):
             lo, hi = (i, i + 1) if i in cuts else (max(0, i - temporal_radius), min(n, i + temporal_radius + 1))
-            with torch.cuda.device(dev):
+            with self.host():
                 out = self._chain_device(i - lo, devs[lo:hi], noise_strength if spatial else None, preserve_edges, edge_threshold)
                 torch.cuda.synchronize(dev)
                 res = out.cpu().numpy()
@@ -487,21 +453,21 @@ class DeviceTemporalAccumulator:
         """One frame of the reference's chain (:1499-1511) on a window of uint8 BGR device frames -> the uint8 device result:
         accumulate (`_denoise_simple`'s weights with `simple`), the spatial denoise when `spatial_strength` is given, the edge
         preserve against the window's centre frame.  Only launches, apart from the edge mask's hysteresis (fw_preserve_edges_u8)."""
-        import torch
         center = window_dev[center_local_idx]
-        dev = center.device
         out = self._window_simple_device(window_dev) if simple else self._window_device(center_local_idx, window_dev)
         if spatial_strength is not None:
             out = self._spatial_denoiser().denoise_device(out, DeviceSpatialDenoiser.h_for_strength(spatial_strength))
-        if preserve_edges:
-            h, w = int(out.shape[0]), int(out.shape[1])
-            scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
-            blended = torch.empty_like(out)
-            st = _lib.stream_ptr(dev)
-            _lib.check(self._lib.fw_preserve_edges_u8(_lib.ptr(center), _lib.ptr(out), h, w,
-                                                      float(edge_threshold), float(edge_threshold * 3),
-                                                      _lib.ptr(scratch), _lib.ptr(blended), st))
-            out = blended
+        return self._preserve_edges_device(center, out, edge_threshold) if preserve_edges else out
+
+    def _preserve_edges_device(self, original, denoised, edge_threshold: int):
+        """`_preserve_edges` on two uint8 BGR device frames of one size -> a new device frame; the device is current."""
+        import torch
+        h, w = int(denoised.shape[0]), int(denoised.shape[1])
+        scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=denoised.device)
+        out = torch.empty_like(denoised)
+        _lib.check(self._lib.fw_preserve_edges_u8(_lib.ptr(original), _lib.ptr(denoised), h, w, float(edge_threshold),
+                                                  float(edge_threshold * 3), _lib.ptr(scratch), _lib.ptr(out),
+                                                  _lib.stream_ptr(denoised.device)))
         return out
 
     @_lib.on_tensor_device
@@ -531,17 +497,8 @@ class DeviceTemporalAccumulator:
         if original.shape != denoised.shape or original.dtype != np.uint8 or denoised.dtype != np.uint8 or original.ndim != 3 or \
                 original.shape[2] != 3:
             raise ValueError("preserve_edges expects two uint8 BGR frames of one size")
-        dev = self._dev()
-        h, w = original.shape[:2]
-        with torch.cuda.device(dev):
-            o = torch.from_numpy(np.ascontiguousarray(original)).to(dev)
-            d = torch.from_numpy(np.ascontiguousarray(denoised)).to(dev)
-            scratch = torch.empty(int(self._lib.fw_preserve_edges_scratch_bytes(h, w)), dtype=torch.uint8, device=dev)
-            out = torch.empty_like(o)
-            st = _lib.stream_ptr(dev)
-            _lib.check(self._lib.fw_preserve_edges_u8(_lib.ptr(o), _lib.ptr(d), h, w, float(edge_threshold),
-                                                      float(edge_threshold * 3), _lib.ptr(scratch),
-                                                      _lib.ptr(out), st))
+        with self.host() as dev:
+            out = self._preserve_edges_device(upload(original, dev), upload(denoised, dev), edge_threshold)
             torch.cuda.synchronize(dev)
         return out.cpu().numpy()
 
@@ -549,14 +506,13 @@ class DeviceTemporalAccumulator:
         """`_denoise_simple` (temporal_denoise.py:1582-1605).  The reference divides by a scalar weight sum; per-pixel sums
         of the same scalars give the same float64 quotient."""
         import torch
-        dev = self._dev()
+        dev = self._dev
         h, w = window[0].shape[:2]
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
         center_idx = len(window) // 2
         for i, frame in enumerate(window):
-            self._accumulate(torch.from_numpy(np.ascontiguousarray(frame)).to(dev), None, math.exp(-abs(i - center_idx) * self.decay),
-                             None, None, False, acc, ws)
+            self._accumulate(upload(frame, dev), None, math.exp(-abs(i - center_idx) * self.decay), None, None, False, acc, ws)
         return self._finish(acc, ws)
 
 
@@ -748,7 +704,7 @@ def _check_clip(frames) -> List[np.ndarray]:
     return frames
 
 
-class DeviceClipAnalyzer:
+class DeviceClipAnalyzer(Stage):
     """Phase 1 of the reference, `TemporalDenoiser.analyze` (temporal_denoise.py:1110-1300), with the per-frame work on one GPU:
     fw_frame_stats_u8 reads a resident batch of frames once and leaves 256 histogram bins and two integer sums per frame; the
     pure host functions above turn those into the reference's `analysis` dict.  Only the frames the reference samples are uploaded
@@ -761,20 +717,14 @@ class DeviceClipAnalyzer:
     def __init__(self, config: Optional[TemporalDenoiseConfig] = None):
         self.config = config or TemporalDenoiseConfig()
         self.gpu_id = int(self.config.gpu_id)
-        self._lib = _lib.load()
-        _lib.require_gpu()
-
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.gpu_id)
+        super().__init__(self.gpu_id)
 
     @_lib.on_tensor_device
     def stats_device(self, clip_u8) -> Tuple[np.ndarray, np.ndarray]:
         """(hist [count][256] uint32, sums [count][2] int64 = sum lap, sum lap^2) of a uint8 count x H x W x 3 BGR device tensor: one
         launch for the whole batch, one wait, one download of count x 258 words."""
         import torch
-        if clip_u8.dtype != torch.uint8 or clip_u8.dim() != 4 or clip_u8.shape[3] != 3 or not clip_u8.is_cuda or clip_u8.shape[0] < 1:
-            raise ValueError("frame statistics expect a uint8 count x H x W x 3 BGR device tensor")
+        check_stack(clip_u8, 4, "frame statistics expect a uint8 count x H x W x 3 BGR device tensor", min_count=1, test_type=False)
         clip_u8 = clip_u8.contiguous()
         dev = clip_u8.device
         count, h, w = (int(v) for v in clip_u8.shape[:3])
@@ -782,19 +732,17 @@ class DeviceClipAnalyzer:
         st = _lib.stream_ptr(dev)
         _lib.check(self._lib.fw_frame_stats_u8(_lib.ptr(clip_u8), count, h, w, _lib.ptr(buf),
                                                C.c_void_p(buf.data_ptr() + count * 1024), st))
-        torch.cuda.current_stream(dev).synchronize()
-        host = buf.cpu().numpy()
+        host = fetch(dev, buf)
         return host[:count * 128].view(np.uint32).reshape(count, 256).copy(), host[count * 128:].reshape(count, 2).copy()
 
     def frame_stats(self, frames: Sequence[np.ndarray]):
         """`stats_device` of host frames, uploaded `config.chunk_size` at a time -> (hist, sums) over all of them."""
-        import torch
         frames = _check_clip(frames)
-        dev, step = self._dev(), int(self.config.chunk_size)
+        step = int(self.config.chunk_size)
         hists, sums = [np.zeros((0, 256), np.uint32)], [np.zeros((0, 2), np.int64)]
         for s in range(0, len(frames), step):
-            with torch.cuda.device(dev):
-                hs, ss = self.stats_device(torch.from_numpy(np.stack(frames[s:s + step])).to(dev))
+            with self.host() as dev:
+                hs, ss = self.stats_device(upload(np.stack(frames[s:s + step]), dev))
             hists.append(hs)
             sums.append(ss)
         return np.concatenate(hists), np.concatenate(sums)
@@ -834,7 +782,7 @@ class DeviceClipAnalyzer:
         return analysis
 
 
-class DeviceFlickerReducer:
+class DeviceFlickerReducer(Stage):
     """`FlickerReducer` (temporal_denoise.py:480-836) on one GPU, on the reference's Python path `_apply_python_deflicker`
     (:764-836); the ffmpeg `deflicker` filter it tries first is not built, so this path is the behaviour, not the fallback.
 
@@ -852,13 +800,8 @@ class DeviceFlickerReducer:
         self.mode, self.preserve_brightness_changes = FlickerMode(mode), bool(preserve_brightness_changes)
         self.gpu_id, self.chunk_size = int(gpu_id), int(chunk_size)
         self._detected_severity: Optional[float] = None
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(self.gpu_id)
         self._analyzer = DeviceClipAnalyzer(TemporalDenoiseConfig(gpu_id=self.gpu_id, chunk_size=max(10, self.chunk_size)))
-
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.gpu_id)
 
     def analyze_flicker(self, frames: Sequence[np.ndarray], sample_rate: int = 1, max_samples: int = 200) -> Dict[str, Any]:
         """`analyze_flicker` (:518-625) of a clip of uint8 BGR frames; only the sampled frames are uploaded.  The severity is
@@ -905,20 +848,19 @@ class DeviceFlickerReducer:
         """One batch: a uint8 count x H x W x 3 BGR device tensor -> the deflickered batch (`out`, which may be `batch` itself, or a
         new tensor).  One wait (the L sums), one upload of count x 256 bytes, two launches."""
         import torch
-        if batch.dtype != torch.uint8 or batch.dim() != 4 or batch.shape[3] != 3 or not batch.is_cuda or batch.shape[0] < 1:
-            raise ValueError("flicker reduction expects a uint8 count x H x W x 3 BGR device tensor")
+        check_stack(batch, 4, "flicker reduction expects a uint8 count x H x W x 3 BGR device tensor", min_count=1, test_type=False)
         batch = batch.contiguous()
         dev = batch.device
         count, h, w = (int(v) for v in batch.shape[:3])
         if out is None:
             out = torch.empty_like(batch)
-        elif out.shape != batch.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-            raise ValueError("flicker reduction: `out` must be a contiguous uint8 device tensor of the batch's shape")
+        else:
+            check_out(out, "flicker reduction: `out` must be a contiguous uint8 device tensor of the batch's shape", torch.uint8, dev,
+                      shape=batch.shape, test_type=False)
         sums = torch.empty(count, dtype=torch.int64, device=dev)
         st = _lib.stream_ptr(dev)
         _lib.check(self._lib.fw_lab_l_sums_u8(_lib.ptr(batch), count, h, w, _lib.ptr(sums), st))
-        torch.cuda.current_stream(dev).synchronize()
-        luts = torch.from_numpy(self.l_luts(sums.cpu().numpy().tolist(), h * w, target)).to(dev)
+        luts = upload(self.l_luts(fetch(dev, sums).tolist(), h * w, target), dev)
         _lib.check(self._lib.fw_deflicker_lab_u8(_lib.ptr(batch), count, h, w, _lib.ptr(luts),
                                                  _lib.ptr(out), st))
         # `luts` is freed when this returns; the caching allocator hands the block out again on this stream only, behind the launch
@@ -947,24 +889,20 @@ class DeviceFlickerReducer:
     def reduce_flicker(self, frames: Sequence[np.ndarray]) -> Tuple[List[np.ndarray], Dict[str, Any]]:
         """The host form of `reduce_flicker` (:626-700): numpy frames in, (numpy frames, the reference's result dict) out.  The clip
         is uploaded `chunk_size` frames at a time; the target comes from the sampled frames only."""
-        import torch
         frames = _check_clip(frames)
         if not frames:
             return [], {"frames_processed": 0, "mode_used": None}
         mode = self.resolved_mode()
         target = self.target_brightness(frames)
-        dev = self._dev()
         out: List[np.ndarray] = []
         for s in range(0, len(frames), self.chunk_size):
-            with torch.cuda.device(dev):
-                batch = torch.from_numpy(np.stack(frames[s:s + self.chunk_size])).to(dev)
-                res = self.deflicker_batch_device(batch, target, out=batch)
-                torch.cuda.current_stream(dev).synchronize()
-                out += list(res.cpu().numpy())
+            with self.host() as dev:
+                batch = upload(np.stack(frames[s:s + self.chunk_size]), dev)
+                out += list(fetch(dev, self.deflicker_batch_device(batch, target, out=batch)))
         return out, {"success": True, "frames_processed": len(out), "method": "python_brightness_normalization", "mode_used": mode.value}
 
 
-class DeviceTemporalConsistencyFilter:
+class DeviceTemporalConsistencyFilter(Stage):
     """Phase 4 of the reference, `TemporalConsistencyFilter` (temporal_denoise.py:839-1061), on one GPU.
 
     Flow-guided form (`use_optical_flow` and more than one frame in the window, :955-1022): every neighbour is remapped onto the
@@ -982,13 +920,8 @@ class DeviceTemporalConsistencyFilter:
             raise ValueError(f"temporal_radius must be an int >= 0, got {temporal_radius!r}")
         self.strength, self.temporal_radius, self.use_optical_flow = float(strength), int(temporal_radius), bool(use_optical_flow)
         self.gpu_id = int(gpu_id)
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(self.gpu_id)
         self.flow_estimator = flow_estimator or (DeviceFlowEstimator(gpu_id=self.gpu_id) if self.use_optical_flow else None)
-
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.gpu_id)
 
     @_lib.on_tensor_device
     def apply_device(self, devs, i: int):
@@ -1003,8 +936,7 @@ class DeviceTemporalConsistencyFilter:
         h, w = int(center.shape[0]), int(center.shape[1])
         acc = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
         ws = torch.zeros((h, w), dtype=torch.float64, device=dev)
-        st = _lib.stream_ptr(dev)
-        p = lambda t: _lib.ptr(t) if t is not None else None
+        st, p = _lib.stream_ptr(dev), _lib.ptr
         guided = self.use_optical_flow and hi - lo > 1
         for j in range(lo, hi):
             tw = float(np.exp(-abs(j - i) * 0.5))
@@ -1031,11 +963,11 @@ class DeviceTemporalConsistencyFilter:
         output frame."""
         import torch
         frames = _check_clip(frames)
-        dev = self._dev()
-        with torch.cuda.device(dev):
-            devs = [torch.from_numpy(f).to(dev) for f in frames]
+        dev = self._dev
+        with self.host():
+            devs = [upload(f, dev) for f in frames]
         for i in range(len(frames)):
-            with torch.cuda.device(dev):
+            with self.host():
                 out = self.apply_device(devs, i)
                 torch.cuda.synchronize(dev)
                 res = out.cpu().numpy()
@@ -1114,7 +1046,7 @@ class DeviceTemporalDenoiser:
         cuts = {i for i in self._scene_changes if i < n}
         r, step = c.temporal_radius, c.chunk_size
         spatial = c.noise_strength if c.noise_strength > DeviceTemporalAccumulator.SPATIAL_THRESHOLD else None
-        dev = self._analyzer._dev()
+        dev = self._analyzer._dev
         inputs: Dict[int, Any] = {}       # resident input frames
         denoised: Dict[int, Any] = {}     # resident phase-3 results
         outputs: List[np.ndarray] = []
@@ -1128,9 +1060,9 @@ class DeviceTemporalDenoiser:
                 fresh = [i for i in range(max(0, s - r), min(n, e + r)) if i not in inputs]
                 if target is None:
                     for i in fresh:
-                        inputs[i] = torch.from_numpy(current[i]).to(dev)
+                        inputs[i] = upload(current[i], dev)
                 elif fresh:
-                    batch = torch.from_numpy(np.stack([current[i] for i in fresh])).to(dev)
+                    batch = upload(np.stack([current[i] for i in fresh]), dev)
                     for i, t in zip(fresh, self._flicker_reducer.reduce_flicker_device(batch, target).unbind(0)):
                         inputs[i] = t
                 for i in range(s, e):

@@ -22,7 +22,7 @@ from typing import Any, Callable, Iterable, Iterator, List, Optional, Sequence, 
 import numpy as np
 
 from . import _lib
-from .deinterlace import _check_no_overlap
+from ._stage import ANY, Stage, check_frame_list, check_no_overlap, contiguous, upload
 
 logger = logging.getLogger(__name__)
 
@@ -31,6 +31,8 @@ TABLE = 64                                       # frames a dropout batch and it
 BOTTOM_ROWS = 30
 MAX_SIDE = 16384
 DEFAULT_RUN_CAPACITY = 8192
+_BOUNDS = ((32, ANY, 0, ANY, "vhs: frames of at least 32 rows expected (below 31 the reference's bottom region wraps round)"),
+           (0, MAX_SIDE, 2, MAX_SIDE, "vhs: frames of 2 .. 16384 columns and at most 16384 rows expected"))
 
 
 class VHSQuality(Enum):
@@ -237,7 +239,7 @@ def _repair_groups(ops: Sequence[tuple]) -> List[List[tuple]]:
     return groups
 
 
-class DeviceVHSProcessor:
+class DeviceVHSProcessor(Stage):
     """The reference's `VHSProcessor` on uint8 CUDA frames of one GPU.  Work is queued on torch's current stream of the frames' device.
     ``rng``: what the chroma detector's `choice` is drawn from - None is NumPy's global generator, which the reference uses, so a
     seeded run consumes it exactly as the reference does; a `np.random.RandomState` keeps the draws to the caller."""
@@ -246,35 +248,13 @@ class DeviceVHSProcessor:
         self.config = config or VHSConfig()
         self.device_id = int(device_id)
         self.rng = rng
-        self._lib = _lib.load()
-        _lib.require_gpu()
+        super().__init__(self.device_id)
+        self._wrong_device = f"vhs: frames on cuda:{self.device_id}, the processor's device, expected"
 
     # ---- checks --------------------------------------------------------------------------------------------------------------------
     def _check_frames(self, frames: Sequence) -> tuple:
-        import torch
-        f0 = frames[0]
-        for f in frames:
-            if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8:
-                raise ValueError("vhs: uint8 tensors expected")
-            if not f.is_cuda or f.device.index != self.device_id:
-                raise ValueError(f"vhs: frames on cuda:{self.device_id}, the processor's device, expected")
-            if f.dim() not in (2, 3) or (f.dim() == 3 and f.shape[2] != 3) or f.shape != f0.shape:
-                raise ValueError("vhs: frames H x W x 3 (BGR) or H x W of one shape expected")
-        h, w = int(f0.shape[0]), int(f0.shape[1])
-        if h < 32:
-            raise ValueError("vhs: frames of at least 32 rows expected (below 31 the reference's bottom region wraps round)")
-        if w < 2 or h > MAX_SIDE or w > MAX_SIDE:
-            raise ValueError("vhs: frames of 2 .. 16384 columns and at most 16384 rows expected")
-        return h, w, (3 if f0.dim() == 3 else 1)
-
-    @staticmethod
-    def _contiguous(frames: Sequence) -> List:
-        return [f if f.is_contiguous() else f.contiguous() for f in frames]
-
-    @staticmethod
-    def _upload(a: np.ndarray, dev):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        return check_frame_list(frames, "vhs: frames H x W x 3 (BGR) or H x W of one shape expected", _BOUNDS, self._dev,
+                                "vhs: uint8 tensors expected", self._wrong_device)
 
     # ---- device entries: queue, and (where they return NumPy arrays) wait once -------------------------------------------------------
     @_lib.on_tensor_device
@@ -284,7 +264,7 @@ class DeviceVHSProcessor:
         what was asked for, as NumPy arrays.  The run list has a capacity; the entry reports the true count, and on overflow the list
         is allocated again with that count and the statistics run again."""
         import torch
-        frames = self._contiguous(frames)
+        frames = contiguous(frames)
         h, w, c = self._check_frames(frames)
         n, dev = len(frames), frames[0].device
         t_sums = torch.empty((n, h), dtype=torch.int64, device=dev) if sums else None
@@ -316,17 +296,17 @@ class DeviceVHSProcessor:
     def blend_rows_device(self, srcs: Sequence, dsts: Sequence, spec_rows: np.ndarray, spec_factors: np.ndarray) -> None:
         """dsts[f][y] = fa * ((srcs[f][y1] + srcs[f][y2]) / 2) + fb * srcs[f][y] for every table row (f, y, y1, y2), (fa, fb)."""
         h, w, c = self._check_frames(list(srcs) + list(dsts))
-        _check_no_overlap(dsts, srcs)
+        check_no_overlap(dsts, srcs, "vhs")
         dev = srcs[0].device
-        rows = self._upload(np.asarray(spec_rows, dtype=np.int32).reshape(-1, 4), dev)
-        fac = self._upload(np.asarray(spec_factors, dtype=np.float32).reshape(-1, 2), dev)
+        rows = upload(np.asarray(spec_rows, dtype=np.int32).reshape(-1, 4), dev)
+        fac = upload(np.asarray(spec_factors, dtype=np.float32).reshape(-1, 2), dev)
         _lib.check(self._lib.fw_vhs_blend_rows_u8(_lib.ptr_table(srcs), _lib.ptr_table(dsts), len(srcs), h, w * c, _lib.ptr(rows),
                                                   _lib.ptr(fac), int(rows.shape[0]), _lib.stream_ptr(dev)))
 
     @_lib.on_tensor_device
     def rainbow_device(self, frames: Sequence, strength: float, outs: Optional[Sequence] = None) -> List:
         """The rainbow stencil and blend of BGR frames into new tensors (or ``outs``, which must not overlap any source)."""
-        frames = self._contiguous(frames)
+        frames = contiguous(frames)
         h, w, c = self._check_frames(frames)
         if c != 3:
             raise ValueError("vhs: BGR frames expected")
@@ -337,7 +317,7 @@ class DeviceVHSProcessor:
             if len(outs) != len(frames) or any(not o.is_contiguous() for o in outs):
                 raise ValueError("vhs: one contiguous destination per frame expected")
             self._check_frames(frames + outs)
-        _check_no_overlap(outs, frames)
+        check_no_overlap(outs, frames, "vhs")
         fa, fb = float(np.float32(strength)), float(np.float32(1 - strength))
         st = _lib.stream_ptr(frames[0].device)
         for b in range(0, len(frames), BATCH):
@@ -351,7 +331,7 @@ class DeviceVHSProcessor:
         import torch
         h, w, c = self._check_frames(frames)
         dev = frames[0].device
-        t = self._upload(np.asarray(tasks, dtype=np.int32).reshape(-1, 5), dev)
+        t = upload(np.asarray(tasks, dtype=np.int32).reshape(-1, 5), dev)
         sums = torch.empty((int(t.shape[0]),), dtype=torch.int64, device=dev)
         _lib.check(self._lib.fw_vhs_box_gray_sums_u8(_lib.ptr_table(frames), len(frames), h, w, c, _lib.ptr(t), int(t.shape[0]),
                                                      _lib.ptr(sums), _lib.stream_ptr(dev)))
@@ -361,9 +341,9 @@ class DeviceVHSProcessor:
     def repair_device(self, sources: Sequence, results: Sequence, boxes: np.ndarray, strength: float) -> None:
         """Boxes (mode, result, source, x, y, w, h, 0) rewritten in place in ``results``; disjoint within a result frame."""
         h, w, c = self._check_frames(list(sources) + list(results))
-        _check_no_overlap(results, sources)
+        check_no_overlap(results, sources, "vhs")
         dev = results[0].device
-        t = self._upload(np.asarray(boxes, dtype=np.int32).reshape(-1, 8), dev)
+        t = upload(np.asarray(boxes, dtype=np.int32).reshape(-1, 8), dev)
         _lib.check(self._lib.fw_vhs_dropout_repair_u8(_lib.ptr_table(sources), len(sources), _lib.ptr_table(results), len(results), h, w, c,
                                                       _lib.ptr(t), int(t.shape[0]), float(strength), _lib.stream_ptr(dev)))
 
@@ -381,7 +361,7 @@ class DeviceVHSProcessor:
         import torch
         h, w, c = self._check_frames(frames)
         dev = frames[0].device
-        t = self._upload(np.asarray(samples, dtype=np.int32).reshape(-1, 3), dev)
+        t = upload(np.asarray(samples, dtype=np.int32).reshape(-1, 3), dev)
         out = torch.empty((int(t.shape[0]), 2), dtype=torch.int32, device=dev)
         _lib.check(self._lib.fw_vhs_chroma_samples_u8(_lib.ptr_table(frames), len(frames), h, w, _lib.ptr(t), int(t.shape[0]),
                                                       _lib.ptr(out), _lib.stream_ptr(dev)))
@@ -391,7 +371,7 @@ class DeviceVHSProcessor:
     def chroma_shift_device(self, frames: Sequence, shifts: Sequence[int]) -> List:
         h, w, c = self._check_frames(frames)
         outs = _lib.empty_like_many(frames)
-        _check_no_overlap(outs, frames)
+        check_no_overlap(outs, frames, "vhs")
         table = (C.c_int32 * len(frames))(*[int(s) for s in shifts])
         _lib.check(self._lib.fw_vhs_chroma_shift_u8(_lib.ptr_table(frames), _lib.ptr_table(outs), table, len(frames), h, w, _lib.stream_ptr(frames[0].device)))
         return outs
@@ -514,7 +494,7 @@ class DeviceVHSProcessor:
         for b0 in range(start, stop, step):
             b1 = min(stop, b0 + step)
             lo, hi = max(0, b0 - r), min(n, b1 + r)
-            window = self._contiguous(frames[lo:hi])
+            window = contiguous(frames[lo:hi])
             boxes = self._dropout_boxes(window[b0 - lo:b1 - lo], run_capacity)
             tasks, owners = [], []
             for i in range(b0, b1):
@@ -610,7 +590,7 @@ class DeviceVHSProcessor:
         result = list(frames)
         if c == 3:
             for b in range(0, len(frames), BATCH):
-                batch = self._contiguous(frames[b:b + BATCH])
+                batch = contiguous(frames[b:b + BATCH])
                 found = self._detect_chroma_bleed_batch(batch)
                 move, shifts = [], []
                 for i, (detected, severity) in enumerate(found):
