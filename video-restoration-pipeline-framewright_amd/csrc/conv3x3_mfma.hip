@@ -60,17 +60,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
     FW_STAMP_INIT();
 
     // ---- persistent workgroup: a contiguous range of tiles ---------------------------------------------------
-    // Blocks b and b+8 share an XCD (and its L2): logical id lb puts the blocks of one XCD on a contiguous band of
-    // tiles, so vertically neighbouring tiles (shared halo rows) and the weights are served by one L2.
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;  // (XCD-banded: conv_common.h)
     const int tiles_x = (p.W + TILE_W - 1) / TILE_W;
     const int tiles_y = (p.H + TILE_H - 1) / TILE_H;
     const int ntiles = tiles_x * tiles_y;
-    const int t_lo = (int)((long)lb * ntiles / NB);
-    const int t_hi = (int)((long)(lb + 1) * ntiles / NB);
+    int t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
     const int nch = p.cin_chunks;
     const int nitems = (t_hi - t_lo) * nch;  // (tile, chunk) pairs, walked as one pipelined sequence
@@ -85,21 +80,17 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
     unsigned relb[ACT_ITERS];  // byte offset from the halo origin, plus (4 - i) KiB: the batch's immediate takes that off again
     auto piece_pos = [&](int i, int* row, int* px) {
         const int idx = (ACT_ITERS * wave + i) * 64 + lane;
-        const int rw = idx / ROW_PIECES;
-        *px = (idx - rw * ROW_PIECES) >> 2;
-        *row = (idx < ACT_PIECES) ? rw : -1;  // -1: the pad pieces behind the 18x34 image
+        const HaloPiece h = halo_piece(idx);
+        *px = h.px;
+        *row = (idx < ACT_PIECES) ? h.row : -1;  // -1: the pad pieces behind the 18x34 image
     };
 #pragma unroll
     for (int i = 0; i < ACT_ITERS; ++i) {
-        const int idx = (ACT_ITERS * wave + i) * 64 + lane;
-        const int row = idx / ROW_PIECES;
-        const int rm = idx - row * ROW_PIECES;
-        const int px = rm >> 2;
-        const int s = (rm & 3) ^ halo_swz(px);  // which 8-channel slot lands at this LDS position
+        const HaloPiece h = halo_piece((ACT_ITERS * wave + i) * 64 + lane);
         // nearest-x2 input reads source pixel (y >> 1, x >> 1); ((row - 1) >> 1) + 1 >= 0 for row >= 0
-        const int srow = ups ? (((row - 1) >> 1) + 1) : row;
-        const int spx = ups ? (((px - 1) >> 1) + 1) : px;
-        relb[i] = (unsigned)(((srow * Ws + spx) * p.in_cstride + s * 8) * 2) + (unsigned)(4 - i % 5) * 1024u;
+        const int srow = ups ? (((h.row - 1) >> 1) + 1) : h.row;
+        const int spx = ups ? (((h.px - 1) >> 1) + 1) : h.px;
+        relb[i] = (unsigned)(((srow * Ws + spx) * p.in_cstride + h.s * 8) * 2) + (unsigned)(4 - i % 5) * 1024u;
     }
     const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)lds;
     const char* in = reinterpret_cast<const char*>(p.in);
@@ -170,10 +161,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            const int px = 16 * ph + q + dx;
-            rd_off[dx][ph] = (RPW * wave) * ROW_PIECES + px * 4 + (sl ^ halo_swz(px));
-        }
+        for (int ph = 0; ph < 2; ++ph) rd_off[dx][ph] = halo_rd_off(RPW * wave, 16 * ph + q + dx, sl);
 
     // identity A-fragments (SPLIT): tile ctl of a 32-channel residual plane, row = cout 16*ctl + q, k = 8*sl + j -> 1 where
     // cout == k, as a lane-private bit mask over (ctl, j); scaled per plane when used
@@ -432,7 +420,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
             FW_STAMP(3);  // fp32-side epilogue
             // (2) typed NHWC output, 16 B per lane straight from the accumulators: v_permlane16_swap pairs the 8-byte fragments
             //     of two neighbouring 16-channel tiles so that a lane ends up with one whole 8-channel slot of its pixel
-            //     (ls; conv3x3_pair.hip has the lane map) and four lanes store a pixel's 64 contiguous bytes.  No transpose
+            //     (ls; pair16 in conv_common.h has the lane map) and four lanes store a pixel's 64 contiguous bytes.  No transpose
             //     through LDS and no barrier: the older wave of a SIMD stores while the younger one still runs MFMAs.
             if (p.out) {
                 // pass 0: the typed output; pass 1 (64-channel convs feeding a split trunk): lo = T(y - T(y)) into out_lo
@@ -456,13 +444,9 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
                                     oa = oa - Op<T>::unpack4(Op<T>::pack4(oa[0], oa[1], oa[2], oa[3]));
                                     ob = ob - Op<T>::unpack4(Op<T>::pack4(ob[0], ob[1], ob[2], ob[3]));
                                 }
-                                const uint2 pa = Op<T>::pack4(oa[0], oa[1], oa[2], oa[3]);
-                                const uint2 pb = Op<T>::pack4(ob[0], ob[1], ob[2], ob[3]);
-                                const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-                                const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
+                                const uint4 v = pair16<T>(oa, ob);
                                 if (x0 + 16 * ph + q < p.W)
-                                    store16(lane_base + rowoff + (long)(16 * ph) * p.out_cstride * 2 + (long)c2 * p.out_pstride * 2,
-                                            make_uint4(sx[0], sy[0], sx[1], sy[1]));
+                                    store16(lane_base + rowoff + (long)(16 * ph) * p.out_cstride * 2 + (long)c2 * p.out_pstride * 2, v);
                             }
                     }
                 }

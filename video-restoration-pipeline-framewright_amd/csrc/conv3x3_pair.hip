@@ -14,11 +14,9 @@
 // 16-byte stores (v_permlane16_swap pairs the fragments of two 16-channel tiles), before the barrier.
 // This is the RING form, used for small frames; conv3x3_pair_slide.hip removes the vertical ring and is the default from
 // about 720p up (launch_conv3x3_pair below chooses).
-#include <mutex>
 #include <type_traits>
-#include <cstdlib>
 #include "fw_internal.h"
-#include "conv_common.h"
+#include "conv_pair_common.h"
 
 namespace fw {
 
@@ -33,10 +31,12 @@ constexpr int PAIR_TH = FW_PAIR_TH_ABLATION;
 constexpr int PAIR_TH = TILE_H - 2;  // 14 valid rows per tile
 #endif
 constexpr int PAIR_TW = TILE_W - 2;  // 30 valid pixels per tile row
+// rows 0 / 15 and pixels 0 / 31 of the compute region are the recompute ring; the x_a tile is the standard 18x34 halo tile
+using RingGeom = PairGeom<1, PAIR_TH, 1, PAIR_TW, 1, 1, ROW_PIECES>;
 
 struct PairSmem {
     static constexpr int NA = 2;                          // activation stages (the x_a tile borrows the idle one)
-    static constexpr int W_REGION = 2 * W_FRAGS * 64;     // weight chunk of conv_a (18 fragments) + conv_b (18)
+    static constexpr int W_REGION = PAIR_W_REGION;        // weight chunk of conv_a (18 fragments) + conv_b (18)
     static constexpr int W_BASE = NA * ACT_REGION;
     static constexpr int W_ITERS = (2 * W_FRAGS + NWAVES - 1) / NWAVES;  // 5
     static constexpr int TOTAL = W_BASE + 2 * W_REGION;   // 152 KiB
@@ -55,15 +55,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
     const int sl = lane >> 4;  // 8-channel slot of the chunk (A/B k index), 4-channel group of the D tile
     FW_STAMP_INIT();
 
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;
     const int tiles_x = (p.W + PAIR_TW - 1) / PAIR_TW;
     const int tiles_y = (p.H + PAIR_TH - 1) / PAIR_TH;
     const int ntiles = tiles_x * tiles_y;
-    const int t_lo = (int)((long)lb * ntiles / NB);
-    const int t_hi = (int)((long)(lb + 1) * ntiles / NB);
+    int t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
     const int na = p.na;             // input chunks shared by both convs
     const int ipt = na + 1;          // items per tile: na shared chunks (both convs), then conv_b's x_a chunk
@@ -73,19 +70,13 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
     unsigned relb[ACT_ITERS];  // byte offset of this lane's piece from the region's halo origin, plus (4 - i) KiB (batch immediate)
     auto piece_pos = [&](int i, int* row, int* px) {
         const int idx = (ACT_ITERS * wave + i) * 64 + lane;
-        const int rw = idx / ROW_PIECES;
-        *px = (idx - rw * ROW_PIECES) >> 2;
-        *row = (idx < ACT_PIECES) ? rw : -1;
+        const HaloPiece h = halo_piece(idx);
+        *px = h.px;
+        *row = (idx < ACT_PIECES) ? h.row : -1;
     };
 #pragma unroll
-    for (int i = 0; i < ACT_ITERS; ++i) {
-        const int idx = (ACT_ITERS * wave + i) * 64 + lane;
-        const int row = idx / ROW_PIECES;
-        const int rm = idx - row * ROW_PIECES;
-        const int px = rm >> 2;
-        const int s = (rm & 3) ^ halo_swz(px);
-        relb[i] = (unsigned)(((row * p.W + px) * p.in_cstride + s * 8) * 2) + (unsigned)(4 - i % 5) * 1024u;
-    }
+    for (int i = 0; i < ACT_ITERS; ++i)
+        relb[i] = halo_piece_off((ACT_ITERS * wave + i) * 64 + lane, p.W, p.in_cstride) + (unsigned)(4 - i % 5) * 1024u;
     const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)lds;
     const char* in = reinterpret_cast<const char*>(p.in);
     const char* wa_b = reinterpret_cast<const char*>(p.wpk_a);
@@ -141,93 +132,26 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
             f_src += chunk_bytes;
         }
     };
-    // weights of item j of a tile -> weight stage ws: fragments [0,18) = conv_a chunk j (waves 0-3: 5, 5, 5, 3 fragments),
-    // [18,36) = conv_b chunk j (waves 4-7); the last item (j == na) only has conv_b's chunk
-    auto issue_w = [&](int j, int ws) {
-        const int half = wave / (NWAVES / 2), k = wave % (NWAVES / 2);
-        if (half == 1 || j < na)
-            issue_w_half((half ? wb_b : wa_b) + (size_t)j * (W_FRAGS * 1024),
-                         lds_base + (unsigned)(SM::W_BASE + ws * SM::W_REGION + W_FRAGS * half * 64) * 16u, k, lane16);
-    };
+    const PairIssueW<SM::W_BASE> issue_w{na, wa_b, wb_b, lds_base, lane16};  // (item j, weight stage, issuing wave)
 
     int rd_off[3][2];  // [dx][ph]: piece index of (halo row RPW*wave, px 16*ph + q + dx, slot sl)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            const int px = 16 * ph + q + dx;
-            rd_off[dx][ph] = (RPW * wave) * ROW_PIECES + px * 4 + (sl ^ halo_swz(px));
-        }
-    // weight fragment of (tap, tile w) inside a weight stage
-    auto widx = [](int tap, int w) { return w < 2 ? tap * 2 + w : W_FRAGS + tap * 2 + (w - 2); };
+        for (int ph = 0; ph < 2; ++ph) rd_off[dx][ph] = halo_rd_off(RPW * wave, 16 * ph + q + dx, sl);
+    const PairWIdx widx;
 
     f32x4 acc[RPW][NW][2];  // [row][tile][16-pixel half]: pixel 16*ph + q, channels 16*(w & 1) + 4*sl + j of conv w >> 1
 
-    // ---- emit: accumulators -> LeakyReLU -> typed, without a transpose through LDS and BEFORE the barrier ------------------
-    // A lane's D fragments hold channels 4*sl.. of tile w0 and of tile w0+1 for pixel 16*ph + q (8 B each).  One
-    // v_permlane16_swap per dword (rows of 16 lanes: odd rows of the first operand <-> even rows of the second) leaves every
-    // lane with 16 contiguous bytes: lanes with even sl get channels 4*sl..4*sl+7 of tile w0 (their own 8 B + those of lane
-    // ^ 16), lanes with odd sl channels 4*(sl-1)..+7 of tile w0+1.  That is one whole 8-channel slot of the pixel:
-    //     ls = sl even ? sl / 2 : 2 + sl / 2
-    // so the global store is 16 B per lane / 64 contiguous bytes per pixel straight from registers, and x_a goes into its LDS
-    // tile with one ds_write_b128 per fragment.  Everything up to the LDS write needs no barrier: a wave converts and stores
-    // as soon as ITS last item is done - the older wave of a SIMD while the younger one still runs MFMAs, the younger one
-    // with the VALU to itself (with the convert behind the barrier both waves of a SIMD converted at the same time: 18 % of
-    // the kernel, phase stamps in DESIGN.md section 6).
+    // ---- emit (conv_pair_common.h): convert, store the valid interior of the compute region, x_a into its halo-format tile ----------
     const int ls = (sl & 1) ? 2 + (sl >> 1) : (sl >> 1);
     const unsigned st_off = (unsigned)((q * p.out_cstride + ls * 8) * 2);  // store offset from (row, compute-region px 16*ph)
-    auto convert = [&](int w0, uint4 (&pk)[RPW][2]) {
-#pragma unroll
-        for (int row = 0; row < RPW; ++row)
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const f32x4 va = lrelu4(w0 ? acc[row][2][ph] : acc[row][0][ph]);
-                const f32x4 vb = lrelu4(w0 ? acc[row][3][ph] : acc[row][1][ph]);
-                const uint2 pa = Op<T>::pack4(va[0], va[1], va[2], va[3]);
-                const uint2 pb = Op<T>::pack4(vb[0], vb[1], vb[2], vb[3]);
-                const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-                const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
-                pk[row][ph] = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-            }
-    };
-    // valid interior of the compute region -> global plane (pixels 0 / 31 and rows 0 / 15 are the recompute ring)
-    auto store_out = [&](const uint4 (&pk)[RPW][2], int oy, int ox, T* plane, auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int row = 0; row < RPW; ++row) {
-            const int cr = RPW * wave + row;
-            const int gy = oy + cr;
-            const bool row_ok = cr >= 1 && cr <= PAIR_TH && (INTERIOR || (unsigned)gy < (unsigned)p.H);  // wave-uniform
-            if (!row_ok) continue;
-            char* rowbase = reinterpret_cast<char*>(plane) + ((long)gy * p.W + ox) * p.out_cstride * 2;  // wave-uniform
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const int cp = 16 * ph + q;
-                if (cp >= 1 && cp <= PAIR_TW && (INTERIOR || (unsigned)(ox + cp) < (unsigned)p.W))
-                    store16(rowbase + (long)(16 * ph) * p.out_cstride * 2 + st_off, pk[row][ph]);
-            }
-        }
-    };
-    // x_a -> its halo-format tile in LDS (zero outside the image = conv_b's zero padding; border tiles only)
-    auto write_xa = [&](const uint4 (&pk)[RPW][2], uint4* xa, int oy, int ox, auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int row = 0; row < RPW; ++row) {
-            const int cr = RPW * wave + row;
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const int cp = 16 * ph + q, hp = cp + 1;
-                uint4 v = pk[row][ph];
-                if (!INTERIOR && !((unsigned)(oy + cr) < (unsigned)p.H && (unsigned)(ox + cp) < (unsigned)p.W)) v = make_uint4(0, 0, 0, 0);
-                xa[((cr + 1) * HALO_W + hp) * 4 + (ls ^ halo_swz(hp))] = v;
-            }
-        }
-    };
+    const PairEmit<RingGeom, T> emit{p, wave, q, ls, st_off, acc};
 
     // ---- pipeline: one item of look-ahead.  Activation stage of DMA item q (q-th fetched chunk) = q & 1; the x_a item of a
     //      tile uses the stage of the tile's last shared chunk (free again after a barrier), while the other stage already
     //      receives the next tile's first chunk. -----------------------------------------------------------------------------
-    issue_w(0, 0);
+    issue_w.issue(0, 0, wave);
     issue_act(0);
 
     int n = 0;    // global item counter (weight stage = n & 1)
@@ -272,7 +196,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
             const bool young = wave >= NWAVES / 2;
             auto dma_slot = [&](int d) {
                 if (d == (young ? FW_DMA_SLOT_W2 : FW_DMA_SLOT_W)) {
-                    if (more && !(FW_PAIR_DBG & 2)) issue_w(jn, (n + 1) & 1);
+                    if (more && !(FW_PAIR_DBG & 2)) issue_w.issue(jn, (n + 1) & 1, wave);
                 } else if (d == (young ? FW_DMA_SLOT_A2 : FW_DMA_SLOT_A)) {
                     if (fetch) issue_act(fetch_stage);
                 }
@@ -307,11 +231,11 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
         const bool interior = oy >= 0 && ox >= 0 && oy + TILE_H <= p.H && ox + TILE_W <= p.W;
         uint4 pk[RPW][2];
         if (!(FW_PAIR_DBG & 4)) {
-            convert(0, pk);
+            emit.convert(0, pk);
             if (interior)
-                store_out(pk, oy, ox, reinterpret_cast<T*>(p.out_a), std::true_type{});
+                emit.template store_out<true>(pk, oy, ox, reinterpret_cast<T*>(p.out_a));
             else
-                store_out(pk, oy, ox, reinterpret_cast<T*>(p.out_a), std::false_type{});
+                emit.template store_out<false>(pk, oy, ox, reinterpret_cast<T*>(p.out_a));
         }
         FW_STAMP(6);  // emit: convert + stores
         // every wave must be finished with the last chunk's stage before it becomes the x_a tile
@@ -319,9 +243,9 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
         FW_STAMP(0);
         if (!(FW_PAIR_DBG & 4)) {
             if (interior)
-                write_xa(pk, lds + ((qd - 1) & 1) * ACT_REGION, oy, ox, std::true_type{});
+                emit.template write_xa<true>(pk, lds + ((qd - 1) & 1) * ACT_REGION, oy, ox);
             else
-                write_xa(pk, lds + ((qd - 1) & 1) * ACT_REGION, oy, ox, std::false_type{});
+                emit.template write_xa<false>(pk, lds + ((qd - 1) & 1) * ACT_REGION, oy, ox);
         }
         FW_STAMP(3);  // x_a tile into LDS
         run_item(na, std::false_type{}, false);
@@ -331,37 +255,15 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_kern
         if (!(FW_PAIR_DBG & 32)) FW_WAIT_VMCNT(0);
         FW_STAMP(5);
         if (!(FW_PAIR_DBG & 4)) {
-            convert(2, pk);
+            emit.convert(2, pk);
             if (interior)
-                store_out(pk, oy, ox, reinterpret_cast<T*>(p.out_b), std::true_type{});
+                emit.template store_out<true>(pk, oy, ox, reinterpret_cast<T*>(p.out_b));
             else
-                store_out(pk, oy, ox, reinterpret_cast<T*>(p.out_b), std::false_type{});
+                emit.template store_out<false>(pk, oy, ox, reinterpret_cast<T*>(p.out_b));
         }
         FW_STAMP(6);
     }
     FW_STAMP_FLUSH(p.stamps);
-}
-
-bool pair_slide_enabled(int H, int W, int num_cus);
-void launch_conv3x3_pair_slide(DType dt, const ConvPairParams& p, int num_cus, hipStream_t stream);
-bool pair_slide32_enabled();   // conv3x3_pair_slide32.hip: the window kernel with all 32 columns of a tile valid
-void launch_conv3x3_pair_slide32(DType dt, const ConvPairParams& p, int num_cus, hipStream_t stream);
-
-static int pair_num_cus() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        // FW_CONV_GRID: persistent workgroups per launch (default one per CU); half of them lets two frames run side by side on
-        // two streams, each kernel on its own half of the CUs
-        if (const char* e = getenv("FW_CONV_GRID")) {
-            const int g = atoi(e);
-            if (g > 0 && g < v) v = g;
-        }
-        return v;
-    }();
-    return n;
 }
 
 void launch_conv3x3_pair(DType dt, const ConvPairParams& p_in, hipStream_t stream) {
@@ -375,20 +277,16 @@ void launch_conv3x3_pair(DType dt, const ConvPairParams& p_in, hipStream_t strea
 #ifdef FW_PAIR_STAMP
     p.stamps = stamp_buffer(0);
 #endif
-    if (pair_slide_enabled(p.H, p.W, pair_num_cus())) {  // the sliding-window form (conv3x3_pair_slide.hip) for all but small frames
+    const int cus = conv_num_cus();  // persistent workgroups per launch (FW_CONV_GRID)
+    if (pair_slide_enabled(p.H, p.W, cus)) {  // the sliding-window form (conv3x3_pair_slide.hip) for all but small frames
         if (pair_slide32_enabled())
-            launch_conv3x3_pair_slide32(dt, p, pair_num_cus(), stream);
+            launch_conv3x3_pair_slide32(dt, p, cus, stream);
         else
-            launch_conv3x3_pair_slide(dt, p, pair_num_cus(), stream);
+            launch_conv3x3_pair_slide(dt, p, cus, stream);
         return;
     }
     const int tiles = ((p.W + PAIR_TW - 1) / PAIR_TW) * ((p.H + PAIR_TH - 1) / PAIR_TH);
-    dim3 grid(tiles < pair_num_cus() ? tiles : pair_num_cus()), block(64 * NWAVES);
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((conv3x3_pair_kernel<__bf16>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((conv3x3_pair_kernel<_Float16>), grid, block, 0, stream, p);
-    FW_HIP_CHECK(hipGetLastError());
+    launch_pair_kernel(conv3x3_pair_kernel<__bf16>, conv3x3_pair_kernel<_Float16>, dt, tiles, cus, p, stream);
 }
 
 }  // namespace fw

@@ -20,7 +20,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "fw_internal.h"
-#include "conv_common.h"
+#include "conv_pair_common.h"
 
 #ifndef FW_DMA_SLOT_W
 #define FW_DMA_SLOT_W 2
@@ -36,6 +36,8 @@ constexpr int PS_PIECES = PS_HALO_H * ROW_PIECES;  // 2584
 constexpr int PS_EXTRA = PS_PIECES - ACT_ITERS * NWAVES * 64;  // 24 pieces beyond the 40 batched KiB: one more DMA of wave 0
 constexpr int PS_REGION = 41 * 64;     // pieces per activation stage
 constexpr int PS_CARRY = 2 * ROW_PIECES;  // two x_a rows
+// every row of a tile is a valid output, pixels 0 / 31 of the region are the recompute ring; x_a row cr is row cr + 2 of the x_a tile
+using SlideGeom = PairGeom<0, TILE_H - 1, 1, PS_TW, 2, 1, ROW_PIECES>;
 
 constexpr int PS_WARM_ROWS = 4;                           // input rows 16 ty - 3 .. 16 ty: what conv_a rows 16 ty - 2, 16 ty - 1 read
 constexpr int PS_WARM_PIECES = PS_WARM_ROWS * ROW_PIECES;  // 544 per chunk
@@ -44,7 +46,7 @@ constexpr int PS_WARM_SLOT = PS_WARM_KIB * 64;            // pieces per chunk sl
 constexpr int PS_WARM_CHUNKS = 4;                         // chunk slots: a warm-up batch
 
 struct SlideSmem {
-    static constexpr int W_REGION = 2 * W_FRAGS * 64;
+    static constexpr int W_REGION = PAIR_W_REGION;
     static constexpr int W_BASE = 2 * PS_REGION;
     static constexpr int CARRY = W_BASE + 2 * W_REGION;
     static constexpr int BIAS = CARRY + PS_CARRY;  // 64 floats: bias_a, bias_b
@@ -75,65 +77,6 @@ enum {
 static_assert(NWAVES == 8 && RPW == 2 && PS_EXTRA > 0 && PS_EXTRA <= 64, "written for 8 waves of 2 rows");
 static_assert(SlideSmem::TOTAL * 16 <= 160 * 1024, "LDS");
 
-// One shared-chunk item with conv_b one row behind conv_a.  acc tiles 0,1 = conv_a rows (2w, 2w+1), 2,3 = conv_b rows
-// (2w-1, 2w); xr[h] = halo row 2w + h.  conv_a row r, tap row dy reads xr[r + dy + 1], conv_b xr[r + dy].  Row h is last used
-// at dy = min(h, 2): rows 0 / 1 are re-read for the next dx after dy = 0 / 1, row 2 after conv_b's tiles of dy = 2, rows 3, 4
-// at the start of the next dx.  conv_b's tiles go first within a step so that the freshly read rows are needed last.
-template <typename T, bool WITH_B, typename WIdx, typename Slot>
-__device__ __forceinline__ void conv_item_lag(f32x4 (&acc)[RPW][4][2], const uint4* a, const uint4* wl, const int (&rd_off)[3][2],
-                                              WIdx widx, Slot dma_slot) {
-    constexpr int NWU = WITH_B ? 4 : 2;
-    constexpr int NK = 9 * NWU;
-    constexpr int RING = 3;
-    uint4 xr[5][2];
-    uint4 wf[RING];
-    auto tile_of = [](int w) { return WITH_B ? ((w + 2) & 3) : w; };
-    auto load_w = [&](int k) {
-        const int t = k / NWU, w = k - t * NWU;
-        const int dx = t / 3, dy = t - 3 * dx;
-        wf[k % RING] = wl[widx(dy * 3 + dx, tile_of(w)) * 64];
-    };
-    auto load_row = [&](int h, int dx) {
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph) xr[h][ph] = a[h * ROW_PIECES + rd_off[dx][ph]];
-    };
-#pragma unroll
-    for (int h = 0; h < 5; ++h) load_row(h, 0);
-#pragma unroll
-    for (int k = 0; k < RING - 1; ++k) load_w(k);
-    FW_SB();
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int dx = t / 3, dy = t - 3 * dx;
-        if (dx < 2 && dy == 1) load_row(0, dx + 1);
-        if (dx < 2 && dy == 2) load_row(1, dx + 1);
-        if (dx > 0 && dy == 0) {
-            load_row(3, dx);
-            load_row(4, dx);
-        }
-#pragma unroll
-        for (int w = 0; w < NWU; ++w) {
-            const int k = t * NWU + w;
-            if (k + RING - 1 < NK) load_w(k + RING - 1);
-            FW_SB();
-            const int tile = tile_of(w);
-            const int lag = tile >= 2 ? 0 : 1;
-#pragma unroll
-            for (int row = 0; row < RPW; ++row)
-#pragma unroll
-                for (int ph = 0; ph < 2; ++ph)
-                    acc[row][tile][ph] = Op<T>::mfma16(wf[k % RING], xr[row + dy + lag][ph], acc[row][tile][ph]);
-            FW_SB();
-#pragma unroll
-            for (int d = 0; d < 4 / NWU; ++d) dma_slot((t * NWU + w) * (4 / NWU) + d);
-            FW_SB();
-            // row 2 is free once conv_b's tiles of dy = 2 are out (WITH_B: after w = 1; conv_a only: row 2 is read by conv_a
-            // row 0 at dy = 1 and row 1 at dy = 0 only, so it is free at dy = 2 as well)
-            if (dx < 2 && dy == 2 && w == (WITH_B ? 1 : 0)) load_row(2, dx + 1);
-        }
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slide_kernel(const ConvPairParams p) {
     using SM = SlideSmem;
@@ -147,15 +90,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     const int sl = lane >> 4;
     FW_STAMP_INIT();  // phase stamps: diagnostic builds only (-DFW_PAIR_STAMP, conv_common.h)
 
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;
     const int tiles_x = (p.W + PS_TW - 1) / PS_TW;
     const int tiles_y = (p.H + PS_TH) / PS_TH;  // the last conv_b row H - 1 = 16 ty + 14 at the latest
     const int ntiles = tiles_x * tiles_y;        // column-major: t = tx * tiles_y + ty
-    const int t_lo = (int)((long)lb * ntiles / NB);
-    const int t_hi = (int)((long)(lb + 1) * ntiles / NB);
+    int t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
 #ifdef FW_PS_NOWARM   // timing only (wrong pixels in the first conv_b row of a run that starts mid-column): what the warm-up tiles cost
     const int needs_warm = 0;
@@ -178,13 +118,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     auto piece_idx = [&](int bt, int i) { return i < ACT_ITERS ? (ACT_ITERS * vwave(bt) + i) * 64 + lane : ACT_ITERS * NWAVES * 64 + lane; };
     unsigned relb[NBB][ACT_ITERS];
     unsigned relb_x = 0;
-    auto piece_off = [&](int idx) {
-        const int row = idx / ROW_PIECES;
-        const int rm = idx - row * ROW_PIECES;
-        const int px = rm >> 2;
-        const int s = (rm & 3) ^ halo_swz(px);
-        return (unsigned)(((row * p.W + px) * p.in_cstride + s * 8) * 2);
-    };
+    auto piece_off = [&](int idx) { return halo_piece_off(idx, p.W, p.in_cstride); };
 #pragma unroll
     for (int bt = 0; bt < NBB; ++bt)
 #pragma unroll
@@ -215,9 +149,8 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         f_src = in + ((long)(R0 - 2) * p.W + (ox - 1)) * p.in_cstride * 2;
         f_ok = 0;
         auto inside = [&](int idx) {
-            const int row = idx / ROW_PIECES;
-            const int px = (idx - row * ROW_PIECES) >> 2;
-            return idx < PS_PIECES && (unsigned)(R0 - 2 + row) < (unsigned)p.H && (unsigned)(ox - 1 + px) < (unsigned)p.W;
+            const HaloPiece h = halo_piece(idx);
+            return idx < PS_PIECES && (unsigned)(R0 - 2 + h.row) < (unsigned)p.H && (unsigned)(ox - 1 + h.px) < (unsigned)p.W;
         };
 #pragma unroll
         for (int bt = 0; bt < NBB; ++bt)
@@ -263,16 +196,13 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             f_src += chunk_bytes;
         }
     };
+    const PairIssueW<SM::W_BASE> pair_w{na, wa_b, wb_b, lds_base, lane16};
     // halves: bit 0 = conv_a's fragments, bit 1 = conv_b's
     auto issue_w = [&](int j, int ws, int halves = 3) {
         if (!issuer) return;
 #pragma unroll
         for (int bt = 0; bt < NBB; ++bt) {
-            const int v = vwave(bt);
-            const int half = v / (NWAVES / 2), k = v % (NWAVES / 2);
-            if (((halves >> half) & 1) && (half == 1 || j < na))
-                issue_w_half((half ? wb_b : wa_b) + (size_t)j * (W_FRAGS * 1024),
-                             lds_base + (unsigned)(SM::W_BASE + ws * SM::W_REGION + W_FRAGS * half * 64) * 16u, k, lane16);
+            pair_w.template issue<true>(j, ws, vwave(bt), halves);
         }
     };
 
@@ -280,62 +210,16 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            const int px = 16 * ph + q + dx;
-            rd_off[dx][ph] = (RPW * wave) * ROW_PIECES + px * 4 + (sl ^ halo_swz(px));
-        }
-    auto widx = [](int tap, int w) { return w < 2 ? tap * 2 + w : W_FRAGS + tap * 2 + (w - 2); };
+        for (int ph = 0; ph < 2; ++ph) rd_off[dx][ph] = halo_rd_off(RPW * wave, 16 * ph + q + dx, sl);
+    const PairWIdx widx;
 
     f32x4 acc[RPW][NW][2];
 
-    // ---- emit pieces (conv3x3_pair.hip has the lane map of the permlane swap) -----------------------------------------------
+    // ---- emit (conv_pair_common.h): columns 1..30 of the region are valid outputs; the wave's rows of x_a start at image row
+    //      R0 + 2 * wave, those of x_b one row higher ---------------------------------------------------------------------------------
     const int ls = (sl & 1) ? 2 + (sl >> 1) : (sl >> 1);
     const unsigned st_off = (unsigned)((q * p.out_cstride + ls * 8) * 2);
-    auto convert = [&](int w0, uint4 (&pk)[RPW][2]) {
-#pragma unroll
-        for (int row = 0; row < RPW; ++row)
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const f32x4 va = lrelu4(w0 ? acc[row][2][ph] : acc[row][0][ph]);
-                const f32x4 vb = lrelu4(w0 ? acc[row][3][ph] : acc[row][1][ph]);
-                const uint2 pa = Op<T>::pack4(va[0], va[1], va[2], va[3]);
-                const uint2 pb = Op<T>::pack4(vb[0], vb[1], vb[2], vb[3]);
-                const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-                const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
-                pk[row][ph] = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-            }
-    };
-    // the wave's two rows start at image row gy0; columns 1..30 of the region are valid outputs
-    auto store_out = [&](const uint4 (&pk)[RPW][2], int gy0, int ox, T* plane, auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int row = 0; row < RPW; ++row) {
-            const int gy = gy0 + row;
-            if (!INTERIOR && !((unsigned)gy < (unsigned)p.H)) continue;  // wave-uniform
-            char* rowbase = reinterpret_cast<char*>(plane) + ((long)gy * p.W + ox) * p.out_cstride * 2;
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const int cp = 16 * ph + q;
-                if (cp >= 1 && cp <= PS_TW && (INTERIOR || (unsigned)(ox + cp) < (unsigned)p.W))
-                    store16(rowbase + (long)(16 * ph) * p.out_cstride * 2 + st_off, pk[row][ph]);
-            }
-        }
-    };
-    // conv_a row cr of the tile -> x_a tile row cr + 2 (zero outside the image = conv_b's zero padding)
-    auto write_xa = [&](const uint4 (&pk)[RPW][2], uint4* xa, int R0, int ox, auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int row = 0; row < RPW; ++row) {
-            const int cr = RPW * wave + row;
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const int cp = 16 * ph + q, hp = cp + 1;
-                uint4 v = pk[row][ph];
-                if (!INTERIOR && !((unsigned)(R0 + cr) < (unsigned)p.H && (unsigned)(ox + cp) < (unsigned)p.W)) v = make_uint4(0, 0, 0, 0);
-                xa[((cr + 2) * HALO_W + hp) * 4 + (ls ^ halo_swz(hp))] = v;
-            }
-        }
-    };
+    const PairEmit<SlideGeom, T> emit{p, wave, q, ls, st_off, acc};
     uint4* carry = lds + SM::CARRY;
     float* bias_l = reinterpret_cast<float*>(lds + SM::BIAS);  // [0, 32) bias_a, [32, 64) bias_b
     // Loaded ahead of every DMA and read by the tiles from LDS: a global load at the top of a tile would make hipcc wait for
@@ -356,7 +240,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         //      first tile's item 0 wants them anyway (weight stage 0, first half), those of the others in the second weight
         //      stage and, with a fourth chunk, in the second half of stage 0 - conv_b's fragments of item 0 then follow the
         //      warm-up.  Waves 4 - 7 (one per SIMD) take one row x one pixel half each and both cout tiles, chunk by chunk
-        //      and tap by tap in the item's order, so every accumulator sees the sums of conv_item_lag in the same order.
+        //      and tap by tap in the item's order, so every accumulator sees the sums of conv_item_lag (conv_pair_common.h) in the same order.
         int R0, ox;
         origin(t_lo, &R0, &ox);
         const int wr0 = R0 - 3;
@@ -369,10 +253,9 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         for (int i = 0; i < 5; ++i) {
             const int li0 = (5 * w_hi + i) * 64 + lane;
             const int li = li0 < PS_WARM_PIECES ? li0 : PS_WARM_PIECES - 1;  // pad pieces: any piece of the chunk
-            const int row = li / ROW_PIECES;
-            const int px = (li - row * ROW_PIECES) >> 2;
+            const HaloPiece h = halo_piece(li);
             w_rel[i] = piece_off(li);
-            if ((unsigned)(wr0 + row) < (unsigned)p.H && (unsigned)(ox - 1 + px) < (unsigned)p.W) w_ok |= 1u << i;
+            if ((unsigned)(wr0 + h.row) < (unsigned)p.H && (unsigned)(ox - 1 + h.px) < (unsigned)p.W) w_ok |= 1u << i;
         }
         auto warm_rows = [&](int b, int c) {  // chunk c -> slot b
             const char* src = w_src + (long)c * chunk_bytes;
@@ -451,12 +334,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         }
         if (wave >= NWAVES / 2) {
             // as convert() and write_xa() do for rows 16, 17 of the x_a tile, straight into the carry buffer
-            const f32x4 va = lrelu4(wacc[0]), vb = lrelu4(wacc[1]);
-            const uint2 pa = Op<T>::pack4(va[0], va[1], va[2], va[3]);
-            const uint2 pb = Op<T>::pack4(vb[0], vb[1], vb[2], vb[3]);
-            const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-            const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
-            uint4 v = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+            uint4 v = pair16<T>(lrelu4(wacc[0]), lrelu4(wacc[1]));
             const int cp = 16 * wph + q, hp = cp + 1;
             if (!((unsigned)(R0 - 2 + wrow) < (unsigned)p.H && (unsigned)(ox + cp) < (unsigned)p.W)) v = make_uint4(0, 0, 0, 0);
             carry[(wrow * HALO_W + hp) * 4 + (ls ^ halo_swz(hp))] = v;
@@ -519,7 +397,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             const uint4* wl = lds + SM::W_BASE + (n & 1) * SM::W_REGION + lane;
             auto& slot_fn = dma_slot;
             if constexpr (KIND == 0)
-                conv_item_lag<T, true>(acc, a, wl, rd_off, widx, slot_fn);
+                conv_item_lag<ROW_PIECES, T, true>(acc, a, wl, rd_off, NoXCol{}, widx, slot_fn);
             else
                 conv_item<T, NW, 2>(acc, a, wl, rd_off, widx, slot_fn, [](const uint4 (&)[RPW][2]) {}, [](int) {});
             if (SHARED) ++qd;
@@ -538,19 +416,19 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         // everything this tile reads, computes and stores inside the image?  (uniform)
         const bool interior = ox >= 0 && ox + TILE_W <= p.W && R0 >= 1 && R0 + TILE_H <= p.H;
         uint4 pk[RPW][2];
-        convert(0, pk);
+        emit.convert(0, pk);
         if (interior)
-            store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::true_type{});
+            emit.template store_out<true>(pk, R0, ox, reinterpret_cast<T*>(p.out_a));
         else
-            store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::false_type{});
+            emit.template store_out<false>(pk, R0, ox, reinterpret_cast<T*>(p.out_a));
         FW_STAMP(ST_XA_EPI);  // convert + stores of x_a
         __syncthreads();      // every wave is done with the last chunk's stage: it becomes the x_a tile
         FW_STAMP(ST_BARRIER);
         uint4* xa = lds + ((qd - 1) & 1) * PS_REGION;
         if (interior)
-            write_xa(pk, xa, R0, ox, std::true_type{});
+            emit.template write_xa<true>(pk, xa, R0, ox);
         else
-            write_xa(pk, xa, R0, ox, std::false_type{});
+            emit.template write_xa<false>(pk, xa, R0, ox);
         // x_a rows R0 - 2, R0 - 1 -> tile rows 0, 1: from the tile above (carry), zero at the top of a column
         if (lane < PS_CARRY / NWAVES) {
             const int i = wave * (PS_CARRY / NWAVES) + lane;
@@ -572,11 +450,11 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         // conv_b done for this wave: rows R0 - 1 + (2w, 2w + 1).  In flight: the x_a stores (an item old), the next weights.
         FW_WAIT_VMCNT(0);
         FW_STAMP(ST_VMCNT);
-        convert(2, pk);
+        emit.convert(2, pk);
         if (interior)
-            store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::true_type{});
+            emit.template store_out<true>(pk, R0 - 1, ox, reinterpret_cast<T*>(p.out_b));
         else
-            store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::false_type{});
+            emit.template store_out<false>(pk, R0 - 1, ox, reinterpret_cast<T*>(p.out_b));
         FW_STAMP(ST_XB_EPI);  // convert + stores of x_b
     }
     FW_STAMP_FLUSH(p.stamps);
@@ -594,12 +472,7 @@ bool pair_slide_enabled(int H, int W, int num_cus) {
 
 void launch_conv3x3_pair_slide(DType dt, const ConvPairParams& p, int num_cus, hipStream_t stream) {
     const int tiles = ((p.W + PS_TW - 1) / PS_TW) * ((p.H + PS_TH) / PS_TH);
-    dim3 grid(tiles < num_cus ? tiles : num_cus), block(64 * NWAVES);
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((conv3x3_pair_slide_kernel<__bf16>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((conv3x3_pair_slide_kernel<_Float16>), grid, block, 0, stream, p);
-    FW_HIP_CHECK(hipGetLastError());
+    launch_pair_kernel(conv3x3_pair_slide_kernel<__bf16>, conv3x3_pair_slide_kernel<_Float16>, dt, tiles, num_cus, p, stream);
 }
 
 }  // namespace fw

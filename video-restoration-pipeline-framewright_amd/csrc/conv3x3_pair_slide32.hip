@@ -22,7 +22,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "fw_internal.h"
-#include "conv_common.h"
+#include "conv_pair_common.h"
 
 #ifndef FW_DMA_SLOT_W
 #define FW_DMA_SLOT_W 2
@@ -42,105 +42,18 @@ constexpr int P32_SKIP = P32_PIECES - 43 * 64;    // 3: the stage's first three 
                                                   // so that the other 2752 are exactly 43 wave-instructions: waves 0-3 and 7 issue
                                                   // five of them as one batch, waves 4-6 six (one M0 write per wave either way)
 constexpr int P32_CARRY = 2 * P32_ROWP;          // two x_a rows = 290 pieces
+// every pixel of a tile is a valid output; x_a (cr, cp) is row cr + 2, px cp + 2 of the x_a tile, whose rows have the pad piece
+using Slide32Geom = PairGeom<0, TILE_H - 1, 0, TILE_W - 1, 2, 2, P32_ROWP>;
 constexpr int P32_CARRY_PW = (P32_CARRY + NWAVES - 1) / NWAVES;   // 37 per wave
 
 struct Slide32Smem {
-    static constexpr int W_REGION = 2 * W_FRAGS * 64;
+    static constexpr int W_REGION = PAIR_W_REGION;
     static constexpr int W_BASE = 2 * P32_REGION;
     static constexpr int TOTAL = W_BASE + 2 * W_REGION;   // 10118 pieces = 161888 bytes
 };
 static_assert(NWAVES == 8 && RPW == 2, "written for 8 waves of 2 rows");
 static_assert(P32_SKIP >= 0 && P32_SKIP <= 4 && 5 * 5 + 3 * 6 == 43 && P32_CARRY_PW <= 64, "DMA plan");
 static_assert(Slide32Smem::TOTAL * 16 <= 160 * 1024, "LDS");
-
-// acc += A * B when `on` (wave-uniform) is non-zero, with the jump inside the statement: no control flow that hipcc can see.  The
-// operands come from LDS reads (the compiler waits for them ahead of the statement) and the accumulator is next touched tiles later,
-// so none of the MFMA's software wait states is at stake.
-template <typename T>
-__device__ __forceinline__ void mfma16_if(f32x4& acc, const uint4& a4, const uint4& b4, int on) {
-    const nt_u32x4 a = {a4.x, a4.y, a4.z, a4.w}, b = {b4.x, b4.y, b4.z, b4.w};   // (a HIP uint4 is a struct: no register constraint takes it)
-    on = __builtin_amdgcn_readfirstlane(on);   // provably scalar, even where hipcc has parked the flag in a vector register
-    if constexpr (std::is_same<T, __bf16>::value)
-        asm volatile("s_cmp_eq_u32 %3, 0\n\ts_cbranch_scc1 .Lfw_skip_%=\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0\n.Lfw_skip_%=:"
-                     : "+v"(acc) : "v"(a), "v"(b), "s"(on) : "scc");
-    else
-        asm volatile("s_cmp_eq_u32 %3, 0\n\ts_cbranch_scc1 .Lfw_skip_%=\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0\n.Lfw_skip_%=:"
-                     : "+v"(acc) : "v"(a), "v"(b), "s"(on) : "scc");
-}
-
-// One shared-chunk item with conv_b one row behind conv_a (conv3x3_pair_slide.hip: conv_item_lag), plus the extra conv_a column of
-// a wave that owns one (xon): its B fragment for tap (dy, dx) is piece xcol + dy * P32_ROWP + xdx[dx] of the stage (16 rows of one
-// halo pixel), its A fragment the one the row-shaped MFMAs of output-channel tile xct use at that tap.
-// Only waves 0-3 own an extra column, and the item must not branch on that in a way hipcc sees: a wave-uniform branch per step made
-// its waitcnt pass drain the LDS queue at every join (the item lost its read-ahead: +3.4 ms per frame), two whole variants of the
-// item under one branch spilled 44-126 registers.  So the two fragment reads are predicated per lane (xlane: true in every lane of
-// waves 0-3 - to the compiler a divergent condition, i.e. an EXEC mask around one ds_read, no branch) and the MFMA sits in an asm
-// statement that jumps over it when xon == 0 (mfma16_if).  wlx = wl + 64 * xct: the extra column's own A fragment (tile xct of
-// conv_a) is read a step ahead like the others, at a compile-time offset.  XCODE = false compiles all of it out (warm-up items).
-template <typename T, bool WITH_B, bool XCODE, typename WIdx, typename Slot>
-__device__ __forceinline__ void conv_item_lag32(f32x4 (&acc)[RPW][4][2], f32x4& accx, const uint4* a, const uint4* wl, const uint4* wlx,
-                                                const int (&rd_off)[3][2], const int (&xoff)[3], bool xlane, int xon, WIdx widx, Slot dma_slot) {
-    constexpr int NWU = WITH_B ? 4 : 2;
-    constexpr int NK = 9 * NWU;
-    constexpr int RING = 3;
-    constexpr int ROWP = P32_ROWP;
-    uint4 xr[5][2];
-    uint4 wf[RING];
-    uint4 xc = make_uint4(0, 0, 0, 0);   // the extra column's B fragment of the current tap: re-read once its MFMA has issued
-    uint4 wx = make_uint4(0, 0, 0, 0);   // ... and its A fragment
-    auto tile_of = [](int w) { return WITH_B ? ((w + 2) & 3) : w; };
-    auto load_w = [&](int k) {
-        const int t = k / NWU, w = k - t * NWU;
-        const int dx = t / 3, dy = t - 3 * dx;
-        wf[k % RING] = wl[widx(dy * 3 + dx, tile_of(w)) * 64];
-    };
-    auto load_row = [&](int h, int dx) {
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph) xr[h][ph] = a[h * ROWP + rd_off[dx][ph]];
-    };
-#pragma unroll
-    for (int h = 0; h < 5; ++h) load_row(h, 0);
-#pragma unroll
-    for (int k = 0; k < RING - 1; ++k) load_w(k);
-    if constexpr (XCODE) { if (xlane) xc = a[xoff[0]]; }   // tap (dy 0, dx 0)
-    FW_SB();
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int dx = t / 3, dy = t - 3 * dx;
-        if (dx < 2 && dy == 1) load_row(0, dx + 1);
-        if (dx < 2 && dy == 2) load_row(1, dx + 1);
-        if (dx > 0 && dy == 0) {
-            load_row(3, dx);
-            load_row(4, dx);
-        }
-#pragma unroll
-        for (int w = 0; w < NWU; ++w) {
-            const int k = t * NWU + w;
-            if (k + RING - 1 < NK) load_w(k + RING - 1);
-            FW_SB();
-            const int tile = tile_of(w);
-            const int lag = tile >= 2 ? 0 : 1;
-#pragma unroll
-            for (int row = 0; row < RPW; ++row)
-#pragma unroll
-                for (int ph = 0; ph < 2; ++ph)
-                    acc[row][tile][ph] = Op<T>::mfma16(wf[k % RING], xr[row + dy + lag][ph], acc[row][tile][ph]);
-            if constexpr (XCODE) {
-                if (w == 0) { if (xlane) wx = wlx[widx(dy * 3 + dx, 0) * 64]; }
-                if (w == NWU - 1) mfma16_if<T>(accx, wx, xc, xon);
-            }
-            FW_SB();
-#pragma unroll
-            for (int d = 0; d < 4 / NWU; ++d) dma_slot((t * NWU + w) * (4 / NWU) + d);
-            FW_SB();
-            if (dx < 2 && dy == 2 && w == (WITH_B ? 1 : 0)) load_row(2, dx + 1);
-        }
-        if (t + 1 < 9) {
-            const int dxn = (t + 1) / 3, dyn = (t + 1) - 3 * dxn;
-            if constexpr (XCODE) { if (xlane) xc = a[xoff[dxn] + dyn * ROWP]; }
-        }
-    }
-}
 
 // A shared chunk of a warm-up tile for a wave that owns an extra column and no rows: its nine column-shaped MFMAs only.
 template <typename T, typename WIdx>
@@ -167,15 +80,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     const int q = lane & 15;
     const int sl = lane >> 4;
 
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;
     const int tiles_x = (p.W + P32_TW - 1) / P32_TW;
     const int tiles_y = (p.H + P32_TH) / P32_TH;  // the last conv_b row H - 1 = 16 ty + 14 at the latest
     const int ntiles = tiles_x * tiles_y;         // column-major: t = tx * tiles_y + ty
-    const int t_lo = (int)((long)lb * ntiles / NB);
-    const int t_hi = (int)((long)(lb + 1) * ntiles / NB);
+    int t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
     const int needs_warm = (t_lo % tiles_y) != 0;  // the run starts below the top of a column: conv_a of the tile above first
     const int t_begin = t_lo - needs_warm;
@@ -188,14 +98,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     const int kib0 = 5 * wave + (wave > 4 ? (wave < 7 ? wave - 4 : 3) : 0);   // 0, 5, 10, 15, 20, 26, 32, 38
     constexpr int NBMAX = ACT_ITERS + 1;
     auto piece_idx = [&](int i) { return P32_SKIP + (kib0 + i) * 64 + lane; };
-    auto piece_off = [&](int idx) {
-        const int row = idx / ROWP;
-        int rm = idx - row * ROWP;
-        rm = rm < ROWP - 1 ? rm : ROWP - 2;
-        const int px = rm >> 2;
-        const int s = (rm & 3) ^ halo_swz(px);
-        return (unsigned)(((row * p.W + px) * p.in_cstride + s * 8) * 2);
-    };
+    auto piece_off = [&](int idx) { return halo_piece_off<ROWP>(idx, p.W, p.in_cstride); };
     unsigned relb[NBMAX];
 #pragma unroll
     for (int i = 0; i < NBMAX; ++i) relb[i] = (i < ACT_ITERS || six) ? piece_off(piece_idx(i)) + (unsigned)((4 - i) * 1024) : 0u;
@@ -223,11 +126,8 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         f_src = in + ((long)(R0 - 2) * p.W + (ox - 2)) * p.in_cstride * 2;
         f_ok = 0;
         auto inside = [&](int idx) {
-            const int row = idx / ROWP;
-            int rm = idx - row * ROWP;
-            rm = rm < ROWP - 1 ? rm : ROWP - 2;
-            const int px = rm >> 2;
-            return (unsigned)(R0 - 2 + row) < (unsigned)p.H && (unsigned)(ox - 2 + px) < (unsigned)p.W;
+            const HaloPiece h = halo_piece<ROWP>(idx);
+            return (unsigned)(R0 - 2 + h.row) < (unsigned)p.H && (unsigned)(ox - 2 + h.px) < (unsigned)p.W;
         };
 #pragma unroll
         for (int i = 0; i < NBMAX; ++i)
@@ -257,22 +157,14 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             f_src += chunk_bytes;
         }
     };
-    auto issue_w = [&](int j, int ws) {
-        const int half = wave / (NWAVES / 2), k = wave % (NWAVES / 2);
-        if (half == 1 || j < na)
-            issue_w_half((half ? wb_b : wa_b) + (size_t)j * (W_FRAGS * 1024),
-                         lds_base + (unsigned)(SM::W_BASE + ws * SM::W_REGION + W_FRAGS * half * 64) * 16u, k, lane16);
-    };
+    const PairIssueW<SM::W_BASE> issue_w{na, wa_b, wb_b, lds_base, lane16};  // (item j, weight stage, issuing wave)
 
     int rd_off[3][2];  // [dx][ph]: piece index of (halo row 2 * wave, column ox + 16 ph + q + dx - 1 = px 16 ph + q + dx + 1, slot sl)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            const int px = 16 * ph + q + dx + 1;
-            rd_off[dx][ph] = (RPW * wave) * ROWP + px * 4 + (sl ^ halo_swz(px));
-        }
-    auto widx = [](int tap, int w) { return w < 2 ? tap * 2 + w : W_FRAGS + tap * 2 + (w - 2); };
+        for (int ph = 0; ph < 2; ++ph) rd_off[dx][ph] = halo_rd_off<ROWP>(RPW * wave, 16 * ph + q + dx + 1, sl);
+    const PairWIdx widx;
 
     // ---- the extra conv_a column of waves 0-3: column ox - 1 (xcs 0) or ox + 32 (xcs 1), output-channel tile xct; lane = (row q of
     //      the tile, slot sl).  Tap (dy, dx) reads halo row q + dy + 1, px (xcs ? 33 : 0) + dx. ------------------------------------
@@ -286,60 +178,17 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     int xoff[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
-        const int px = (xcs ? 33 : 0) + dx;
-        xoff[dx] = (q + 1) * ROWP + px * 4 + (sl ^ halo_swz(px));
+        xoff[dx] = halo_rd_off<ROWP>(q + 1, (xcs ? 33 : 0) + dx, sl);
     }
 
     f32x4 acc[RPW][NW][2];
     f32x4 accx;
 
-    // ---- emit pieces (conv3x3_pair.hip has the lane map of the permlane swap) -----------------------------------------------
+    // ---- emit (conv_pair_common.h): all 32 columns of the tile are valid outputs: whole 2-KiB rows.  The wave's rows of x_a start
+    //      at image row R0 + 2 * wave, those of x_b one row higher -----------------------------------------------------------------
     const int ls = (sl & 1) ? 2 + (sl >> 1) : (sl >> 1);
     const unsigned st_off = (unsigned)((q * p.out_cstride + ls * 8) * 2);
-    auto convert = [&](int w0, uint4 (&pk)[RPW][2]) {
-#pragma unroll
-        for (int row = 0; row < RPW; ++row)
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const f32x4 va = lrelu4(w0 ? acc[row][2][ph] : acc[row][0][ph]);
-                const f32x4 vb = lrelu4(w0 ? acc[row][3][ph] : acc[row][1][ph]);
-                const uint2 pa = Op<T>::pack4(va[0], va[1], va[2], va[3]);
-                const uint2 pb = Op<T>::pack4(vb[0], vb[1], vb[2], vb[3]);
-                const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-                const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
-                pk[row][ph] = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-            }
-    };
-    // the wave's two rows start at image row gy0; all 32 columns of the tile are valid outputs: whole 2-KiB rows
-    auto store_out = [&](const uint4 (&pk)[RPW][2], int gy0, int ox, T* plane, auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int row = 0; row < RPW; ++row) {
-            const int gy = gy0 + row;
-            if (!INTERIOR && !((unsigned)gy < (unsigned)p.H)) continue;  // wave-uniform
-            char* rowbase = reinterpret_cast<char*>(plane) + ((long)gy * p.W + ox) * p.out_cstride * 2;
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const int cp = 16 * ph + q;
-                if (INTERIOR || ox + cp < p.W) store16(rowbase + (long)(16 * ph) * p.out_cstride * 2 + st_off, pk[row][ph]);
-            }
-        }
-    };
-    // conv_a row cr, column ox + cp of the tile -> x_a tile row cr + 2, px cp + 2 (zero outside the image = conv_b's zero padding)
-    auto write_xa = [&](const uint4 (&pk)[RPW][2], uint4* xa, int R0, int ox, auto interior_tag) {
-        constexpr bool INTERIOR = decltype(interior_tag)::value;
-#pragma unroll
-        for (int row = 0; row < RPW; ++row) {
-            const int cr = RPW * wave + row;
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-                const int cp = 16 * ph + q, hp = cp + 2;
-                uint4 v = pk[row][ph];
-                if (!INTERIOR && !((unsigned)(R0 + cr) < (unsigned)p.H && ox + cp < p.W)) v = make_uint4(0, 0, 0, 0);
-                xa[(cr + 2) * ROWP + hp * 4 + (ls ^ halo_swz(hp))] = v;
-            }
-        }
-    };
+    const PairEmit<Slide32Geom, T> emit{p, wave, q, ls, st_off, acc};
     // the extra column: lane (row q, channels 16 xct + 4 sl .. + 3) -> 8 bytes of x_a tile row q + 2, px 1 or 34
     auto write_xa_col = [&](uint4* xa, int R0, int ox) {
         const f32x4 v = lrelu4(accx);
@@ -355,7 +204,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
     const int ci = wave * P32_CARRY_PW + lane;
     const bool carry_lane = lane < P32_CARRY_PW && ci < P32_CARRY;
 
-    issue_w(0, 0);
+    issue_w.issue(0, 0, wave);
     issue_act(0);
 
     int n = 0;   // item counter (weight stage = n & 1)
@@ -387,7 +236,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             const int fetch_stage = (qd + 1) & 1;
             auto dma_slot = [&](int d) {
                 if (d == FW_DMA_SLOT_W) {
-                    if (more) issue_w(jn, (n + 1) & 1);
+                    if (more) issue_w.issue(jn, (n + 1) & 1, wave);
                 } else if (d == FW_DMA_SLOT_A) {
                     if (fetch) issue_act(fetch_stage);
                 }
@@ -397,12 +246,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
             auto& slot_fn = dma_slot;
             const uint4* wlx = wl + 64 * xct;
             if constexpr (KIND == 0) {
-                conv_item_lag32<T, true, true>(acc, accx, a, wl, wlx, rd_off, xoff, xlane, xon ? 1 : 0, widx, slot_fn);
+                conv_item_lag<ROWP, T, true>(acc, a, wl, rd_off, XCol{accx, wlx, xoff, xlane, xon ? 1 : 0}, widx, slot_fn);
             } else if constexpr (KIND == 1) {
                 // warm-up: only the carry rows (conv_a rows 14, 15 = the last wave's, and the same rows of the two extra columns) are
                 // wanted; the other waves just keep the DMA stream going
                 if (wave == NWAVES - 1) {
-                    conv_item_lag32<T, false, false>(acc, accx, a, wl, wlx, rd_off, xoff, false, 0, widx, slot_fn);
+                    conv_item_lag<ROWP, T, false>(acc, a, wl, rd_off, NoXCol{}, widx, slot_fn);
                 } else {
                     slot_fn(FW_DMA_SLOT_W);
                     slot_fn(FW_DMA_SLOT_A);
@@ -428,20 +277,20 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         // everything this tile computes and stores inside the image?  (uniform; the extra columns check for themselves)
         const bool interior = ox + P32_TW <= p.W && R0 >= 1 && R0 + P32_TH <= p.H;
         uint4 pk[RPW][2];
-        if (!warm || wave == NWAVES - 1) convert(0, pk);
+        if (!warm || wave == NWAVES - 1) emit.convert(0, pk);
         if (!warm) {
             if (interior)
-                store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::true_type{});
+                emit.template store_out<true>(pk, R0, ox, reinterpret_cast<T*>(p.out_a));
             else
-                store_out(pk, R0 + RPW * wave, ox, reinterpret_cast<T*>(p.out_a), std::false_type{});
+                emit.template store_out<false>(pk, R0, ox, reinterpret_cast<T*>(p.out_a));
         }
         __syncthreads();  // every wave is done with the last chunk's stage: it becomes the x_a tile
         uint4* xa = lds + ((qd - 1) & 1) * P32_REGION;
         if (!warm || wave == NWAVES - 1) {
             if (interior)
-                write_xa(pk, xa, R0, ox, std::true_type{});
+                emit.template write_xa<true>(pk, xa, R0, ox);
             else
-                write_xa(pk, xa, R0, ox, std::false_type{});
+                emit.template write_xa<false>(pk, xa, R0, ox);
         }
         if (xon) write_xa_col(xa, R0, ox);
         if (!warm) {
@@ -457,11 +306,11 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_pair_slid
         if (!warm) {
             // conv_b done for this wave: rows R0 - 1 + (2w, 2w + 1).  In flight: the x_a stores (an item old), the next weights.
             FW_WAIT_VMCNT(0);
-            convert(2, pk);
+            emit.convert(2, pk);
             if (interior)
-                store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::true_type{});
+                emit.template store_out<true>(pk, R0 - 1, ox, reinterpret_cast<T*>(p.out_b));
             else
-                store_out(pk, R0 - 1 + RPW * wave, ox, reinterpret_cast<T*>(p.out_b), std::false_type{});
+                emit.template store_out<false>(pk, R0 - 1, ox, reinterpret_cast<T*>(p.out_b));
         }
     }
 }
@@ -481,12 +330,7 @@ bool pair_slide32_enabled() {
 
 void launch_conv3x3_pair_slide32(DType dt, const ConvPairParams& p, int num_cus, hipStream_t stream) {
     const int tiles = ((p.W + P32_TW - 1) / P32_TW) * ((p.H + P32_TH) / P32_TH);
-    dim3 grid(tiles < num_cus ? tiles : num_cus), block(64 * NWAVES);
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((conv3x3_pair_slide32_kernel<__bf16>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((conv3x3_pair_slide32_kernel<_Float16>), grid, block, 0, stream, p);
-    FW_HIP_CHECK(hipGetLastError());
+    launch_pair_kernel(conv3x3_pair_slide32_kernel<__bf16>, conv3x3_pair_slide32_kernel<_Float16>, dt, tiles, num_cus, p, stream);
 }
 
 }  // namespace fw

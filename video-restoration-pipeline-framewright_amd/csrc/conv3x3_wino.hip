@@ -92,15 +92,12 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_wino_spli
     const int j = lane & 15;    // column pair of the tile (columns 2j, 2j + 1); output channel within a tile for A fragments
     const int sl = lane >> 4;   // 8-channel slot of the chunk; 4-channel group of a D tile
 
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;
     const int tiles_x = (p.W + TILE_W - 1) / TILE_W;
     const int tiles_y = (p.H + TILE_H - 1) / TILE_H;
     const int ntiles = tiles_x * tiles_y;
-    const int t_lo = (int)((long)lb * ntiles / NB);
-    const int t_hi = (int)((long)(lb + 1) * ntiles / NB);
+    int t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
     const int nch = p.cin_chunks;
     const int nitems = (t_hi - t_lo) * nch;
@@ -388,12 +385,8 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_wino_spli
                             oa = oa - Op<T>::unpack4(Op<T>::pack4(oa[0], oa[1], oa[2], oa[3]));
                             ob = ob - Op<T>::unpack4(Op<T>::pack4(ob[0], ob[1], ob[2], ob[3]));
                         }
-                        const uint2 pa = Op<T>::pack4(oa[0], oa[1], oa[2], oa[3]);
-                        const uint2 pb = Op<T>::pack4(ob[0], ob[1], ob[2], ob[3]);
-                        const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-                        const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
-                        if (x0 + 2 * j + e < p.W)
-                            store16(lane_base + rowoff + (long)e * p.out_cstride * 2 + (long)c2 * p.out_pstride * 2, make_uint4(sx[0], sy[0], sx[1], sy[1]));
+                        const uint4 v = pair16<T>(oa, ob);
+                        if (x0 + 2 * j + e < p.W) store16(lane_base + rowoff + (long)e * p.out_cstride * 2 + (long)c2 * p.out_pstride * 2, v);
                     }
             }
         }

@@ -1,4 +1,6 @@
-// Device-side pieces shared by the conv3x3 MFMA kernels (conv3x3_mfma.hip, conv3x3_pair.hip).  gfx950 only.
+// Device-side pieces shared by the MFMA kernels that stage their operands by LDS-DMA: conv3x3_mfma.hip, conv3x3_pair.hip,
+// conv3x3_pair_slide.hip, conv3x3_pair_slide32.hip, conv3x3_wino.hip, conv_up2x_phase.hip, pointwise_gemm.hip, pw_dw_fused.hip and
+// naf_tail128.hip.  What only the three fused-pair kernels share is in conv_pair_common.h.  gfx950 only.
 #pragma once
 #include "fw_internal.h"
 
@@ -69,6 +71,23 @@ __device__ __forceinline__ void store16(void* dst, uint4 v) {
 #endif
 }
 
+// Two 8-byte D fragments -> one 16-byte slot.  A lane's D fragments hold channels 4*sl.. of 16-channel tile w0 (a) and of tile
+// w0+1 (b) for its pixel (8 B each once packed).  One v_permlane16_swap per dword (rows of 16 lanes: odd rows of the first
+// operand <-> even rows of the second) leaves every lane with 16 contiguous bytes: lanes with even sl get channels 4*sl..4*sl+7
+// of tile w0 (their own 8 B + those of lane ^ 16), lanes with odd sl channels 4*(sl-1)..+7 of tile w0+1.  That is one whole
+// 8-channel slot of the pixel:
+//     ls = sl even ? sl / 2 : 2 + sl / 2
+// so a global store is 16 B per lane / 64 contiguous bytes per pixel straight from registers, and an LDS tile in the halo
+// format takes one ds_write_b128 per fragment.  No transpose through LDS, no barrier.
+template <typename T>
+__device__ __forceinline__ uint4 pair16(f32x4 a, f32x4 b) {
+    const uint2 pa = Op<T>::pack4(a[0], a[1], a[2], a[3]);
+    const uint2 pb = Op<T>::pack4(b[0], b[1], b[2], b[3]);
+    const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
+    const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
+    return make_uint4(sx[0], sy[0], sx[1], sy[1]);
+}
+
 constexpr int TILE_H = 16;
 constexpr int TILE_W = 32;
 constexpr int HALO_H = TILE_H + 2;                        // 18
@@ -117,6 +136,50 @@ __device__ __forceinline__ void tile_pos(int t, int tiles_x, int tiles_y, int* t
 
 __host__ __device__ constexpr int halo_swz(int px) { return ((px >> 2) & 1) << 1; }
 
+// Persistent workgroups: each owns a contiguous share of a kernel's linear tile (or item) index.  Blocks b and b+8 share an XCD
+// (and its L2): the logical id lb puts the blocks of one XCD on a contiguous band, so neighbouring tiles (shared halo rows) and
+// the weights are served by one L2.  Construct it FIRST and call range() once the tile count is known: the kernels' scalar
+// prologues are scheduled in that order.
+struct TileBand {
+    int nb, lb;
+    __device__ __forceinline__ TileBand() : nb(gridDim.x) {
+        const int xcd = blockIdx.x & 7;
+        const int qn = nb >> 3, rn = nb & 7;
+        lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    }
+    // [*t_lo, *t_hi) of ntiles
+    template <typename I>
+    __device__ __forceinline__ void range(I ntiles, I* t_lo, I* t_hi) const {
+        *t_lo = (I)((long)lb * ntiles / nb);
+        *t_hi = (I)((long)(lb + 1) * ntiles / nb);
+    }
+};
+
+// Piece idx of a halo image with ROWP pieces per row: (halo row, halo px, the 8-channel slot that lands there).  A row pitch that
+// is no multiple of 4 has pad pieces behind the last pixel (conv3x3_pair_slide32.hip: 145); they repeat the piece before them.
+struct HaloPiece {
+    int row, px, s;
+};
+template <int ROWP = ROW_PIECES>
+__device__ __forceinline__ HaloPiece halo_piece(int idx) {
+    const int row = idx / ROWP;
+    int rm = idx - row * ROWP;
+    if constexpr ((ROWP & 3) != 0) rm = rm < ROWP - 1 ? rm : ROWP - 2;
+    const int px = rm >> 2;
+    return {row, px, (rm & 3) ^ halo_swz(px)};
+}
+// Its byte offset from the halo origin in an NHWC plane of W pixels per row, cstride elements per pixel: the per-lane DMA source
+template <int ROWP = ROW_PIECES>
+__device__ __forceinline__ unsigned halo_piece_off(int idx, int W, int cstride) {
+    const HaloPiece h = halo_piece<ROWP>(idx);
+    return (unsigned)(((h.row * W + h.px) * cstride + h.s * 8) * 2);
+}
+
+// Fragment-read plan: the piece index of (halo row, halo px, channel slot sl) in a stage of ROWP pieces per row.  A kernel's
+// rd_off[dx][ph] is this for (the wave's first halo row, px 16*ph + q + dx [+ the column of its first output], sl).
+template <int ROWP = ROW_PIECES>
+__device__ __forceinline__ int halo_rd_off(int row, int px, int sl) { return row * ROWP + px * 4 + (sl ^ halo_swz(px)); }
+
 template <int CT>
 struct Smem {
     static constexpr int NA = CT == 1 ? 3 : 2;                  // activation stages in flight
@@ -135,12 +198,15 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // first ds_read of the chunk being computed, which serialises the pipeline (cdna_hip_programming.md §5 "Three .s-level
 // traps" (b)).  The matching waits are the explicit counted vmcnt at the top of the chunk loop.  M0 is written inside the
 // statement; nothing else in these kernels uses M0.  Inactive lanes (EXEC) neither load nor write LDS.
-__device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
+__device__ __forceinline__ unsigned long long uniform_base(const void* sbase) {
     // wave-uniform by construction; readfirstlane makes it provably so where the compiler has lost track (SGPR operands)
     const unsigned long long b = (unsigned long long)sbase;
     // (the builtin returns int: without the casts the low half would be sign-extended over the high half)
-    const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
+           (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
+}
+__device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
+    const unsigned long long sb = uniform_base(sbase);
     lds_dst = __builtin_amdgcn_readfirstlane(lds_dst);
     // s_nop 4: an SGPR written by v_readfirstlane must not be read as the base of a global_* for 5 wait states, and
     // nothing inside an asm statement is padded by hipcc
@@ -163,9 +229,7 @@ __device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigne
 template <int N>
 __device__ __forceinline__ void glds16_batch_w(const void* sbase, unsigned voff, unsigned lds_piece4) {
     static_assert(N >= 3 && N <= 5, "batch sizes in use");
-    const unsigned long long b = (unsigned long long)sbase;
-    const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
+    const unsigned long long sb = uniform_base(sbase);
     lds_piece4 = __builtin_amdgcn_readfirstlane(lds_piece4);
     if constexpr (N == 5)
         asm volatile(
@@ -206,9 +270,7 @@ __device__ __forceinline__ void glds16_batch_w(const void* sbase, unsigned voff,
 }
 // Five pieces with their own per-lane offsets (activations); voff[i] already contains -(i - 4) KiB.
 __device__ __forceinline__ void glds16_batch_a(const void* sbase, const unsigned* voff, unsigned lds_piece4) {
-    const unsigned long long b = (unsigned long long)sbase;
-    const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
+    const unsigned long long sb = uniform_base(sbase);
     lds_piece4 = __builtin_amdgcn_readfirstlane(lds_piece4);
     asm volatile(
         "s_nop 4\n\t"
@@ -227,9 +289,7 @@ __device__ __forceinline__ void glds16_batch_a(const void* sbase, const unsigned
 // Six pieces with their own per-lane offsets: the fifth piece is M0's, the sixth sits one KiB above it; voff[i] already contains
 // -(i - 4) KiB (conv3x3_pair_slide32.hip: 43 KiB per stage over eight waves = five waves of 5 and three of 6).
 __device__ __forceinline__ void glds16_batch_a6(const void* sbase, const unsigned* voff, unsigned lds_piece4) {
-    const unsigned long long b = (unsigned long long)sbase;
-    const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
+    const unsigned long long sb = uniform_base(sbase);
     lds_piece4 = __builtin_amdgcn_readfirstlane(lds_piece4);
     asm volatile(
         "s_nop 4\n\t"
@@ -249,9 +309,7 @@ __device__ __forceinline__ void glds16_batch_a6(const void* sbase, const unsigne
 // Four pieces with their own per-lane offsets (the GEMM kernel's activation rows); voff[i] already contains -(i - 3) KiB and
 // lds_piece3 is the LDS address of the FOURTH piece.
 __device__ __forceinline__ void glds16_batch_a4(const void* sbase, const unsigned* voff, unsigned lds_piece3) {
-    const unsigned long long b = (unsigned long long)sbase;
-    const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
+    const unsigned long long sb = uniform_base(sbase);
     lds_piece3 = __builtin_amdgcn_readfirstlane(lds_piece3);
     asm volatile(
         "s_nop 4\n\t"

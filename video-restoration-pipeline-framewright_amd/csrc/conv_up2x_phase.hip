@@ -115,29 +115,20 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv_up2x_phase_k
     const int q = lane & 15;
     const int sl = lane >> 4;
 
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;
     const int tiles_x = (p.W + TILE_W - 1) / TILE_W;
     const int tiles_y = (p.H + TILE_H - 1) / TILE_H;
     const int ntiles = tiles_x * tiles_y;
-    const int t_lo = (int)((long)lb * ntiles / NB);
-    const int t_hi = (int)((long)(lb + 1) * ntiles / NB);
+    int t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
     const int nitems = (t_hi - t_lo) * 4;
 
     // ---- per-lane DMA plan of the 18 x 34 source halo (conv3x3_mfma.hip without the gather) ------------------------------------
     unsigned relb[ACT_ITERS];
 #pragma unroll
-    for (int i = 0; i < ACT_ITERS; ++i) {
-        const int idx = (ACT_ITERS * wave + i) * 64 + lane;
-        const int row = idx / ROW_PIECES;
-        const int rm = idx - row * ROW_PIECES;
-        const int px = rm >> 2;
-        const int s = (rm & 3) ^ halo_swz(px);
-        relb[i] = (unsigned)(((row * p.W + px) * p.in_cstride + s * 8) * 2) + (unsigned)(4 - i) * 1024u;
-    }
+    for (int i = 0; i < ACT_ITERS; ++i)
+        relb[i] = halo_piece_off((ACT_ITERS * wave + i) * 64 + lane, p.W, p.in_cstride) + (unsigned)(4 - i) * 1024u;
     const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)lds;
     const char* in = reinterpret_cast<const char*>(p.in);
     const char* w_b = reinterpret_cast<const char*>(p.wpk);
@@ -154,9 +145,8 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv_up2x_phase_k
 #pragma unroll
         for (int i = 0; i < ACT_ITERS; ++i) {
             const int idx = (ACT_ITERS * wave + i) * 64 + lane;
-            const int row = idx / ROW_PIECES;
-            const int px = (idx - row * ROW_PIECES) >> 2;
-            if (idx < ACT_PIECES && (unsigned)(ty0 - 1 + row) < (unsigned)p.H && (unsigned)(tx0 - 1 + px) < (unsigned)p.W) ok |= 1u << i;
+            const HaloPiece h = halo_piece(idx);
+            if (idx < ACT_PIECES && (unsigned)(ty0 - 1 + h.row) < (unsigned)p.H && (unsigned)(tx0 - 1 + h.px) < (unsigned)p.W) ok |= 1u << i;
         }
         const bool all = __builtin_amdgcn_readfirstlane(__all(ok == (1u << ACT_ITERS) - 1u)) != 0;
         const unsigned dst = (unsigned)(c * ACT_REGION + ACT_ITERS * wave * 64);
@@ -180,10 +170,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv_up2x_phase_k
 #pragma unroll
     for (int tx = 0; tx < 3; ++tx)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            const int px = 16 * ph + q + tx;
-            rd_off[tx][ph] = (RPW * wave) * ROW_PIECES + px * 4 + (sl ^ halo_swz(px));
-        }
+        for (int ph = 0; ph < 2; ++ph) rd_off[tx][ph] = halo_rd_off(RPW * wave, 16 * ph + q + tx, sl);
 
     f32x4 acc[RPW][8][2];  // [row][4 * column phase b + 16-channel tile w][16-pixel half]
     const int ls = (sl & 1) ? 2 + (sl >> 1) : (sl >> 1);   // the 8-channel slot this lane holds after the permlane swap
@@ -262,11 +249,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv_up2x_phase_k
                                     oa = lrelu4(oa);
                                     ob = lrelu4(ob);
                                 }
-                                const uint2 pa = Op<T>::pack4(oa[0], oa[1], oa[2], oa[3]);
-                                const uint2 pb = Op<T>::pack4(ob[0], ob[1], ob[2], ob[3]);
-                                const u32x2 sx = __builtin_amdgcn_permlane16_swap(pa.x, pb.x, false, false);
-                                const u32x2 sy = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
-                                v[b] = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+                                v[b] = pair16<T>(oa, ob);
                             }
                             char* base = rowbase + (long)c2 * p.out_pstride * 2 + (long)(32 * ph) * p.out_cstride * 2;
 #if FW_UP_FULL_LINES
@@ -296,8 +279,6 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv_up2x_phase_k
         }
     }
 }
-
-int conv_num_cus();
 
 void launch_conv_up2x_phase(DType dt, const ConvUpParams& p_in, hipStream_t stream) {
     ConvUpParams p = p_in;

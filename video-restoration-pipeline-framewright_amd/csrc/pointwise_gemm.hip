@@ -43,14 +43,12 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_kernel(const PointwiseParams p
     const int lane = tid & 63, q = lane & 15, sl = lane >> 4;
     const int pg = wave & 3, ch = wave >> 2;   // pixel group (64 px), channel half (8 tiles of 16)
 
-    const int NB = gridDim.x;
-    const int xcd = blockIdx.x & 7;
-    const int qn = NB >> 3, rn = NB & 7;
-    const int lb = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const TileBand band;
     const int n_tiles = p.N_tiles / 8 * NH;                  // 256- (NH = 2: 128-) channel tiles (N_tiles counts 32-channel tiles)
     const long m_tiles = (p.M + G_PX - 1) / G_PX;
     const long ntiles = m_tiles * n_tiles;                   // t = mt * n_tiles + nt: a workgroup's consecutive tiles share A rows
-    const long t_lo = lb * ntiles / NB, t_hi = (long)(lb + 1) * ntiles / NB;
+    long t_lo, t_hi;
+    band.range(ntiles, &t_lo, &t_hi);
     if (t_lo >= t_hi) return;
     const int nkb = p.K / G_KB;
     const long nitems = (t_hi - t_lo) * nkb;
