@@ -211,6 +211,22 @@ int fw_conv3x3_split_nhwc(int dtype, int winograd, const void* x, int in_cstride
 int fw_conv3x3_wino_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int height, int width,
                          const void* packed_weight, const float* bias, int act_lrelu, void* out, int out_cstride,
                          long out_plane_stride, int out_coff, void* stream);
+/* The tail of the RRDBNet, conv_last(lrelu(conv_hr(x), 0.2)): 64 -> 64 -> 3 channels at the output resolution, written as an image
+ * (out_u8: uint8 BGR = clamp -> x255 -> rint; out_u16: uint16 BGR, x65535; out_rgb_f32: float RGB, un-clamped; any of them may be
+ * NULL, not all), cropped to img_height x img_width <= height x width.  x, the padding and the strides as in fw_conv3x3_nhwc.
+ *   fused = 0: the two launches, conv_hr into scratch_u3 (two 32-channel planes [height][width][32] of the operand type), conv_last
+ *              out of it; packed_w_hr = fw_pack_conv3x3(cout 64, cin 64, 2, 2), packed_w_last = fw_pack_conv3x3(cout 3, cin 64, 1, 2).
+ *   fused = 1: one launch that keeps the 64-channel map on the chip (scratch_u3 and packed_w_last are not used);
+ *              packed_w_last_pw = fw_pack_conv_last_pointwise(...).
+ * bias_hr: 64 floats; bias_last: 32 floats (3 used, the rest zero).  The two forms round the 64-channel map to the operand type at
+ * the same point and differ only in the fp32 summation order of conv_last.
+ * fw_pack_conv_last_pointwise packs conv_last's torch-layout weight [3][64][3][3] (host fp32) into the fused form's six matrix
+ * fragments; returns the number of uint16, dst = NULL to size the buffer. */
+size_t fw_pack_conv_last_pointwise(int dtype, const float* weight, uint16_t* dst);
+int fw_conv3x3_hr_last_nhwc(int dtype, int fused, const void* x, int in_cstride, long in_plane_stride, int height, int width,
+                            const void* packed_w_hr, const float* bias_hr, const void* packed_w_last, const void* packed_w_last_pw,
+                            const float* bias_last, void* scratch_u3, int img_height, int img_width, uint8_t* out_u8,
+                            uint16_t* out_u16, float* out_rgb_f32, void* stream);
 /* Self-check of the Winograd launchers' argument checks (host only, no device call, nothing launched): for each of the fields
  * the Winograd kernels do not implement (post_act, chan_scale, res1, res2, out_f32, n_groups > 1, act in the split form, in_id_scale /
  * id_scale not exact in f16; out_f32, n_groups, chan_scale, post_act, res1, PReLU and out_lo in the STORE form), one otherwise valid

@@ -63,6 +63,13 @@ for fr in frames:
     names = ["u8 -> NHWC", "conv_first", "conv_body", "conv_up1 (phase)", "conv_up2 (phase)", "conv_hr", "conv_last"]
     algs = [0, gflop(3, 64), gflop(64, 64), gflop(64, 64, 4 * px), gflop(64, 64, 16 * px), gflop(64, 64, 16 * px), gflop(64, 3, 16 * px)]
     exes = [0, gflop(32, 64), gflop(64, 64), gflop(64, 64, 4 * px) * 4 / 9, gflop(64, 64, 16 * px) * 4 / 9, gflop(64, 64, 16 * px), gflop(64, 32, 16 * px)]
+    if len(rest) == len(names) - 1 and "hr_last" in rest[-1][0]:
+        # the fused tail (conv3x3_hr_last_kernel): one launch with the algorithmic FLOPs of both convs; it executes conv_hr's 288 MFMAs
+        # per wave and tile plus 24 of the pointwise step, on 30-column tiles with the outputs one row behind
+        tiles_tail = -(-4 * W // 30) * ((4 * H + 16) // 16)
+        names = names[:5] + ["conv_hr + conv_last (fused)"]
+        algs = algs[:5] + [algs[5] + algs[6]]
+        exes = exes[:5] + [gflop(64, 64, tiles_tail * 512) * 312 / 288]
     if len(rest) == len(names):
         for (nm, d), n, a, e in zip(rest, names, algs, exes):
             add(n, d / 1e3, a, e)

@@ -76,8 +76,17 @@ m = re.search(r"frame: ([\d.]+) ms of kernels.*bench ([\d.]+) ms -> ([\d.]+) J p
 g = lambda n: tbl[n]
 c5name = "conv5 of rdb1 / rdb2, Winograd F(2, 3) rows" if "conv5 of rdb1 / rdb2, Winograd F(2, 3) rows" in tbl else "conv5 of rdb1 / rdb2"
 p12, p34, c5a, c5b = g("pair conv1+conv2"), g("pair conv3+conv4"), g(c5name), g("conv5 of rdb3 (+ R hi, R lo; writes hi + lo)")
-first, body, up1, up2, hr, last = g("conv_first"), g("conv_body"), g("conv_up1 (phase)"), g("conv_up2 (phase)"), g("conv_hr"), g("conv_last")
+first, body, up1, up2 = g("conv_first"), g("conv_body"), g("conv_up1 (phase)"), g("conv_up2 (phase)")
 f = float
+if "conv_hr + conv_last (fused)" in tbl:   # the tail as one launch (conv3x3_hr_last_kernel)
+    t = g("conv_hr + conv_last (fused)")
+    tail_rows = f"| conv_hr + conv_last in one launch (`conv3x3_hr_last_kernel`, image store) | 1 | {t[2]} | {t[3]} | {t[4]} | {t[5]} | {t[6]} | {t[7]} |"
+    n_launch = 213
+else:
+    hr, last = g("conv_hr"), g("conv_last")
+    tail_rows = (f"| conv_hr | 1 | {hr[2]} | {hr[3]} | {hr[4]} | 1.000 | {hr[6]} | {hr[7]} |\n"
+                 f"| conv_last (64 → 3, image store) | 1 | {last[2]} | {last[3]} | 0.04 (HBM-bound: 4.25 GB read) | – | {last[6]} | – |")
+    n_launch = 214
 new = f'''| launch class | per frame | ms | avg launch µs | of MFMA peak | executed / algorithmic MACs | J | pJ per algorithmic FLOP |
 |---|---|---|---|---|---|---|---|
 | pair conv1+conv2 (`conv3x3_pair_slide_kernel`) | 69 | {p12[2]} | {p12[3]} | {p12[4]} | {p12[5]} | {p12[6]} | {p12[7]} |
@@ -86,9 +95,8 @@ new = f'''| launch class | per frame | ms | avg launch µs | of MFMA peak | exec
 | conv5 of rdb3 (`conv3x3_mfma_kernel<2, split>`; + R hi, R lo; writes hi + lo) | 23 | {c5b[2]} | {c5b[3]} | {c5b[4]} | {c5b[5]} | {c5b[6]} | {c5b[7]} |
 | conv_first / conv_body | 2 | {f(first[2]) + f(body[2]):.2f} | – | – | – | {f(first[6]) + f(body[6]):.1f} | – |
 | conv_up1 / conv_up2 as four 2×2 phase convs | 2 | {f(up1[2]) + f(up2[2]):.2f} | – | {up1[4]} / {up2[4]} | 0.444 | {f(up1[6]) + f(up2[6]):.1f} | {up2[7]} |
-| conv_hr | 1 | {hr[2]} | {hr[3]} | {hr[4]} | 1.000 | {hr[6]} | {hr[7]} |
-| conv_last (64 → 3, image store) | 1 | {last[2]} | {last[3]} | 0.04 (HBM-bound: 4.25 GB read) | – | {last[6]} | – |
-| **frame** | 214 | **{f(m.group(1)):.1f}** (bench {f(m.group(2)):.1f}) | | **{sr['roofline']['frac']:.2f}** | 1.05 | **{f(m.group(3)):.1f} J** | **{m.group(4)}** |
+{tail_rows}
+| **frame** | {n_launch} | **{f(m.group(1)):.1f}** (bench {f(m.group(2)):.1f}) | | **{sr['roofline']['frac']:.2f}** | 1.05 | **{f(m.group(3)):.1f} J** | **{m.group(4)}** |
 
 '''
 a, e = s.index("| launch class | per frame | ms | avg launch µs |"), s.index("Executed MACs: pairs × 1.067")

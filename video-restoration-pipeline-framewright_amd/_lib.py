@@ -44,6 +44,7 @@ EXPORTS = [
     "fw_attn_matrix", "fw_attn_apply", "fw_attn_pack", "fw_attn_proj_pack", "fw_pixel_shuffle2_f32", "fw_copy_channels_f32", "fw_f32_to_planar", "fw_tap_post_u8",
     "fw_flow_accumulate_u8", "fw_flow_accumulate_finish_u8", "fw_resize_lanczos4_u8", "fw_resize_linear_u8", "fw_face_paste_u8", "fw_grain_addback_u8", "fw_attn_softmax_rows", "fw_pack_pointwise_transposed", "fw_attn_qk_scratch_elems", "fw_attn_matrix_mfma",
     "fw_pack_conv3x3_wino", "fw_conv3x3_split_nhwc", "fw_conv3x3_wino_nhwc", "fw_conv3x3_wino_check_fields",
+    "fw_pack_conv_last_pointwise", "fw_conv3x3_hr_last_nhwc",
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
@@ -169,6 +170,10 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_conv3x3_wino_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, i32, vp, i32, C.c_long, i32, vp]
     lib.fw_conv3x3_wino_check_fields.restype = i32
     lib.fw_conv3x3_wino_check_fields.argtypes = [C.POINTER(i32), i32]
+    lib.fw_pack_conv_last_pointwise.restype = sz
+    lib.fw_pack_conv_last_pointwise.argtypes = [i32, vp, vp]
+    lib.fw_conv3x3_hr_last_nhwc.restype = i32
+    lib.fw_conv3x3_hr_last_nhwc.argtypes = [i32, i32, vp, i32, C.c_long, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.fw_conv3x3_pair_nhwc.restype = i32
     lib.fw_conv3x3_pair_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.fw_u8_to_rgb_f32.restype = i32

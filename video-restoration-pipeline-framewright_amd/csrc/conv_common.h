@@ -1,6 +1,6 @@
 // Device-side pieces shared by the MFMA kernels that stage their operands by LDS-DMA: conv3x3_mfma.hip, conv3x3_pair.hip,
-// conv3x3_pair_slide.hip, conv3x3_pair_slide32.hip, conv3x3_wino.hip, conv_up2x_phase.hip, pointwise_gemm.hip, pw_dw_fused.hip and
-// naf_tail128.hip.  What only the three fused-pair kernels share is in conv_pair_common.h.  gfx950 only.
+// conv3x3_pair_slide.hip, conv3x3_pair_slide32.hip, conv3x3_wino.hip, conv3x3_hr_last.hip, conv_up2x_phase.hip, pointwise_gemm.hip,
+// pw_dw_fused.hip and naf_tail128.hip.  What only the three fused-pair kernels share is in conv_pair_common.h.  gfx950 only.
 #pragma once
 #include "fw_internal.h"
 

@@ -127,6 +127,14 @@ void launch_conv_up2x_phase(DType dt, const ConvUpParams& p, hipStream_t stream)
 size_t pack_conv_up2x_phase_weights(DType dt, const float* w, uint16_t* dst);
 int conv_num_cus();     // persistent workgroups per conv launch (CUs of the current device, FW_CONV_GRID)
 
+// conv_last(lrelu(conv_hr(x))) in one launch, the 64-channel map between them never stored (conv3x3_hr_last.hip).  `hr` = conv_hr's
+// ConvParams as for launch_conv3x3(dt, 2, EPI_STORE, ...) (in, strides, H, W, wpk, bias; `out` is not used) plus EPI_IMAGE's outputs
+// (out_u8 / out_u16 / out_rgb, img_H, img_W); wlast = pack_conv_last_pointwise's fragments, bias_last = conv_last's bias (>= 3 floats).
+void launch_conv3x3_hr_last(DType dt, const ConvParams& hr, const void* wlast, const float* bias_last, hipStream_t stream);
+// w[3][64][3][3] fp32 -> the six A fragments of the fused tail's pointwise step (returns the number of uint16; dst may be null to query)
+size_t pack_conv_last_pointwise(DType dt, const float* w, uint16_t* dst);
+bool hr_last_default(int H, int W);   // the fused tail's size rule: at least six steps per workgroup
+
 // Launches the kernel; cout_tiles in {1,2} (32 or 64 output channels).
 void launch_conv3x3(DType dt, int cout_tiles, ConvEpilogue epi, const ConvParams& p, hipStream_t stream);
 

@@ -23,6 +23,7 @@ struct ConvLayer {
     float* d_b = nullptr;
     void* d_wphase = nullptr;   // conv_up1 / conv_up2: the same weights as four 2x2 phase convolutions (conv_up2x_phase.hip)
     void* d_wwino = nullptr;    // conv5 of a dense block, f16: the same weights as row-wise Winograd fragments (conv3x3_wino.hip)
+    void* d_wlast = nullptr;    // conv_last: the same weights as the pointwise fragments of the fused tail (conv3x3_hr_last.hip)
     bool set = false;
 };
 
@@ -66,6 +67,9 @@ struct fw_rrdbnet {
     // and is 1 ms SLOWER than the direct kernel there: profiles/r03_ab/conv5_winograd_rows.txt)
     int c5_wino = 1;
     bool hr_wino = false;   // conv_hr at the output resolution in the same form (FW_RRDB_HR_WINO=1)
+    // conv_hr + conv_last in one launch, the 64-channel map at the output resolution never stored (conv3x3_hr_last.hip).
+    // FW_RRDB_HR_LAST: 0 never, 1 always, unset (-1): when a workgroup gets at least six steps (hr_last_default)
+    int hr_last = -1;
     int abl_rdb3 = 0;   // TIMING-ONLY ablation of rdb3's conv5 (wrong pixels): 1 no lo write, 2 no R lo planes, 4 no R hi planes (FW_RRDB_ABL_RDB3)
     // hipGraph capture of the per-frame forward (BASELINE configs[4] "hipGraph-captured per-frame stages").  graph_mode: 0 never
     // (default), 1 always, 2 for frames of at most graph_max_px input pixels.  Off by default because it buys nothing here: the
@@ -168,6 +172,8 @@ void free_layer(ConvLayer& l) {
     if (l.d_b) (void)hipFree(l.d_b);
     if (l.d_wphase) (void)hipFree(l.d_wphase);
     if (l.d_wwino) (void)hipFree(l.d_wwino);
+    if (l.d_wlast) (void)hipFree(l.d_wlast);
+    l.d_wlast = nullptr;
     l.d_wphase = nullptr;
     l.d_wwino = nullptr;
     l.d_w = nullptr;
@@ -411,16 +417,44 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     run_up(n->conv_up1, cat[cur], PL, Ht, Wt, U1, 4 * PL);
     run_up(n->conv_up2, U1, 4 * PL, 2 * Ht, 2 * Wt, U2, 16 * PL);
     // conv_last(lrelu(conv_hr(feat)))                                              (:268)
+    ConvParams hr = base;
+    hr.H = 4 * Ht;
+    hr.W = 4 * Wt;
+    hr.in = U2;
+    hr.in_pstride = 16 * PL;
+    ConvParams img = base;
+    img.H = 4 * Ht;
+    img.W = 4 * Wt;
+    if (bits == 16)
+        img.out_u16 = (uint16_t*)d_out;
+    else
+        img.out_u8 = (uint8_t*)d_out;
+    img.out_rgb = d_rgb;
+    img.img_H = n->scale * H;  // crops the mod-pad of the x2 model
+    img.img_W = n->scale * W;
+    const bool hr_wino = n->c5_wino && n->dt == DT_F16 && n->conv_hr.d_wwino && n->hr_wino;
+    if (!hr_wino && (n->hr_last < 0 ? hr_last_default(hr.H, hr.W) : n->hr_last != 0)) {
+        // one launch, U3 never written: the algorithmic FLOPs of both convs
+        ConvParams p = hr;
+        p.out_u8 = img.out_u8;
+        p.out_u16 = img.out_u16;
+        p.out_rgb = img.out_rgb;
+        p.img_H = img.img_H;
+        p.img_W = img.img_W;
+        p.cin_chunks = n->conv_hr.chunks;
+        p.wpk = n->conv_hr.d_w;
+        p.bias = n->conv_hr.d_b;
+        const size_t px = (size_t)p.H * p.W;
+        timed(n, st, conv_flops(n->conv_hr, px) + conv_flops(n->conv_last, px),
+              [&] { launch_conv3x3_hr_last(n->dt, p, n->conv_last.d_wlast, n->conv_last.d_b, st); });
+        return;
+    }
     {
-        ConvParams p = base;
-        p.H = 4 * Ht;
-        p.W = 4 * Wt;
-        p.in = U2;
-        p.in_pstride = 16 * PL;
+        ConvParams p = hr;
         p.out = U3;
         p.out_pstride = 16 * PL;
         p.act = 1;
-        if (n->c5_wino && n->dt == DT_F16 && n->conv_hr.d_wwino && n->hr_wino) {
+        if (hr_wino) {
             p.cin_chunks = n->conv_hr.chunks;
             p.wpk = n->conv_hr.d_wwino;
             p.bias = n->conv_hr.d_b;
@@ -430,18 +464,9 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
         }
     }
     {
-        ConvParams p = base;
-        p.H = 4 * Ht;
-        p.W = 4 * Wt;
+        ConvParams p = img;
         p.in = U3;
         p.in_pstride = 16 * PL;
-        if (bits == 16)
-            p.out_u16 = (uint16_t*)d_out;
-        else
-            p.out_u8 = (uint8_t*)d_out;
-        p.out_rgb = d_rgb;
-        p.img_H = n->scale * H;  // crops the mod-pad of the x2 model
-        p.img_W = n->scale * W;
         run_conv(n, n->conv_last, EPI_IMAGE, p, st);
     }
 }
@@ -489,6 +514,7 @@ int fw_rrdbnet_create(int device_id, int num_block, int scale, int dtype, fw_rrd
         if (const char* e = getenv("FW_RRDB_ABL_RDB3")) n->abl_rdb3 = atoi(e);
         if (const char* e = getenv("FW_RRDB_C5_WINO")) n->c5_wino = atoi(e);
         if (const char* e = getenv("FW_RRDB_HR_WINO")) n->hr_wino = atoi(e) != 0;
+        if (const char* e = getenv("FW_RRDB_HR_LAST")) n->hr_last = atoi(e) != 0;
         *out = n.release();
     });
 }
@@ -525,6 +551,12 @@ int fw_rrdbnet_set_conv(fw_rrdbnet* n, const char* key, const float* weight, con
             pack_conv3x3_wino_weights(n->dt, weight, cout, cin, l->chunks, wn.data());
             FW_HIP_CHECK(hipMalloc(&l->d_wwino, nw * 2));
             FW_HIP_CHECK(hipMemcpy(l->d_wwino, wn.data(), nw * 2, hipMemcpyHostToDevice));
+        }
+        if (l == &n->conv_last) {
+            std::vector<uint16_t> pw(pack_conv_last_pointwise(n->dt, nullptr, nullptr));
+            pack_conv_last_pointwise(n->dt, weight, pw.data());
+            FW_HIP_CHECK(hipMalloc(&l->d_wlast, pw.size() * 2));
+            FW_HIP_CHECK(hipMemcpy(l->d_wlast, pw.data(), pw.size() * 2, hipMemcpyHostToDevice));
         }
         if (l == &n->conv_up1 || l == &n->conv_up2) {
             const size_t np = pack_conv_up2x_phase_weights(n->dt, nullptr, nullptr);
@@ -808,6 +840,68 @@ int fw_conv3x3_split_nhwc(int dtype, int winograd, const void* x, int in_cstride
             launch_conv3x3_wino_split(p, (hipStream_t)stream);
         else
             launch_conv3x3((DType)dtype, 2, EPI_RESIDUAL_SPLIT, p, (hipStream_t)stream);
+    });
+}
+
+size_t fw_pack_conv_last_pointwise(int dtype, const float* weight, uint16_t* dst) {
+    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return 0;
+    if (dst && !weight) return 0;
+    return pack_conv_last_pointwise((DType)dtype, weight, dst);
+}
+
+int fw_conv3x3_hr_last_nhwc(int dtype, int fused, const void* x, int in_cstride, long in_plane_stride, int H, int W,
+                            const void* packed_w_hr, const float* bias_hr, const void* packed_w_last, const void* packed_w_last_pw,
+                            const float* bias_last, void* scratch_u3, int img_H, int img_W, uint8_t* out_u8, uint16_t* out_u16,
+                            float* out_rgb_f32, void* stream) {
+    if (!x || !packed_w_hr || !bias_hr || !bias_last) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: NULL argument");
+    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: bad dtype");
+    if (fused != 0 && fused != 1) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: fused must be 0 or 1");
+    if (fused ? !packed_w_last_pw : (!packed_w_last || !scratch_u3))
+        return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: missing conv_last weights or scratch for this form");
+    if (H < 1 || W < 1 || img_H < 1 || img_W < 1 || img_H > H || img_W > W) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: bad size");
+    if (!out_u8 && !out_u16 && !out_rgb_f32) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: no output");
+    return guarded([&] {
+        ConvParams hr{};
+        hr.in = x;
+        hr.in_cstride = in_cstride;
+        hr.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
+        hr.cin_chunks = 2;
+        hr.H = H;
+        hr.W = W;
+        hr.wpk = packed_w_hr;
+        hr.bias = bias_hr;
+        hr.s1 = hr.s2 = 1.f;
+        ConvParams img{};
+        img.H = H;
+        img.W = W;
+        img.s1 = img.s2 = 1.f;
+        img.out_u8 = out_u8;
+        img.out_u16 = out_u16;
+        img.out_rgb = out_rgb_f32;
+        img.img_H = img_H;
+        img.img_W = img_W;
+        if (fused) {
+            hr.out_u8 = out_u8;
+            hr.out_u16 = out_u16;
+            hr.out_rgb = out_rgb_f32;
+            hr.img_H = img_H;
+            hr.img_W = img_W;
+            launch_conv3x3_hr_last((DType)dtype, hr, packed_w_last_pw, bias_last, (hipStream_t)stream);
+            return;
+        }
+        const long plane = (long)H * W * 32;   // scratch_u3: two 32-channel planes [H][W][32]
+        hr.out = scratch_u3;
+        hr.out_cstride = 32;
+        hr.out_pstride = plane;
+        hr.act = 1;
+        launch_conv3x3((DType)dtype, 2, EPI_STORE, hr, (hipStream_t)stream);
+        img.in = scratch_u3;
+        img.in_cstride = 32;
+        img.in_pstride = plane;
+        img.cin_chunks = 2;
+        img.wpk = packed_w_last;
+        img.bias = bias_last;
+        launch_conv3x3((DType)dtype, 1, EPI_IMAGE, img, (hipStream_t)stream);
     });
 }
 
