@@ -862,6 +862,41 @@ int fw_vhs_column_sums_u8(const uint8_t* frame, int height, int width, int64_t* 
 int fw_vhs_jitter_shifts_u8(const uint8_t* frame, int height, int width, int channels, int32_t* shifts, void* stream);
 int fw_vhs_saturation_f64(const uint8_t* frame, int height, int width, double* saturation /* device [H][W] */, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Letterbox / pillarbox statistics, crop and aspect conversion (csrc/aspect.hip): the frame path of the reference's `AspectHandler`
+ * (processors/format/aspect.py) on uint8 frames in DEVICE memory, gray (H x W) or BGR (H x W x 3), without row padding.
+ * tests/aspect_ref.py is the contract, held byte for byte against the reference's own methods on the CPU.  Integers only.  Explicit
+ * stream; the calls enqueue and never wait or allocate.  `frames`, `src`, `dst`, `background`, `strips` are HOST tables of device
+ * pointers; 1 .. 32 frames a call.  Gray g is the bytes (channels 1) or (1868 B + 9617 G + 4899 R + 8192) >> 14.
+ *   fw_aspect_bar_sums_u8 : row_sums uint32 [n][H] = sum_x g[y][x], column_sums uint32 [n][W] = sum_y g[y][x], exact (aspect.py:636-680,
+ *     `_detect_horizontal_bars` / `_detect_vertical_bars`: np.mean(line) > threshold is sum > threshold * length; the walk over the
+ *     sums is the caller's).  The sums are zeroed on the stream first and accumulated with integer atomics: the same in every run.
+ *   fw_aspect_crop_u8 : dst[i] = src[i][y : y + crop_height, x : x + crop_width] contiguous (aspect.py:458-470 `crop_letterbox`,
+ *     :708-728 `_crop_to_ratio`); flip 1 reverses the columns of the result, flip 2 its rows (cv2.flip of a strip, :851 - :885).
+ *   fw_aspect_pad_u8 : every byte of dst[i] (out_height x out_width): src[i] at (x_offset, y_offset) (aspect.py:730-781
+ *     `_pad_to_ratio`), outside it mode 0 the three bytes of `color` (HOST, taken in B, G, R order as given; gray: color[0]); mode 2
+ *     the byte of background[i], a frame of the output size (:811-834 `_apply_blur_fill`); mode 1 the mirror fill (:836-892
+ *     `_apply_mirror_fill`): beside the source, over its span only, a bar no wider than the source is the source's edge strip reversed;
+ *     a wider bar takes the bytes of strips[4 i + k] (k = 0 left, 1 right, 2 top, 3 bottom; contiguous, of the bar's size; the caller
+ *     makes it from the whole source with fw_aspect_crop_u8 reversed and fw_resize_linear_u8); the corners take `color`.
+ *   fw_aspect_gauss99_u8 : cv2.GaussianBlur(src, (99, 99), 0) on uint8 (:822) in fixed point: weights is a HOST table of 99 values in 8
+ *     fractional bits that sum to 256 (getGaussianKernel(99, 0), sigma 15.2, quantised by the caller); rows: scratch uint16 [H][W][C] =
+ *     sum src * w; columns: dst = (sum scratch * w + 2^15) >> 16; BORDER_REFLECT_101, reflected as often as it takes, index 0 for a
+ *     side of one pixel.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers or tables, n outside 1 .. 32, height or width (of the
+ * frame or of the output) outside 1 .. 16384, channels other than 1 or 3, a crop that is empty or not inside the frame, a flip or a
+ * mode out of range, a source that does not lie inside the output, a missing strip of a bar wider than the source, weights that do
+ * not sum to 256, a dst (or scratch) that overlaps anything the call reads or another dst of the call. */
+int fw_aspect_bar_sums_u8(const void* const* frames /* host [n] */, int n, int height, int width, int channels,
+                          uint32_t* row_sums /* device [n][H] */, uint32_t* column_sums /* device [n][W] */, void* stream);
+int fw_aspect_crop_u8(const void* const* src /* host [n] */, void* const* dst /* host [n] */, int n, int height, int width, int channels,
+                      int x, int y, int crop_width, int crop_height, int flip, void* stream);
+int fw_aspect_pad_u8(const void* const* src /* host [n] */, void* const* dst /* host [n] */, int n, int height, int width, int channels,
+                     int out_height, int out_width, int x_offset, int y_offset, int mode, const uint8_t* color /* host [3] */,
+                     const void* const* background /* host [n], mode 2 */, const void* const* strips /* host [n][4], mode 1 */, void* stream);
+int fw_aspect_gauss99_u8(const uint8_t* src, int height, int width, int channels, const uint16_t* weights /* host [99] */,
+                         uint16_t* scratch /* device [H][W][C] */, uint8_t* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,9 @@ EXPORTS = [
     "fw_flow_accumulate_u8", "fw_flow_accumulate_finish_u8", "fw_resize_lanczos4_u8", "fw_resize_linear_u8", "fw_face_paste_u8", "fw_grain_addback_u8", "fw_attn_softmax_rows", "fw_pack_pointwise_transposed", "fw_attn_qk_scratch_elems", "fw_attn_matrix_mfma",
     "fw_pack_conv3x3_wino", "fw_conv3x3_split_nhwc", "fw_conv3x3_wino_nhwc", "fw_conv3x3_wino_check_fields",
     "fw_pack_conv_last_pointwise", "fw_conv3x3_hr_last_nhwc",
+    # csrc/aspect.hip.  In front of fw_farneback_scratch_bytes: from there on the list is the entries whose refusals
+    # tests/golden/stage_errors.json pins; these are held by tests/test_aspect_gpu.py.
+    "fw_aspect_bar_sums_u8", "fw_aspect_crop_u8", "fw_aspect_pad_u8", "fw_aspect_gauss99_u8",
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
@@ -385,6 +388,14 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_vhs_jitter_shifts_u8.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.fw_vhs_saturation_f64.restype = i32
     lib.fw_vhs_saturation_f64.argtypes = [vp, i32, i32, vp, vp]
+    lib.fw_aspect_bar_sums_u8.restype = i32
+    lib.fw_aspect_bar_sums_u8.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.fw_aspect_crop_u8.restype = i32
+    lib.fw_aspect_crop_u8.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.fw_aspect_pad_u8.restype = i32
+    lib.fw_aspect_pad_u8.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.fw_aspect_gauss99_u8.restype = i32
+    lib.fw_aspect_gauss99_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
 
 
 def load() -> C.CDLL:

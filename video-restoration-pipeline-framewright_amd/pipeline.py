@@ -36,10 +36,18 @@ class DeviceRestorationPipeline:
     ``vhs_processor`` (a `vhs.DeviceVHSProcessor`; opt-in) runs its `process` on the input frames behind the deinterlacer and in front
     of every other stage; the streaming forms use its `stream`, which keeps `temporal_radius` frames on both sides for the dropout
     repair and equals `run_device`.
+
+    ``aspect_handler`` (an `aspect.DeviceAspectHandler`; opt-in) with ``crop_bars`` crops letterbox and pillarbox bars off the input
+    frames (`crop_letterbox`: the analysis of the first 20 frames decides for the clip) behind the deinterlacer and the VHS processor -
+    an odd crop offset in front of the deinterlacer would swap the field parity, and the VHS analysis reads the bottom rows of the full
+    frame - and in front of every other stage, so the networks never see the bars.  With ``aspect_target`` (a ratio as the
+    reference's `convert_aspect` takes it) the output frames are converted with the handler's configured method and fill behind the
+    colour grade, so the padding is not graded.  The streaming forms hold back the first min(20, n) frames for the analysis
+    (`DeviceAspectHandler.stream`) and equal `run_device`.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
-                 deinterlacer=None, vhs_processor=None):
+                 deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -47,6 +55,7 @@ class DeviceRestorationPipeline:
         self.color_grader = color_grader
         self.deinterlacer = deinterlacer
         self.vhs_processor = vhs_processor
+        self.aspect_handler, self.aspect_target, self.crop_bars = aspect_handler, aspect_target, bool(crop_bars)
 
     @classmethod
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
@@ -67,6 +76,8 @@ class DeviceRestorationPipeline:
                 cur = list(self.deinterlacer.deinterlace(cur))
             if self.vhs_processor is not None:
                 cur = list(self.vhs_processor.process(cur))
+            if self.aspect_handler is not None and self.crop_bars:
+                cur = list(self.aspect_handler.crop_letterbox(cur))
             if self.denoiser is not None:
                 cur = self.denoiser.denoise_clip_device(cur)
             if self.upscaler is not None and self.deduplicator is not None and cur:
@@ -84,6 +95,8 @@ class DeviceRestorationPipeline:
                     cur = nxt
             if self.color_grader is not None:
                 cur = self.color_grader.apply_device(cur)      # new tensors: a repeated frame may be one tensor several times
+            if self.aspect_handler is not None and self.aspect_target is not None:
+                cur = list(self.aspect_handler.convert_aspect(cur, self.aspect_target))
         return cur
 
     def run(self, frames: Sequence) -> List[np.ndarray]:
@@ -96,9 +109,10 @@ class DeviceRestorationPipeline:
     def _device(self):
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
-        the first of denoiser, colour grader, deinterlacer, VHS processor.  Every stage answers through `_lib.owner_device`: a new
+        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler.  Every stage answers through `_lib.owner_device`: a new
         stage adds its name to the tuple."""
-        for stage in (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor):
+        for stage in (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
+                      self.aspect_handler):
             dev = _lib.owner_device(stage)
             if dev is not None:
                 return dev
@@ -179,6 +193,8 @@ class DeviceRestorationPipeline:
                 g = self.deinterlacer.stream(g, block=block)
             if self.vhs_processor is not None:
                 g = self.vhs_processor.stream(g, block=block)
+            if self.aspect_handler is not None and self.crop_bars:
+                g = self.aspect_handler.stream(g, block=block)
             if self.denoiser is not None:
                 g = self._gen_denoise(g, block)
             if self.upscaler is not None:
@@ -188,6 +204,8 @@ class DeviceRestorationPipeline:
                     g = self._gen_interp(g)
             if self.color_grader is not None:
                 g = (self.color_grader.apply_device([f])[0] for f in g)
+            if self.aspect_handler is not None and self.aspect_target is not None:
+                g = (self.aspect_handler.convert_aspect([f], self.aspect_target)[0] for f in g)
             yield from g
 
     def run_stream(self, frames: Iterable, writer, block: int = 8, slots: int = 3) -> int:
