@@ -897,6 +897,32 @@ int fw_aspect_pad_u8(const void* const* src /* host [n] */, void* const* dst /* 
 int fw_aspect_gauss99_u8(const uint8_t* src, int height, int width, int channels, const uint16_t* weights /* host [99] */,
                          uint16_t* scratch /* device [H][W][C] */, uint8_t* dst, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Frame quality statistics (csrc/quality.hip): the integers every measure of the reference's `FrameQualityScorer.score_frame`
+ * (processors/frame_quality_scorer.py:148-427) is a function of, for n uint8 H x W x 3 BGR frames in DEVICE memory (a HOST table of n
+ * device pointers; 1 .. 32 frames a call, 2 .. 16384 pixels a side, both sides even: the reference's row-pair subtraction raises on an
+ * odd side).  One pass over each frame; the scores are the caller's (quality.py).  tests/quality_ref.frame_statistics is the contract;
+ * cv2 parity unpinned.  Gray g = (1868 B + 9617 G + 4899 R + 8192) >> 14; L is L of the 8-bit gamma Lab of fw_bgr_to_lab_u8; every
+ * stencil reads BORDER_REFLECT_101.
+ *   sums [n][12] int64: 0 sum lap, 1 sum lap^2 (lap = the 3 x 3 cross Laplacian of g), 2 sum d, 3 sum d^2 (d = |g - blur|, blur the
+ *     1 4 6 4 1 taps in both directions, (sum + 128) >> 8), 4 sum |g[y-1][x-1] - g[y-1][x+1] - g[y+1][x-1] + g[y+1][x+1]|, 5 and 6 the
+ *     number of pixels whose |Sobel x of L| (ksize 3) is above 30 / above 5 and at most 30, 7 sum |g[2k][x] - g[2k+1][x]|, 8 sum
+ *     |g[y][2k] - g[y][2k+1]|, 9 sum v and 10 sum v^2 over all 3 H W bytes, 11 zero.
+ *   histograms [n][512] uint32: 256 bins of g, then 256 bins of all bytes.
+ *   block_sums [n][R + C] uint32, R = len(range(8, H - 8, 8)), C = len(range(8, W - 8, 8)): sum_x |g[i][x] - g[i-1][x]| for each such
+ *     row i, then sum_y |g[y][j] - g[y][j-1]| for each such column j.  May be any non-NULL pointer when R + C = 0.
+ *   thumbnails [n][1024] uint8: cv2.resize(g, (32, 32)) as fw_resize_linear_u8 computes it (a copy at 32 x 32, the 2 x 2 mean at 64 x 64).
+ * scratch: fw_quality_scratch_bytes(n, height, width) bytes of DEVICE memory, 8-byte aligned, where the workgroups leave their partial
+ * sums and histograms for a second small launch to add; 0 from that function means a bad argument.  sums is 8-byte aligned too.
+ * Everything is an integer (plain stores, and integer atomics for the block sums, which are zeroed on the stream first): the same in
+ * every run.  The entry only enqueues work and never waits for the device (the Lab tables are made on a device's first call).
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, n outside 1 .. 32, a side outside 1 .. 16384 or odd, a
+ * misaligned scratch or sums, an output or the scratch that overlaps a frame of the call, an output that overlaps the scratch. */
+size_t fw_quality_scratch_bytes(int n, int height, int width);
+int fw_quality_stats_u8(const void* const* frames /* host [n] */, int n, int height, int width, void* scratch, int64_t* sums /* device [n][12] */,
+                        uint32_t* histograms /* device [n][512] */, uint32_t* block_sums /* device [n][R + C] */,
+                        uint8_t* thumbnails /* device [n][1024] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,3 +11,4 @@ from .dedup import (DeduplicationConfig, DeduplicationResult, DeviceFrameDedupli
                     deduplicate_and_enhance, detect_duplicate_frames)
 from .color_grade import (LUT, DeviceColorGrader, LUTType, combine_luts, create_contrast_lut,  # noqa: E402,F401
                           create_film_emulation_lut, create_identity_lut, create_seasonal_lut, read_cube, write_cube)
+from .quality import DeviceFrameQualityScorer, FrameScore, QualityIssue, QualityReport  # noqa: E402,F401

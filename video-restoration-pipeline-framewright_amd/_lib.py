@@ -48,6 +48,7 @@ EXPORTS = [
     # csrc/aspect.hip.  In front of fw_farneback_scratch_bytes: from there on the list is the entries whose refusals
     # tests/golden/stage_errors.json pins; these are held by tests/test_aspect_gpu.py.
     "fw_aspect_bar_sums_u8", "fw_aspect_crop_u8", "fw_aspect_pad_u8", "fw_aspect_gauss99_u8",
+    "fw_quality_scratch_bytes", "fw_quality_stats_u8",    # csrc/quality.hip, held by tests/test_quality_gpu.py
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
@@ -396,6 +397,10 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_aspect_pad_u8.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.fw_aspect_gauss99_u8.restype = i32
     lib.fw_aspect_gauss99_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.fw_quality_stats_u8.restype = i32
+    lib.fw_quality_stats_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.fw_quality_scratch_bytes.restype = sz
+    lib.fw_quality_scratch_bytes.argtypes = [i32, i32, i32]
 
 
 def load() -> C.CDLL:

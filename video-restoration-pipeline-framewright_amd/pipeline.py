@@ -44,10 +44,17 @@ class DeviceRestorationPipeline:
     reference's `convert_aspect` takes it) the output frames are converted with the handler's configured method and fill behind the
     colour grade, so the padding is not graded.  The streaming forms hold back the first min(20, n) frames for the analysis
     (`DeviceAspectHandler.stream`) and equal `run_device`.
+
+    ``input_quality_scorer`` and ``quality_scorer`` (each a `quality.DeviceFrameQualityScorer`; opt-in) score the frames as they enter,
+    in front of the deinterlacer, and the final frames, behind the aspect conversion; the frames themselves pass through as they are.
+    The reports are kept as ``last_input_quality_report`` and ``last_quality_report`` (timestamps from ``quality_fps``; 0 gives the
+    reference's timestamp 0).  The streaming forms score each frame as it passes (`DeviceFrameQualityScorer.stream`: a few kilobytes of
+    integers a frame are kept, never the frame) and build each report when its stream ends; a generator that is abandoned leaves None.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
-                 deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True):
+                 deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True,
+                 quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -56,6 +63,11 @@ class DeviceRestorationPipeline:
         self.deinterlacer = deinterlacer
         self.vhs_processor = vhs_processor
         self.aspect_handler, self.aspect_target, self.crop_bars = aspect_handler, aspect_target, bool(crop_bars)
+        self.quality_scorer, self.input_quality_scorer, self.quality_fps = quality_scorer, input_quality_scorer, float(quality_fps)
+        self.last_quality_report = self.last_input_quality_report = None
+
+    def _keep_report(self, name: str):
+        return lambda report: setattr(self, name, report)
 
     @classmethod
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
@@ -70,8 +82,11 @@ class DeviceRestorationPipeline:
         def up(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a.contiguous()
 
+        self.last_quality_report = self.last_input_quality_report = None
         with torch.cuda.device(dev):
             cur = [up(f) for f in frames]
+            if self.input_quality_scorer is not None:
+                self.last_input_quality_report = self.input_quality_scorer.analyze_frames(cur, self.quality_fps)
             if self.deinterlacer is not None:
                 cur = list(self.deinterlacer.deinterlace(cur))
             if self.vhs_processor is not None:
@@ -97,6 +112,8 @@ class DeviceRestorationPipeline:
                 cur = self.color_grader.apply_device(cur)      # new tensors: a repeated frame may be one tensor several times
             if self.aspect_handler is not None and self.aspect_target is not None:
                 cur = list(self.aspect_handler.convert_aspect(cur, self.aspect_target))
+            if self.quality_scorer is not None:
+                self.last_quality_report = self.quality_scorer.analyze_frames(cur, self.quality_fps)
         return cur
 
     def run(self, frames: Sequence) -> List[np.ndarray]:
@@ -109,10 +126,10 @@ class DeviceRestorationPipeline:
     def _device(self):
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
-        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler.  Every stage answers through `_lib.owner_device`: a new
+        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers.  Every stage answers through `_lib.owner_device`: a new
         stage adds its name to the tuple."""
         for stage in (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
-                      self.aspect_handler):
+                      self.aspect_handler, self.quality_scorer, self.input_quality_scorer):
             dev = _lib.owner_device(stage)
             if dev is not None:
                 return dev
@@ -187,8 +204,11 @@ class DeviceRestorationPipeline:
                 else:
                     yield a.contiguous()
 
+        self.last_quality_report = self.last_input_quality_report = None
         with torch.cuda.device(dev):
             g = gen_up()
+            if self.input_quality_scorer is not None:
+                g = self.input_quality_scorer.stream(g, self.quality_fps, self._keep_report("last_input_quality_report"))
             if self.deinterlacer is not None:
                 g = self.deinterlacer.stream(g, block=block)
             if self.vhs_processor is not None:
@@ -206,6 +226,8 @@ class DeviceRestorationPipeline:
                 g = (self.color_grader.apply_device([f])[0] for f in g)
             if self.aspect_handler is not None and self.aspect_target is not None:
                 g = (self.aspect_handler.convert_aspect([f], self.aspect_target)[0] for f in g)
+            if self.quality_scorer is not None:
+                g = self.quality_scorer.stream(g, self.quality_fps, self._keep_report("last_quality_report"))
             yield from g
 
     def run_stream(self, frames: Iterable, writer, block: int = 8, slots: int = 3) -> int:
