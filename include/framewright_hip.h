@@ -923,6 +923,54 @@ int fw_quality_stats_u8(const void* const* frames /* host [n] */, int n, int hei
                         uint32_t* histograms /* device [n][512] */, uint32_t* block_sums /* device [n][R + C] */,
                         uint8_t* thumbnails /* device [n][1024] */, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * SDR to HDR conversion of final frames (csrc/hdr.hip): the frame path of the reference's `HDRConverter.convert_frame`
+ * (processors/hdr_conversion.py:573-882) on uint8 / uint16 H x W x 3 BGR frames in DEVICE memory, 8 .. 16384 pixels a side, to
+ * uint16 BGR.  tests/hdr_ref.py is the contract, byte for byte where a quantising step is on and the curve is rational (cv2's CLAHE,
+ * addWeighted, Lab and HSV as that file restates them; cv2 parity unpinned); hdr.py derives everything below from an HDRConfig.
+ *   fw_hdr_params: every constant already rounded to float32 by the caller, as numpy rounds a Python float that meets a float32
+ *     array.  matrix: rows R, G, B over (R, G, B), applied as round(m0 r), fma(m1, g, .), fma(m2, b, .).  lum_weights over (B, G, R).
+ *     curve 0 REINHARD k = {(peak / 100)^2}; 1 ACES {peak / 100, a, b, c, d, e}; 2 HABLE {peak / 100, A, C B, D E, B, D F, E / F,
+ *     1 / hable(peak / 100)}; 3 MOBIUS {peak / 100, transition, 1 - transition, -slope}.  clip_code: the first code whose normalised
+ *     value exceeds 0.98.  transfer 0 PQ k = {peak / 10000, m1, m2, c1, c2, c3}; 1 HLG {1 / 12, a, b, c} (read only when neither
+ *     local_contrast nor saturation is set).  hue_scale: 6 / 180.
+ *   gamma: DEVICE float32 [256] (uint8 input) or [65536] (uint16): power(code / maxv, 2.2) as numpy evaluates it.
+ *   tail: DEVICE uint16 [2][256]: the transfer function and the 16-bit quantisation of byte / 255 and of float32(byte / 255 * 0.95);
+ *     hsv_div: DEVICE int32 [512]: round((255 << 12) / i), then round((180 << 12) / (6 i)), entry 0 of each 0.
+ *   fw_hdr_convert: n frames (HOST tables of n device pointers, 1 .. 32) -> dst (uint16, n x H W 3).  With local_contrast: a pass
+ *     that accumulates the 8 x 8 x 256 CLAHE tile histograms (integer atomics), a small launch that makes the 64 byte LUTs, and the
+ *     pass that writes; scratch is fw_hdr_scratch_bytes(n) bytes of DEVICE memory, 4-byte aligned (else it may be NULL).  With
+ *     saturation only: one pass through the tail table.  With neither: one pass, the transfer function per pixel in float32 (powf,
+ *     logf: within the error bound of DESIGN K20 of a float64 evaluation, not bit-pinned).
+ *   fw_hdr_tonemap_f32: steps 1 - 3 of one frame as float32 H W 3 (recover != 0: times the highlight gain where the flag is set);
+ *     fw_hdr_quantise_u8: trunc(. * 255) of that plane; fw_hdr_clahe_u8: cv2.createCLAHE(2.0, (8, 8)).apply on a uint8 H x W plane;
+ *     fw_hdr_saturation_u8: BGR -> HSV, s = trunc(clip(s * boost, 0, 255)), HSV -> BGR on n_pixels interleaved pixels;
+ *     fw_hdr_transfer_f32: the transfer function and trunc(clip(. * 65535, 0, 65535)) of `count` float32 values.
+ * The entries only enqueue work (the Lab tables are made on a device's first call).  Refused with FW_ERR_INVALID and a message,
+ * nothing launched: NULL pointers, n outside 1 .. 32, a side outside 8 .. 16384, sample_bytes other than 1 or 2, a curve or a
+ * transfer out of range, misaligned 16-bit or float buffers, a dst that overlaps a frame or another dst of the call. */
+typedef struct fw_hdr_params {
+    float matrix[9];
+    float lum_weights[3];
+    float curve_k[8];
+    float transfer_k[8];
+    float lum_floor;          /* 0.0001 */
+    float recover_gain;       /* 0.95 */
+    float saturation_boost;
+    float hue_scale;
+    int32_t use_matrix, curve, transfer, local_contrast, saturation, recover, clip_code;
+} fw_hdr_params;
+size_t fw_hdr_scratch_bytes(int n);
+int fw_hdr_convert(const void* const* frames /* host [n] */, void* const* dst /* host [n] */, int n, int height, int width, int sample_bytes,
+                   const fw_hdr_params* params, const float* gamma, const uint16_t* tail, const int32_t* hsv_div, void* scratch, void* stream);
+int fw_hdr_tonemap_f32(const void* frame, int height, int width, int sample_bytes, const fw_hdr_params* params, const float* gamma,
+                       int recover, float* dst, void* stream);
+int fw_hdr_quantise_u8(const void* frame, int height, int width, int sample_bytes, const fw_hdr_params* params, const float* gamma,
+                       uint8_t* dst, void* stream);
+int fw_hdr_clahe_u8(const uint8_t* plane, int height, int width, void* scratch, uint8_t* dst, void* stream);
+int fw_hdr_saturation_u8(const uint8_t* bgr, int64_t n_pixels, const int32_t* hsv_div, float boost, float hue_scale, uint8_t* dst, void* stream);
+int fw_hdr_transfer_f32(const float* plane, int64_t count, const fw_hdr_params* params, uint16_t* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

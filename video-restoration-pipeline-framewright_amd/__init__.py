@@ -12,3 +12,5 @@ from .dedup import (DeduplicationConfig, DeduplicationResult, DeviceFrameDedupli
 from .color_grade import (LUT, DeviceColorGrader, LUTType, combine_luts, create_contrast_lut,  # noqa: E402,F401
                           create_film_emulation_lut, create_identity_lut, create_seasonal_lut, read_cube, write_cube)
 from .quality import DeviceFrameQualityScorer, FrameScore, QualityIssue, QualityReport  # noqa: E402,F401
+from .hdr import (ColorSpace, DeviceHDRConverter, HDRConfig, HDRConversionResult, HDRFormat, ToneMapping,  # noqa: E402,F401
+                  create_hdr_converter)

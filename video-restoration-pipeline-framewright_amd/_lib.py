@@ -49,6 +49,8 @@ EXPORTS = [
     # tests/golden/stage_errors.json pins; these are held by tests/test_aspect_gpu.py.
     "fw_aspect_bar_sums_u8", "fw_aspect_crop_u8", "fw_aspect_pad_u8", "fw_aspect_gauss99_u8",
     "fw_quality_scratch_bytes", "fw_quality_stats_u8",    # csrc/quality.hip, held by tests/test_quality_gpu.py
+    "fw_hdr_scratch_bytes", "fw_hdr_convert", "fw_hdr_tonemap_f32", "fw_hdr_quantise_u8", "fw_hdr_clahe_u8", "fw_hdr_saturation_u8",
+    "fw_hdr_transfer_f32",                                # csrc/hdr.hip, held by tests/test_hdr_gpu.py
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
@@ -401,6 +403,20 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_quality_stats_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.fw_quality_scratch_bytes.restype = sz
     lib.fw_quality_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.fw_hdr_scratch_bytes.restype = sz
+    lib.fw_hdr_scratch_bytes.argtypes = [i32]
+    lib.fw_hdr_convert.restype = i32
+    lib.fw_hdr_convert.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.fw_hdr_tonemap_f32.restype = i32
+    lib.fw_hdr_tonemap_f32.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp]
+    lib.fw_hdr_quantise_u8.restype = i32
+    lib.fw_hdr_quantise_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.fw_hdr_clahe_u8.restype = i32
+    lib.fw_hdr_clahe_u8.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.fw_hdr_saturation_u8.restype = i32
+    lib.fw_hdr_saturation_u8.argtypes = [vp, C.c_int64, vp, f32, f32, vp, vp]
+    lib.fw_hdr_transfer_f32.restype = i32
+    lib.fw_hdr_transfer_f32.argtypes = [vp, C.c_int64, vp, vp, vp]
 
 
 def load() -> C.CDLL:

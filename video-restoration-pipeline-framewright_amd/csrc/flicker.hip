@@ -18,7 +18,7 @@
 // other lane touches those bytes, so dst may alias src.  The small tables (decode, fy / Y / a / b, thresholds, the frame's LUT:
 // 5.4 KiB) are copied to LDS per workgroup; the 65281-entry f(t) table (255 KiB) is gathered from global memory, where it stays in L2.
 #include "stage_common.h"
-#include "lab_tables.h"
+#include "gamma_lab.h"
 
 #include <cmath>
 #include <map>
@@ -28,18 +28,11 @@
 namespace fw {
 namespace {
 
-constexpr int LIN_MAX = 255 * 256;                              // the scale of a decoded channel = the last f(t) index
-constexpr int LIN_SHIFT = F_BITS + INV_COEF_BITS - 8;           // the inverse matrix carries x 255: this leaves x 255 x 256
 constexpr int FK_NT = 256;
 enum { MODE_FWD = 0, MODE_INV = 1, MODE_DEFLICKER = 2 };
 
-struct SmallTables {
-    int t256[1024];             // fy, Y, a / 500, b / 200 (MODE_INV, MODE_DEFLICKER)
-    uint16_t dec[256];          // sRGB decode (MODE_FWD, MODE_DEFLICKER)
-    uint16_t thr[256];          // encode thresholds, [255] = 0xffff: above every value
-    uint8_t lut[256];           // the frame's map of L (MODE_DEFLICKER)
-};
-
+// The per-pixel transforms (bgr_to_lab_px, lab_to_bgr_px, l_of_px) and SmallTables are gamma_lab.h's: t256 is read by MODE_INV and
+// MODE_DEFLICKER, dec by MODE_FWD and MODE_DEFLICKER, lut by MODE_DEFLICKER.
 // small_g: decode[256], thresholds[256] as int
 template <int MODE>
 __device__ __forceinline__ void load_small(SmallTables& s, const int* __restrict__ t256_g, const int* __restrict__ small_g,
@@ -53,56 +46,6 @@ __device__ __forceinline__ void load_small(SmallTables& s, const int* __restrict
     }
     if (MODE == MODE_DEFLICKER) s.lut[tid] = lut_g[tid];
     __syncthreads();
-}
-
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
-
-// index into f(t) of row q: (coef . decoded + 2^19) >> 20, 0 .. 65280 (the rows sum to 2^20)
-__device__ __forceinline__ int f_index(const LabFwd& k, int q, uint32_t db, uint32_t dg, uint32_t dr) {
-    const unsigned long long s = (unsigned long long)(uint32_t)k.coef[3 * q] * db + (unsigned long long)(uint32_t)k.coef[3 * q + 1] * dg +
-                                 (unsigned long long)(uint32_t)k.coef[3 * q + 2] * dr + (1ull << (COEF_BITS - 1));
-    return (int)(s >> COEF_BITS);
-}
-
-__device__ __forceinline__ int l_of_fy(const LabFwd& k, int fy) {
-    constexpr int sh = F_BITS + L_SCALE_BITS;
-    return clamp255((k.l_scale * fy - k.l_offset + (1 << (sh - 1))) >> sh);
-}
-
-// packed pixel: byte 0 | byte 1 << 8 | byte 2 << 16
-__device__ __forceinline__ uint32_t bgr_to_lab_px(uint32_t p, const SmallTables& s, const LabFwd& k, const int* __restrict__ cbrt_tab) {
-    const uint32_t db = s.dec[p & 255u], dg = s.dec[(p >> 8) & 255u], dr = s.dec[(p >> 16) & 255u];
-    const int fx = cbrt_tab[f_index(k, 0, db, dg, dr)], fy = cbrt_tab[f_index(k, 1, db, dg, dr)], fz = cbrt_tab[f_index(k, 2, db, dg, dr)];
-    int a = clamp255((500 * (fx - fy) + (128 << F_BITS) + (1 << (F_BITS - 1))) >> F_BITS);
-    const int b = clamp255((200 * (fy - fz) + (128 << F_BITS) + (1 << (F_BITS - 1))) >> F_BITS);
-    // Keeps a and b from being fused into one v_ashr_pk_u8_i32 (shift, saturate and pack two bytes).  The compiler ORs that
-    // instruction's result into a dword as if its upper 16 bits were zero; on the MI355X they were observed to hold the old
-    // destination bits (pixel 2 of a group of four came back with L | a of pixel 1).
-    asm volatile("" : "+v"(a));
-    return (uint32_t)l_of_fy(k, fy) | (uint32_t)a << 8 | (uint32_t)b << 16;
-}
-
-// the number of thresholds <= v: the contract's encode[v]
-__device__ __forceinline__ uint32_t srgb_encode(const uint16_t* thr, int v) {
-    int n = 0;
-#pragma unroll
-    for (int step = 128; step > 0; step >>= 1)
-        if ((int)thr[n + step - 1] <= v) n += step;
-    return (uint32_t)n;
-}
-
-__device__ __forceinline__ uint32_t lab_to_bgr_px(uint32_t p, const SmallTables& s, const LabInv& k) {
-    const int L = p & 255u, a = (p >> 8) & 255u, b = (p >> 16) & 255u;
-    const long long fy = s.t256[L];
-    const long long v[3] = {lab_inv_g(fy + s.t256[512 + a], k), (long long)s.t256[256 + L], lab_inv_g(fy - s.t256[768 + b], k)};
-    uint32_t out = 0;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        long long lin = (k.coef[3 * q] * v[0] + k.coef[3 * q + 1] * v[1] + k.coef[3 * q + 2] * v[2] + (1ll << (LIN_SHIFT - 1))) >> LIN_SHIFT;
-        lin = lin < 0 ? 0 : lin > LIN_MAX ? LIN_MAX : lin;
-        out |= srgb_encode(s.thr, (int)lin) << (8 * q);
-    }
-    return out;
 }
 
 template <int MODE>
@@ -164,10 +107,6 @@ __global__ __launch_bounds__(FK_NT) void gamma_map_kernel(const uint8_t* src, ui
     }
 }
 
-__device__ __forceinline__ uint32_t l_of_px(uint32_t p, const uint16_t* dec, const LabFwd& k, const int* __restrict__ cbrt_tab) {
-    return (uint32_t)l_of_fy(k, cbrt_tab[f_index(k, 1, dec[p & 255u], dec[(p >> 8) & 255u], dec[(p >> 16) & 255u])]);
-}
-
 __global__ __launch_bounds__(FK_NT) void l_sums_kernel(const uint8_t* __restrict__ frames, long npx, int vec, LabFwd kf,
                                                        const int* __restrict__ cbrt_tab, const int* __restrict__ small_g,
                                                        unsigned long long* l_sums) {
@@ -227,7 +166,9 @@ const GammaTables& gamma_tables() {
 std::mutex g_mutex;
 std::map<int, int*> g_small;          // per device: decode[256], thresholds[256] ([255] = 0xffff)
 
-int* device_small() {
+}  // namespace
+
+int* device_gamma_small() {
     int dev = 0;
     FW_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(g_mutex);
@@ -245,6 +186,8 @@ int* device_small() {
     return d;
 }
 
+namespace {
+
 constexpr long MAX_PIXELS = 1L << 30;
 
 // workgroups per frame: a lane takes four pixels per step, and a workgroup stays long enough to pay for its copy of the tables
@@ -257,7 +200,7 @@ template <int MODE>
 void launch_map(const uint8_t* src, uint8_t* dst, int count, long npx, const uint8_t* luts, hipStream_t st) {
     const LabTables& t = lab_tables();
     const DeviceLab lab = device_lab();
-    const int* small = device_small();
+    const int* small = device_gamma_small();
     const int vec = (((uintptr_t)src ^ (uintptr_t)dst) & 3) == 0;
     const dim3 grid(blocks_for(npx, 1024), 1, (unsigned)count);
     hipLaunchKernelGGL((gamma_map_kernel<MODE>), grid, dim3(FK_NT), 0, st, src, dst, npx, vec, t.fwd, t.inv, lab.cbrt_tab, lab.t256, small, luts);
@@ -298,7 +241,7 @@ int fw_lab_l_sums_u8(const uint8_t* frames_bgr, int count, int height, int width
         hipStream_t st = (hipStream_t)stream;
         const LabTables& t = lab_tables();
         const DeviceLab lab = device_lab();
-        const int* small = device_small();
+        const int* small = device_gamma_small();
         const long npx = (long)height * width;
         FW_HIP_CHECK(hipMemsetAsync(l_sums, 0, (size_t)count * sizeof(int64_t), st));
         const dim3 grid(blocks_for(npx, 256), 1, (unsigned)count);

@@ -50,11 +50,16 @@ class DeviceRestorationPipeline:
     The reports are kept as ``last_input_quality_report`` and ``last_quality_report`` (timestamps from ``quality_fps``; 0 gives the
     reference's timestamp 0).  The streaming forms score each frame as it passes (`DeviceFrameQualityScorer.stream`: a few kilobytes of
     integers a frame are kept, never the frame) and build each report when its stream ends; a generator that is abandoned leaves None.
+
+    ``hdr_converter`` (an `hdr.DeviceHDRConverter`; opt-in) is the last step: behind the colour grade, the aspect conversion and
+    ``quality_scorer``, which scores the 8-bit frames, every output frame is converted to a new uint16 PQ / HLG tensor.  It is
+    elementwise apart from the frame's own CLAHE histograms, so the streaming forms have it too, and `run_stream`'s pinned ring
+    takes the frames' type.  `close` releases it, and every other stage that has a `close`.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
                  deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True,
-                 quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0):
+                 quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0, hdr_converter=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -65,6 +70,18 @@ class DeviceRestorationPipeline:
         self.aspect_handler, self.aspect_target, self.crop_bars = aspect_handler, aspect_target, bool(crop_bars)
         self.quality_scorer, self.input_quality_scorer, self.quality_fps = quality_scorer, input_quality_scorer, float(quality_fps)
         self.last_quality_report = self.last_input_quality_report = None
+        self.hdr_converter = hdr_converter
+
+    def _stages(self) -> tuple:
+        """Every configured stage slot, in the order `_device` asks them: a new stage adds its name here."""
+        return (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
+                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter)
+
+    def close(self) -> None:
+        """Closes every stage that can be closed (the engines free their native handles, the HDR converter its tables)."""
+        for stage in self._stages():
+            if stage is not None and callable(getattr(stage, "close", None)):
+                stage.close()
 
     def _keep_report(self, name: str):
         return lambda report: setattr(self, name, report)
@@ -114,6 +131,8 @@ class DeviceRestorationPipeline:
                 cur = list(self.aspect_handler.convert_aspect(cur, self.aspect_target))
             if self.quality_scorer is not None:
                 self.last_quality_report = self.quality_scorer.analyze_frames(cur, self.quality_fps)
+            if self.hdr_converter is not None:
+                cur = self.hdr_converter.convert_device(cur)   # new uint16 tensors: a repeated frame may be one tensor several times
         return cur
 
     def run(self, frames: Sequence) -> List[np.ndarray]:
@@ -126,10 +145,9 @@ class DeviceRestorationPipeline:
     def _device(self):
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
-        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers.  Every stage answers through `_lib.owner_device`: a new
-        stage adds its name to the tuple."""
-        for stage in (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
-                      self.aspect_handler, self.quality_scorer, self.input_quality_scorer):
+        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers, the HDR converter.
+        Every stage answers through `_lib.owner_device`: a new stage adds its name to `_stages`."""
+        for stage in self._stages():
             dev = _lib.owner_device(stage)
             if dev is not None:
                 return dev
@@ -228,6 +246,8 @@ class DeviceRestorationPipeline:
                 g = (self.aspect_handler.convert_aspect([f], self.aspect_target)[0] for f in g)
             if self.quality_scorer is not None:
                 g = self.quality_scorer.stream(g, self.quality_fps, self._keep_report("last_quality_report"))
+            if self.hdr_converter is not None:
+                g = self.hdr_converter.stream(g)
             yield from g
 
     def run_stream(self, frames: Iterable, writer, block: int = 8, slots: int = 3) -> int:
@@ -247,7 +267,7 @@ class DeviceRestorationPipeline:
         with torch.cuda.device(dev):
             for t in self.stream_device(frames, block):
                 if pins is None:
-                    pins = [torch.empty(tuple(t.shape), dtype=torch.uint8).pin_memory() for _ in range(max(2, int(slots)))]
+                    pins = [torch.empty(tuple(t.shape), dtype=t.dtype).pin_memory() for _ in range(max(2, int(slots)))]
                     for k in range(len(pins)):
                         free.put(k)
                 k = free.get()                       # every slot with the writer: wait for it (back-pressure)
