@@ -40,7 +40,7 @@ __device__ __forceinline__ uint4 pack8<_Float16>(const float* v) {
 // reflect index (torch 'reflect' padding on the right/bottom edge): n + k -> n - 2 - k
 __device__ __forceinline__ int reflect_hi(int i, int n) { return i < n ? i : 2 * n - 2 - i; }
 
-// UNSHUFFLE == 1: out[y][x][c] = in[y][x][2 - c] / 255 for c < 3, zero for 3 <= c < 32.
+// UNSHUFFLE == 1: out[y][x][c] = in[y][x][2 - c] / 255 for c < 3, zero for 3 <= c < out_cstride.
 // UNSHUFFLE == 2: out is ceil(H/2) x ceil(W/2); channel c*4 + dy*2 + dx = RGB channel c of input pixel
 //                 (2y+dy, 2x+dx) (torch.pixel_unshuffle order), zero for 12 <= ch < 32.
 // IN = uint8_t (/255) or uint16_t (/65535: RealESRGANer.enhance treats an image whose maximum exceeds 256 as 16-bit).
@@ -77,6 +77,7 @@ __global__ __launch_bounds__(256) void u8_to_nhwc_kernel(const IN* __restrict__ 
         o[1] = pack8<T>(v + 8);
         o[2] = make_uint4(0, 0, 0, 0);
         o[3] = make_uint4(0, 0, 0, 0);
+        for (int k = 4; k < out_cstride / 8; ++k) o[k] = make_uint4(0, 0, 0, 0);   // zeros up to the channel stride (a multiple of 8)
     }
 }
 

@@ -789,7 +789,7 @@ __global__ __launch_bounds__(256) void attn_softmax_rows_kernel(const T* __restr
             const V kv = __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(k + j * ldk));
             float s = 0.f;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) s += qf[c] * (float)kv[c];
+            for (int c = 0; c < 8; ++c) s += qf[c] * (c < d ? (float)kv[c] : 0.f);   // k masked like q: 0 * NaN of an unused channel is NaN
             return s;
         };
         float mx = -3.0e38f;
