@@ -971,6 +971,34 @@ int fw_hdr_clahe_u8(const uint8_t* plane, int height, int width, void* scratch, 
 int fw_hdr_saturation_u8(const uint8_t* bgr, int64_t n_pixels, const int32_t* hsv_div, float boost, float hue_scale, uint8_t* dst, void* stream);
 int fw_hdr_transfer_f32(const float* plane, int64_t count, const fw_hdr_params* params, uint16_t* dst, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Compression-artifact removal, the classical path (csrc/qp_artifacts.hip, DESIGN K21): the frame path of the reference's
+ * processors/qp_artifact_removal.py with backend 'opencv' on uint8 BGR H x W x 3 DEVICE frames; tests/qp_artifact_ref.py is the
+ * contract, byte for byte.  Tables are DEVICE float32 arrays that the host builds in float64:
+ *   color [768]: exp(k^2 * -0.5 / sigma_color^2); space [(2r+1)^2], r = max(d / 2, 1): exp((i^2 + j^2) * -0.5 / sigma_space^2), row-major
+ *   (entries outside the circular support are not read); gauss15: HOST float32 [15], cv2.getGaussianKernel(15, 0);
+ *   noise_table [65536]: standard-normal quantiles at (k + 0.5) / 65536 times 1 + 2 strength.
+ *   fw_bilateral_u8c3: cv2.bilateralFilter(frame, d, ...), d 2 .. 15, REFLECT_101, L1 colour distance, float32 sums in the stated order.
+ *   fw_gaussian5_u8: cv2.GaussianBlur(frame, (5, 5), 0) as exact fixed point, ([1 4 6 4 1] x [1 4 6 4 1] + 128) >> 8.
+ *   fw_qp_artifacts_u8: type_mask bit 0 blocking (bilateral with d, then the float64 blend with the 5 x 5 Gaussian on the rows and
+ *     columns next to a multiple of block_size: 4, 8, 16 or 32), bit 1 ringing (Canny 50 / 150, 5 x 5 maximum minus the edges, float32
+ *     5-tap Gaussian, float64 blend with the 5 x 5 Gaussian), bit 2 banding (gray, Laplacian, 1 - clip(|.| / 30), 15-tap float32 Gaussian,
+ *     out = trunc(clip(frame + noise * mask * strength, 0, 255)) in float64), applied in that order.  The dither is `noise`
+ *     (float32 H x W x 3) where it is not NULL, else noise_table[mix64(noise_key + pixel * 3 + channel) >> 48] with the splitmix64
+ *     finaliser; noise_key is the host-mixed (seed, frame index).  Tables of steps that the mask leaves out may be NULL.  scratch:
+ *     fw_qp_artifacts_scratch_bytes(height, width) bytes, 256-byte aligned.  With ringing the call synchronises `stream` (the
+ *     hysteresis reads its round flags on the host); otherwise it only enqueues.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, a side outside 1 .. 16384, channels other than 3,
+ * d outside 2 .. 15, a block size other than 4, 8, 16, 32, a type mask outside 0 .. 7, a strength outside (0, 1], an `out` that
+ * overlaps `frame`. */
+size_t fw_qp_artifacts_scratch_bytes(int height, int width);
+int fw_bilateral_u8c3(const uint8_t* frame, uint8_t* out, int height, int width, int channels, int d, const float* color, const float* space,
+                      void* stream);
+int fw_gaussian5_u8(const uint8_t* frame, uint8_t* out, int height, int width, int channels, void* stream);
+int fw_qp_artifacts_u8(const uint8_t* frame, uint8_t* out, int height, int width, int channels, int d, const float* color, const float* space,
+                       const float* gauss15, double strength, int block_size, int type_mask, const float* noise, const float* noise_table,
+                       uint64_t noise_key, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,3 +14,5 @@ from .color_grade import (LUT, DeviceColorGrader, LUTType, combine_luts, create_
 from .quality import DeviceFrameQualityScorer, FrameScore, QualityIssue, QualityReport  # noqa: E402,F401
 from .hdr import (ColorSpace, DeviceHDRConverter, HDRConfig, HDRConversionResult, HDRFormat, ToneMapping,  # noqa: E402,F401
                   create_hdr_converter)
+from .qp_artifacts import (ArtifactType, CompressionLevel, DeviceQPArtifactRemover, QPArtifactConfig, QPArtifactResult,  # noqa: E402,F401
+                           create_qp_artifact_remover)

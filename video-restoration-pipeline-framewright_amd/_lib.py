@@ -51,6 +51,7 @@ EXPORTS = [
     "fw_quality_scratch_bytes", "fw_quality_stats_u8",    # csrc/quality.hip, held by tests/test_quality_gpu.py
     "fw_hdr_scratch_bytes", "fw_hdr_convert", "fw_hdr_tonemap_f32", "fw_hdr_quantise_u8", "fw_hdr_clahe_u8", "fw_hdr_saturation_u8",
     "fw_hdr_transfer_f32",                                # csrc/hdr.hip, held by tests/test_hdr_gpu.py
+    "fw_qp_artifacts_scratch_bytes", "fw_bilateral_u8c3", "fw_gaussian5_u8", "fw_qp_artifacts_u8",    # csrc/qp_artifacts.hip, held by tests/test_qp_artifacts_gpu.py
     "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
     "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
     "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
@@ -417,6 +418,14 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_hdr_saturation_u8.argtypes = [vp, C.c_int64, vp, f32, f32, vp, vp]
     lib.fw_hdr_transfer_f32.restype = i32
     lib.fw_hdr_transfer_f32.argtypes = [vp, C.c_int64, vp, vp, vp]
+    lib.fw_qp_artifacts_scratch_bytes.restype = sz
+    lib.fw_qp_artifacts_scratch_bytes.argtypes = [i32, i32]
+    lib.fw_bilateral_u8c3.restype = i32
+    lib.fw_bilateral_u8c3.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.fw_gaussian5_u8.restype = i32
+    lib.fw_gaussian5_u8.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.fw_qp_artifacts_u8.restype = i32
+    lib.fw_qp_artifacts_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, C.c_uint64, vp, vp]
 
 
 def load() -> C.CDLL:

@@ -978,17 +978,33 @@ size_t preserve_edges_scratch_bytes(int H, int W) {
     return n * (4 + 2 + 1 + 4) + 256 + 64 + 64;   // two alignment gaps (<= 255, <= 63 bytes) and the round flags
 }
 
-void launch_preserve_edges(const uint8_t* orig, const uint8_t* den, int H, int W, int lo, int hi, void* scratch, uint8_t* out,
-                           hipStream_t st) {
+// The scratch of one frame: Sobel planes, the float32 row pass and the map, behind each other
+struct EdgeScratch {
+    short *dxy, *mag;
+    float* rows;
+    uint8_t* map;
+    int* changed;
+    EdgeScratch(void* scratch, size_t n) {
+        char* s = (char*)scratch;
+        dxy = (short*)s;
+        mag = (short*)(s + n * 4);
+        rows = (float*)(s + ((n * 6 + 255) / 256) * 256);
+        map = (uint8_t*)(rows + n);
+        changed = (int*)(((size_t)(map + n) + 63) / 64 * 64);
+    }
+};
+
+static int pixel_blocks(size_t n) { return (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); }
+
+// The edge map: Sobel, non-maximum suppression and the hysteresis to its fixed point.  2 marks an edge pixel.
+const uint8_t* launch_canny_edge_map(const uint8_t* bgr, int H, int W, int lo, int hi, void* scratch, hipStream_t st) {
     const size_t n = (size_t)H * W;
-    char* s = (char*)scratch;
-    short* dxy = (short*)s;
-    short* mag = (short*)(s + n * 4);
-    float* rows = (float*)(s + ((n * 6 + 255) / 256) * 256);
-    uint8_t* map = (uint8_t*)(rows + n);
-    int* changed = (int*)(((size_t)(map + n) + 63) / 64 * 64);
-    const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-    hipLaunchKernelGGL(pe_sobel_kernel, dim3(blocks), dim3(256), 0, st, orig, H, W, dxy, mag);
+    const EdgeScratch e(scratch, n);
+    short *dxy = e.dxy, *mag = e.mag;
+    uint8_t* map = e.map;
+    int* changed = e.changed;
+    const int blocks = pixel_blocks(n);
+    hipLaunchKernelGGL(pe_sobel_kernel, dim3(blocks), dim3(256), 0, st, bgr, H, W, dxy, mag);
     hipLaunchKernelGGL(pe_nms_kernel, dim3(blocks), dim3(256), 0, st, dxy, mag, H, W, lo, hi, map);
     const int tiles = ((W + 31) / 32) * ((H + 31) / 32);
     // Global sweeps until no tile changed.  A chain of weak pixels that crosses T tiles needs T sweeps; almost every frame is done
@@ -1005,6 +1021,15 @@ void launch_preserve_edges(const uint8_t* orig, const uint8_t* den, int H, int W
         converged = flags[BATCH - 1] == 0;
     }
     if (!converged) throw Error(4, "preserve_edges: the hysteresis did not reach its fixed point");
+    return map;
+}
+
+void launch_preserve_edges(const uint8_t* orig, const uint8_t* den, int H, int W, int lo, int hi, void* scratch, uint8_t* out,
+                           hipStream_t st) {
+    const size_t n = (size_t)H * W;
+    const uint8_t* map = launch_canny_edge_map(orig, H, W, lo, hi, scratch, st);
+    float* rows = EdgeScratch(scratch, n).rows;
+    const int blocks = pixel_blocks(n);
     hipLaunchKernelGGL(pe_mask_rows_kernel, dim3(blocks), dim3(256), 0, st, map, H, W, rows);
     hipLaunchKernelGGL(pe_blend_kernel, dim3(blocks), dim3(256), 0, st, orig, den, rows, H, W, out);
     FW_HIP_CHECK(hipGetLastError());

@@ -299,6 +299,9 @@ void launch_flow_accumulate_finish(const double* acc, const double* wsum, long n
 size_t preserve_edges_scratch_bytes(int H, int W);
 void launch_preserve_edges(const uint8_t* orig, const uint8_t* den, int H, int W, int lo, int hi, void* scratch, uint8_t* out,
                            hipStream_t st);
+// its first half alone: cv2.Canny(BGR2GRAY(bgr), lo, hi) as a map inside `scratch` (preserve_edges_scratch_bytes) in which 2 marks an
+// edge pixel; synchronises the stream (the hysteresis reads its round flags on the host)
+const uint8_t* launch_canny_edge_map(const uint8_t* bgr, int H, int W, int lo, int hi, void* scratch, hipStream_t st);
 
 // ---- IFNet building blocks (ifnet_ops.hip), used by the whole-model engine in ifnet.hip -------------------------------------
 void launch_ifnet_u8_to_rgb(const uint8_t* in_bgr, int H, int W, int Hp, int Wp, float* out, hipStream_t st);

@@ -55,11 +55,17 @@ class DeviceRestorationPipeline:
     ``quality_scorer``, which scores the 8-bit frames, every output frame is converted to a new uint16 PQ / HLG tensor.  It is
     elementwise apart from the frame's own CLAHE histograms, so the streaming forms have it too, and `run_stream`'s pinned ring
     takes the frames' type.  `close` releases it, and every other stage that has a `close`.
+
+    ``artifact_remover`` (a `qp_artifacts.DeviceQPArtifactRemover`; opt-in) removes compression artifacts from the input frames behind
+    the bar crop and in front of the denoiser, where the reference has its step 5c in front of 5d, with the quantisation parameter
+    ``artifact_qp`` (None: the remover's `manual_qp`, then 28).  It works frame by frame and its dither is keyed by the frame's position
+    in the clip, so the streaming forms (`DeviceQPArtifactRemover.stream`) equal `run_device`.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
                  deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True,
-                 quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0, hdr_converter=None):
+                 quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0, hdr_converter=None, artifact_remover=None,
+                 artifact_qp=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -71,11 +77,12 @@ class DeviceRestorationPipeline:
         self.quality_scorer, self.input_quality_scorer, self.quality_fps = quality_scorer, input_quality_scorer, float(quality_fps)
         self.last_quality_report = self.last_input_quality_report = None
         self.hdr_converter = hdr_converter
+        self.artifact_remover, self.artifact_qp = artifact_remover, artifact_qp
 
     def _stages(self) -> tuple:
         """Every configured stage slot, in the order `_device` asks them: a new stage adds its name here."""
         return (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
-                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter)
+                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter, self.artifact_remover)
 
     def close(self) -> None:
         """Closes every stage that can be closed (the engines free their native handles, the HDR converter its tables)."""
@@ -110,6 +117,8 @@ class DeviceRestorationPipeline:
                 cur = list(self.vhs_processor.process(cur))
             if self.aspect_handler is not None and self.crop_bars:
                 cur = list(self.aspect_handler.crop_letterbox(cur))
+            if self.artifact_remover is not None:
+                cur = self.artifact_remover.process_device(cur, self.artifact_qp)
             if self.denoiser is not None:
                 cur = self.denoiser.denoise_clip_device(cur)
             if self.upscaler is not None and self.deduplicator is not None and cur:
@@ -145,7 +154,8 @@ class DeviceRestorationPipeline:
     def _device(self):
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
-        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers, the HDR converter.
+        the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers, the HDR converter, the
+        artifact remover.
         Every stage answers through `_lib.owner_device`: a new stage adds its name to `_stages`."""
         for stage in self._stages():
             dev = _lib.owner_device(stage)
@@ -233,6 +243,8 @@ class DeviceRestorationPipeline:
                 g = self.vhs_processor.stream(g, block=block)
             if self.aspect_handler is not None and self.crop_bars:
                 g = self.aspect_handler.stream(g, block=block)
+            if self.artifact_remover is not None:
+                g = self.artifact_remover.stream(g, self.artifact_qp)
             if self.denoiser is not None:
                 g = self._gen_denoise(g, block)
             if self.upscaler is not None:
