@@ -571,6 +571,26 @@ int fw_restormer_finalize(fw_restormer* net);
 int fw_restormer_denoise_u8(fw_restormer* net, const uint8_t* in_bgr, int in_loc, int height, int width, uint8_t* out_bgr,
                             int out_loc, float* out_rgb_f32, void* stream);
 size_t fw_restormer_workspace_bytes(fw_restormer* net, int height, int width);   /* 0 before finalize */
+/* Single steps of a forward on the caller's device buffers, launched exactly as a forward launches them (tests, tools).
+ * run_block: one transformer block, `key` as fw_restormer_set_tensor names blocks ("encoder_level1.0.", "latent.0.",
+ *   "decoder_level1.0."), in place on the fp32 stream [height][width][pad32(c)] (lanes c .. pad32(c) - 1 hold zeros and keep them);
+ *   attn_out (optional, device fp32 [heads][c / heads][c / heads]) receives the softmaxed attention matrix.
+ * block_paths: which kernels that block dispatches to, as FW_REST_PATH_* bits.
+ * run_step: what lies between two stages, on a source of height x width pixels.  "down1_2" / "down2_3" / "down3_4": conv3x3 +
+ *   PixelUnshuffle, src [h][w][pad32(c)] -> dst [h/2][w/2][pad32(2c)] (even sides); "up4_3" / "up3_2" / "up2_1": conv3x3,
+ *   PixelShuffle, the copy of skip [2h][2w][pad32(c/2)] behind it and, for the first two, the reduce_chan 1x1:
+ *   src [h][w][pad32(c)] -> dst [2h][2w][pad32(c/2)] ("up2_1": [2h][2w][pad32(c)], the concatenation itself); "output": the last
+ *   conv3x3 alone, src [h][w][96] -> dst [h][w][64] with the RGB residual in lanes 0..2 (fw_tap_post_u8 follows it).  Lanes of dst
+ *   behind the real channels are written as zeros. */
+#define FW_REST_PATH_FRONT_QKV 1   /* norm1 + qkv + qkv_dwconv in one kernel (c = 48, 96) */
+#define FW_REST_PATH_FRONT_FFN 2   /* norm2 + project_in + dwconv + GELU gate in one kernel (c = 48, 96) */
+#define FW_REST_PATH_QK_DIRECT 4   /* the qkv front writes q / k in the Gram kernel's operand layout */
+#define FW_REST_PATH_MERGE_PROJ 8  /* project_out folded into the attention matrix: one residual GEMM */
+#define FW_REST_PATH_GEMM16 16     /* qkv / project_in on the pipelined GEMM kernel (c = 192, 384) */
+int fw_restormer_run_block(fw_restormer* net, const char* key, float* stream_f32, int height, int width, float* attn_out, void* stream);
+int fw_restormer_block_paths(fw_restormer* net, const char* key, int* flags);
+int fw_restormer_run_step(fw_restormer* net, const char* step, const float* src_f32, const float* skip_f32, int height, int width,
+                          float* dst_f32, void* stream);
 int fw_restormer_destroy(fw_restormer* net);
 
 /* `TemporalDenoiser._preserve_edges` (reference src/framewright/processors/temporal_denoise.py:1636-1667): the Canny edges of

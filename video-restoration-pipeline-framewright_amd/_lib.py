@@ -17,6 +17,7 @@ FW_OK, FW_ERR_INVALID, FW_ERR_OOM, FW_ERR_HIP, FW_ERR_INTERNAL = 0, 1, 2, 3, 4
 FW_HOST, FW_DEVICE = 0, 1
 FW_DTYPE_BF16, FW_DTYPE_F16 = 0, 1
 FW_NAF_PATH_FRONT, FW_NAF_PATH_TAIL128, FW_NAF_PATH_TAIL64, FW_NAF_PATH_GEMM, FW_NAF_PATH_FUSE_LN = 1, 2, 4, 8, 16
+FW_REST_PATH_FRONT_QKV, FW_REST_PATH_FRONT_FFN, FW_REST_PATH_QK_DIRECT, FW_REST_PATH_MERGE_PROJ, FW_REST_PATH_GEMM16 = 1, 2, 4, 8, 16
 DTYPES = {"bf16": FW_DTYPE_BF16, "bfloat16": FW_DTYPE_BF16, "f16": FW_DTYPE_F16, "fp16": FW_DTYPE_F16,
           "float16": FW_DTYPE_F16, "half": FW_DTYPE_F16}
 
@@ -38,7 +39,7 @@ EXPORTS = [
     "fw_srvgg_create", "fw_srvgg_set_tensor", "fw_srvgg_finalize", "fw_srvgg_upscale_u8", "fw_srvgg_upscale_u16", "fw_resize_lanczos4_u16", "fw_srvgg_workspace_bytes", "fw_srvgg_flops",
     "fw_srvgg_destroy",
     "fw_restormer_create", "fw_restormer_set_tensor", "fw_restormer_finalize", "fw_restormer_denoise_u8",
-    "fw_restormer_workspace_bytes", "fw_restormer_destroy", "fw_preserve_edges_scratch_bytes", "fw_preserve_edges_u8",
+    "fw_restormer_workspace_bytes", "fw_restormer_destroy", "fw_restormer_run_block", "fw_restormer_block_paths", "fw_restormer_run_step", "fw_preserve_edges_scratch_bytes", "fw_preserve_edges_u8",
     "fw_u8_to_nhwc", "fw_pixel_shuffle_add_u8",
     "fw_layernorm_nhwc", "fw_pack_pointwise", "fw_pointwise_nhwc", "fw_dwconv3x3_nhwc", "fw_attn_workspace_floats",
     "fw_attn_matrix", "fw_attn_apply", "fw_attn_pack", "fw_attn_proj_pack", "fw_pixel_shuffle2_f32", "fw_copy_channels_f32", "fw_f32_to_planar", "fw_tap_post_u8",
@@ -259,6 +260,12 @@ def _declare_ifnet(lib: C.CDLL) -> None:
     lib.fw_restormer_workspace_bytes.argtypes = [vp, i32, i32]
     lib.fw_restormer_destroy.restype = i32
     lib.fw_restormer_destroy.argtypes = [vp]
+    lib.fw_restormer_run_block.restype = i32
+    lib.fw_restormer_run_block.argtypes = [vp, C.c_char_p, vp, i32, i32, vp, vp]
+    lib.fw_restormer_block_paths.restype = i32
+    lib.fw_restormer_block_paths.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
+    lib.fw_restormer_run_step.restype = i32
+    lib.fw_restormer_run_step.argtypes = [vp, C.c_char_p, vp, vp, i32, i32, vp, vp]
     lib.fw_preserve_edges_scratch_bytes.restype = sz
     lib.fw_preserve_edges_scratch_bytes.argtypes = [i32, i32]
     lib.fw_preserve_edges_u8.restype = i32

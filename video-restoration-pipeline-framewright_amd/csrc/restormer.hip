@@ -132,22 +132,51 @@ void chk(int status) {
 const char* GLOBAL_CONV3[] = {"patch_embed.proj.weight", "down1_2.body.0.weight", "down2_3.body.0.weight", "down3_4.body.0.weight",
                               "up4_3.body.0.weight", "up3_2.body.0.weight", "up2_1.body.0.weight", "output.weight"};
 
-void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8_t* d_out, float* d_rgb, hipStream_t st_) {
-    void* st = (void*)st_;
-    const int dt = (int)n->dt;
-    const bool run = !A.plan;
-    auto f32 = [&](size_t elems) { return (float*)A.take(elems * 4); };
-    auto typ = [&](size_t elems) { return A.take(elems * 2); };
-    auto zero = [&](void* p, size_t bytes) {
+// what a forward runs between its stages (Sequencer::step), by the names fw_restormer_run_step takes
+enum { STEP_DOWN1_2, STEP_DOWN2_3, STEP_DOWN3_4, STEP_UP4_3, STEP_UP3_2, STEP_UP2_1, STEP_OUTPUT, STEP_COUNT };
+const char* STEP_NAMES[STEP_COUNT] = {"down1_2", "down2_3", "down3_4", "up4_3", "up3_2", "up2_1", "output"};
+
+// which kernels a block goes to: the one place that decides it, for Sequencer::block and for fw_restormer_block_paths
+struct BlockDispatch {
+    bool front_qkv;    // norm1 + qkv + qkv_dwconv in one kernel (pw_dw_fused.hip, c = 48 / 96)
+    bool front_ffn;    // norm2 + project_in + dwconv + GELU gate in one kernel
+    bool qk_direct;    // ... and the qkv front writes q / k in the Gram kernel's operand layout
+    bool merge_proj;   // project_out folded into the attention matrix: one residual GEMM
+    bool gemm16;       // qkv / project_in on the pipelined GEMM kernel (c = 192 / 384)
+};
+
+BlockDispatch block_dispatch(const fw_restormer* n, const RBlock& b) {
+    BlockDispatch d{};
+    d.front_qkv = b.front_qkv.p != nullptr;
+    d.front_ffn = b.front_ffn.p != nullptr;
+    d.qk_direct = d.front_qkv && n->qk_direct;
+    d.merge_proj = n->merge_proj;
+    d.gemm16 = b.qkv16.p != nullptr && b.pin16.p != nullptr;
+    return d;
+}
+
+// The launch sequence of a forward and of its single steps (fw_restormer_run_block / _run_step) over one workspace arena; with a
+// planning arena nothing is launched and only the arena's peak is measured.
+struct Sequencer {
+    fw_restormer* n;
+    Arena& A;
+    hipStream_t st_;
+    void* st;
+    const int dt;
+    const bool run;
+    Sequencer(fw_restormer* net, Arena& arena, hipStream_t stream) : n(net), A(arena), st_(stream), st((void*)stream), dt((int)net->dt), run(!arena.plan) {}
+    float* f32(size_t elems) { return (float*)A.take(elems * 4); }
+    void* typ(size_t elems) { return A.take(elems * 2); }
+    void zero(void* p, size_t bytes) {
         if (run) FW_HIP_CHECK(hipMemsetAsync(p, 0, bytes, st_));
-    };
+    }
 #define RUN(expr)            \
     do {                     \
         if (run) chk(expr);  \
     } while (0)
 
     // 3x3 conv of the fp32 stream x [h*w][cin_pad] -> fp32 y [h*w][cout_pad] (y allocated by the caller)
-    auto conv3 = [&](const Conv3& cv, const float* x, int h, int w, float* y) {
+    void conv3(const Conv3& cv, const float* x, int h, int w, float* y) {
         const long M = (long)h * w;
         const size_t mark = A.top;
         void* xp = typ((size_t)cv.cin_pad * M);
@@ -165,12 +194,14 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
                                        1.f, nullptr, 1.f, nullptr, 0, cv.cout_pad, (int)g * 64, nullptr, 32, 0, 0, y, st));
         }
         A.top = mark;
-    };
+    }
 
-    // one transformer block on the fp32 stream x [h*w][cp], updated in place
-    auto block = [&](const RBlock& b, float* x, int h, int w) {
+    // one transformer block on the fp32 stream x [h*w][cp], updated in place; attn_out (optional, device fp32 [heads][ch][ch]) receives
+    // the softmaxed attention matrix
+    void block(const RBlock& b, float* x, int h, int w, float* attn_out = nullptr) {
         const long M = (long)h * w;
         const int c = b.c, cp = b.cp, hp = b.hp, heads = b.heads, ch = b.ch;
+        const BlockDispatch disp = block_dispatch(n, b);
         const size_t mark = A.top;
         void* t = typ((size_t)M * cp);
         const int nq = pad_to(3 * cp, 64);          // output channels of the fused qkv kernel: whole 64-channel chunks (q | k | v | zeros)
@@ -186,16 +217,16 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
         };
         float* attn = f32((size_t)heads * ch * ch);
         float* aws = f32(fw_attn_workspace_floats(heads, ch));
-        if (b.front_qkv.p) {
+        if (disp.front_qkv) {
             // q and k leave the kernel already in the Gram kernel's operand layout (no pixel-major copy of them, no transpose pass)
             // (q | k: 2 cp channel rows per pixel group = whole chunks at 64 and at 96 channels; v: the chunks behind them, from channel 0 of qkv2)
             const long Mp = pw_dw_transposed_pixels(h, w);
-            void* qT = n->qk_direct ? typ((size_t)Mp * 2 * cp) : nullptr;
+            void* qT = disp.qk_direct ? typ((size_t)Mp * 2 * cp) : nullptr;
             PwDwParams f{};
             f.x = x; f.ldx = cp; f.H = h; f.W = w; f.cin = c; f.ln_eps = 1e-5f; f.blocks = b.front_qkv.p; f.n_chunks = nq / 64; f.mode = PWDW_NONE;
-            f.out = qkv2; f.ldo = n->qk_direct ? nq - 2 * cp : nq; f.qT = qT; f.t_chunks = 2 * cp / 64; f.t_ld = 2 * cp;
+            f.out = qkv2; f.ldo = disp.qk_direct ? nq - 2 * cp : nq; f.qT = qT; f.t_chunks = 2 * cp / 64; f.t_ld = 2 * cp;
             if (run) launch_pw_dw(n->dt, f, st_);
-            if (n->qk_direct) {
+            if (disp.qk_direct) {
                 v = qkv2;
                 v_ld = nq - 2 * cp;
                 if (run)
@@ -211,20 +242,21 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
             // a typed-store 1x1 GEMM of the staged levels on the pipelined kernel (256-channel tiles: the output rows are qld wide)
             auto gemm = [&](const DevBuf& w, const DevBuf& w16, int tiles, int n16, void* out, long ld) {
                 PointwiseParams p{};
-                p.a = t; p.lda = cp; p.M = M; p.K = cp; p.wpk = w.p; p.wpk16 = w16.p; p.N_tiles = w16.p ? n16 / 32 : tiles; p.mode = PW_STORE;
+                p.a = t; p.lda = cp; p.M = M; p.K = cp; p.wpk = w.p; p.wpk16 = w16.p; p.N_tiles = disp.gemm16 ? n16 / 32 : tiles; p.mode = PW_STORE;
                 p.out_typed = out; p.ldo = ld;
                 if (run) launch_pointwise(n->dt, p, st_);
             };
-            const long qld = b.qkv16.p ? b.qkv16_n : 3 * cp;
+            const long qld = disp.gemm16 ? b.qkv16_n : 3 * cp;
             void* qkv = typ((size_t)M * qld);
             gemm(b.qkv, b.qkv16, b.qkv_t, b.qkv16_n, qkv, qld);
             RUN(fw_dwconv3x3_nhwc(dt, qkv, qld, h, w, 3 * cp, (const float*)b.qkv_dw.p, 0, qkv2, 3 * cp, st));
             void* scratch = typ(fw_attn_qk_scratch_elems(M, heads, ch));
             RUN(fw_attn_matrix_mfma(dt, qkv2, 3 * cp, M, cp, heads, ch, (const float*)b.temp.p, aws, scratch, attn, st));
         }
+        if (attn_out && run) FW_HIP_CHECK(hipMemcpyAsync(attn_out, attn, (size_t)heads * ch * ch * 4, hipMemcpyDeviceToDevice, st_));
         // attn @ v as a 1x1 convolution with the block-diagonal attention matrix on the MFMA GEMM
         void* apk = typ(fw_pack_pointwise(dt, nullptr, cp, cp, nullptr));
-        if (n->merge_proj) {
+        if (disp.merge_proj) {
             // x += (project_out . attn) v: the two matrices are multiplied first (c x c x ch MACs), the pixels see one GEMM
             RUN(fw_attn_proj_pack(dt, attn, (const float*)b.proj_f32.p, heads, ch, cp, b.proj_t, apk, st));
             RUN(fw_pointwise_nhwc(dt, v, 0, v_ld, M, cp, apk, nullptr, b.proj_t, nullptr, 0, x, cp, x, (const float*)n->ones.p, st));
@@ -234,15 +266,15 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
             RUN(fw_pointwise_nhwc(dt, t, 0, cp, M, cp, b.proj.p, nullptr, b.proj_t, nullptr, 0, x, cp, x, (const float*)n->ones.p, st));
         }
         void* g2 = typ((size_t)M * hp);
-        if (b.front_ffn.p) {
+        if (disp.front_ffn) {
             front(b.front_ffn, 2 * hp, PWDW_GATE_GELU, g2, hp);
         } else {
             RUN(fw_layernorm_nhwc(dt, x, cp, M, c, (const float*)b.n2w.p, (const float*)b.n2b.p, 1e-5f, t, cp, cp, st));
-            const long gld = b.pin16.p ? b.pin16_n : 2 * hp;
+            const long gld = disp.gemm16 ? b.pin16_n : 2 * hp;
             void* g = typ((size_t)M * gld);
             {
                 PointwiseParams p{};
-                p.a = t; p.lda = cp; p.M = M; p.K = cp; p.wpk = b.pin.p; p.wpk16 = b.pin16.p; p.N_tiles = b.pin16.p ? b.pin16_n / 32 : b.pin_t; p.mode = PW_STORE;
+                p.a = t; p.lda = cp; p.M = M; p.K = cp; p.wpk = b.pin.p; p.wpk16 = b.pin16.p; p.N_tiles = disp.gemm16 ? b.pin16_n / 32 : b.pin_t; p.mode = PW_STORE;
                 p.out_typed = g; p.ldo = gld;
                 if (run) launch_pointwise(n->dt, p, st_);
             }
@@ -250,16 +282,17 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
         }
         RUN(fw_pointwise_nhwc(dt, g2, 0, hp, M, hp, b.pout.p, nullptr, b.pout_t, nullptr, 0, x, cp, x, (const float*)n->ones.p, st));
         A.top = mark;
-    };
-    auto stage = [&](int si, float* x, int h, int w) {
+    }
+    void stage(int si, float* x, int h, int w) {
         const Stage& s = n->stages[si];
         for (int i = 0; i < s.n; ++i) block(n->blocks.at(s.name + "." + std::to_string(i) + "."), x, h, w);
-    };
+    }
     // conv3x3 (c -> c/2) + PixelUnshuffle(2): fp32 [h*w][stream_pad(c)] -> fp32 [(h/2)*(w/2)][stream_pad(2c)]
-    auto down = [&](const char* key, const float* x, int h, int w, int c) {
+    // (down, up_cat, reduce: the result goes to `o` where the caller has a buffer for it, else to the arena)
+    float* down(const char* key, const float* x, int h, int w, int c, float* o = nullptr) {
         const Conv3& cv = n->convs.at(key);
         const size_t ostride = stream_pad(2 * c);
-        float* o = f32((size_t)(h / 2) * (w / 2) * ostride);
+        if (!o) o = f32((size_t)(h / 2) * (w / 2) * ostride);
         zero(o, (size_t)(h / 2) * (w / 2) * ostride * 4);
         const size_t mark = A.top;
         float* y = f32((size_t)h * w * cv.cout_pad);
@@ -267,12 +300,12 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
         RUN(fw_pixel_shuffle2_f32(y, cv.cout_pad, h / 2, w / 2, c / 2, o, (long)ostride, 0, 1, st));
         A.top = mark;
         return o;
-    };
+    }
     // cat([PixelShuffle(2)(conv3x3 (c -> 2c)(x)), skip]): fp32 [(2h)*(2w)][stream_pad(c)], c/2 + c/2 channels
-    auto up_cat = [&](const char* key, const float* x, int h, int w, int c, const float* skip, int skip_stride) {
+    float* up_cat(const char* key, const float* x, int h, int w, int c, const float* skip, int skip_stride, float* o = nullptr) {
         const Conv3& cv = n->convs.at(key);
         const size_t ostride = stream_pad(c);
-        float* o = f32((size_t)4 * h * w * ostride);
+        if (!o) o = f32((size_t)4 * h * w * ostride);
         zero(o, (size_t)4 * h * w * ostride * 4);
         const size_t mark = A.top;
         float* y = f32((size_t)h * w * cv.cout_pad);
@@ -281,42 +314,79 @@ void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8
         A.top = mark;
         RUN(fw_copy_channels_f32(skip, skip_stride, (long)4 * h * w, c / 2, o, (long)ostride, c / 2, st));
         return o;
-    };
-    auto reduce = [&](const DevBuf& wpk, int tiles, const float* x, int x_stride, long M, int cin) {
-        float* o = f32((size_t)M * 32 * tiles);
+    }
+    float* reduce(const DevBuf& wpk, int tiles, const float* x, int x_stride, long M, int cin, float* o = nullptr) {
+        if (!o) o = f32((size_t)M * 32 * tiles);
         RUN(fw_pointwise_nhwc(dt, x, 1, x_stride, M, cin, wpk.p, nullptr, tiles, nullptr, 0, o, 32 * tiles, nullptr, nullptr, st));
         return o;
-    };
+    }
 
-    const int d = n->dim;
-    void* x0 = typ((size_t)H * W * 32);
-    RUN(fw_u8_to_nhwc(dt, d_in, H, W, x0, 32, st));
-    const Conv3& pe = n->convs.at("patch_embed.proj.weight");
-    float* e1 = f32((size_t)H * W * pe.cout_pad);
-    for (size_t g = 0; g < pe.groups.size(); ++g)
-        RUN(fw_conv3x3_nhwc_ex(dt, x0, 32, 0, 1, H, W, pe.groups[g].p, (const float*)n->conv_bias.p, 2, 0, 0, nullptr, 1.f, nullptr, 1.f, nullptr, 0,
-                               pe.cout_pad, (int)g * 64, nullptr, 32, 0, 0, e1, st));
-    stage(0, e1, H, W);
-    float* e2 = down("down1_2.body.0.weight", e1, H, W, d);
-    stage(1, e2, H / 2, W / 2);
-    float* e3 = down("down2_3.body.0.weight", e2, H / 2, W / 2, 2 * d);
-    stage(2, e3, H / 4, W / 4);
-    float* lat = down("down3_4.body.0.weight", e3, H / 4, W / 4, 4 * d);
-    stage(3, lat, H / 8, W / 8);
-    float* c3 = up_cat("up4_3.body.0.weight", lat, H / 8, W / 8, 8 * d, e3, stream_pad(4 * d));
-    float* d3 = reduce(n->red3, n->red3_t, c3, stream_pad(8 * d), (long)(H / 4) * (W / 4), 8 * d);
-    stage(4, d3, H / 4, W / 4);
-    float* c2 = up_cat("up3_2.body.0.weight", d3, H / 4, W / 4, 4 * d, e2, stream_pad(2 * d));
-    float* d2 = reduce(n->red2, n->red2_t, c2, stream_pad(4 * d), (long)(H / 2) * (W / 2), 4 * d);
-    stage(5, d2, H / 2, W / 2);
-    float* d1 = up_cat("up2_1.body.0.weight", d2, H / 2, W / 2, 2 * d, e1, stream_pad(d));
-    stage(6, d1, H, W);
-    stage(7, d1, H, W);
-    const Conv3& oc = n->convs.at("output.weight");
-    float* y = f32((size_t)H * W * oc.cout_pad);
-    conv3(oc, d1, H, W, y);
-    RUN(fw_tap_post_u8(d_in, y, H, W, W, oc.cout_pad, d_out, d_rgb, st));
+    // What lies between two stages, on a source of h x w pixels: the down convs (STEP_DOWN1_2 ..: conv3 + unshuffle into a zeroed stream
+    // of twice the channels), the up steps (conv3, shuffle and the skip copy into a zeroed stream, then the reduce_chan GEMM where the
+    // network has one) and the output conv (fp32 [h*w][cout_pad]: fw_tap_post_u8 follows it in a forward)
+    float* step(int s, const float* x, const float* skip, int h, int w, float* o = nullptr) {
+        const int d = n->dim;
+        switch (s) {
+            case STEP_DOWN1_2: return down("down1_2.body.0.weight", x, h, w, d, o);
+            case STEP_DOWN2_3: return down("down2_3.body.0.weight", x, h, w, 2 * d, o);
+            case STEP_DOWN3_4: return down("down3_4.body.0.weight", x, h, w, 4 * d, o);
+            case STEP_UP4_3: {
+                float* c3 = up_cat("up4_3.body.0.weight", x, h, w, 8 * d, skip, stream_pad(4 * d));
+                return reduce(n->red3, n->red3_t, c3, stream_pad(8 * d), (long)4 * h * w, 8 * d, o);
+            }
+            case STEP_UP3_2: {
+                float* c2 = up_cat("up3_2.body.0.weight", x, h, w, 4 * d, skip, stream_pad(2 * d));
+                return reduce(n->red2, n->red2_t, c2, stream_pad(4 * d), (long)4 * h * w, 4 * d, o);
+            }
+            case STEP_UP2_1: return up_cat("up2_1.body.0.weight", x, h, w, 2 * d, skip, stream_pad(d), o);
+            default: {
+                const Conv3& oc = n->convs.at("output.weight");
+                if (!o) o = f32((size_t)h * w * oc.cout_pad);
+                conv3(oc, x, h, w, o);
+                return o;
+            }
+        }
+    }
+
+    void forward(const uint8_t* d_in, int H, int W, uint8_t* d_out, float* d_rgb) {
+        void* x0 = typ((size_t)H * W * 32);
+        RUN(fw_u8_to_nhwc(dt, d_in, H, W, x0, 32, st));
+        const Conv3& pe = n->convs.at("patch_embed.proj.weight");
+        float* e1 = f32((size_t)H * W * pe.cout_pad);
+        for (size_t g = 0; g < pe.groups.size(); ++g)
+            RUN(fw_conv3x3_nhwc_ex(dt, x0, 32, 0, 1, H, W, pe.groups[g].p, (const float*)n->conv_bias.p, 2, 0, 0, nullptr, 1.f, nullptr, 1.f, nullptr, 0,
+                                   pe.cout_pad, (int)g * 64, nullptr, 32, 0, 0, e1, st));
+        stage(0, e1, H, W);
+        float* e2 = step(STEP_DOWN1_2, e1, nullptr, H, W);
+        stage(1, e2, H / 2, W / 2);
+        float* e3 = step(STEP_DOWN2_3, e2, nullptr, H / 2, W / 2);
+        stage(2, e3, H / 4, W / 4);
+        float* lat = step(STEP_DOWN3_4, e3, nullptr, H / 4, W / 4);
+        stage(3, lat, H / 8, W / 8);
+        float* d3 = step(STEP_UP4_3, lat, e3, H / 8, W / 8);
+        stage(4, d3, H / 4, W / 4);
+        float* d2 = step(STEP_UP3_2, d3, e2, H / 4, W / 4);
+        stage(5, d2, H / 2, W / 2);
+        float* d1 = step(STEP_UP2_1, d2, e1, H / 2, W / 2);
+        stage(6, d1, H, W);
+        stage(7, d1, H, W);
+        float* y = step(STEP_OUTPUT, d1, nullptr, H, W);
+        RUN(fw_tap_post_u8(d_in, y, H, W, W, n->convs.at("output.weight").cout_pad, d_out, d_rgb, st));
+    }
 #undef RUN
+};
+
+void forward(fw_restormer* n, Arena& A, const uint8_t* d_in, int H, int W, uint8_t* d_out, float* d_rgb, hipStream_t st) {
+    Sequencer(n, A, st).forward(d_in, H, W, d_out, d_rgb);
+}
+
+// the block of a key such as "latent.0." and the stage it belongs to; nullptr where the network has none
+const RBlock* find_block(const fw_restormer* n, const std::string& key, int* stage_index) {
+    auto it = n->blocks.find(key);
+    if (it == n->blocks.end()) return nullptr;
+    for (size_t si = 0; si < n->stages.size(); ++si)
+        if (key.compare(0, n->stages[si].name.size() + 1, n->stages[si].name + ".") == 0) *stage_index = (int)si;
+    return &it->second;
 }
 
 }  // namespace
@@ -548,6 +618,78 @@ int fw_restormer_denoise_u8(fw_restormer* n, const uint8_t* in_bgr, int in_loc, 
             FW_HIP_CHECK(hipMemcpyAsync(out_bgr, d_out, (size_t)H * W * 3, hipMemcpyDeviceToHost, st));
             FW_HIP_CHECK(hipStreamSynchronize(st));
         }
+    });
+}
+
+// ---- single steps of a forward, for tests and tools: what the engine runs for one block / between two stages, on the caller's buffers ----
+int fw_restormer_run_block(fw_restormer* n, const char* key_c, float* stream_f32, int H, int W, float* attn_out, void* stream) {
+    if (!n || !key_c || !stream_f32) return fail(FW_ERR_INVALID, "fw_restormer_run_block: NULL argument");
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(FW_ERR_INVALID, "fw_restormer_run_block: bad size");
+    const std::string key(key_c);
+    {
+        std::lock_guard<std::mutex> lk(n->mu);
+        if (!n->want.count(key + "norm1.body.weight")) return fail(FW_ERR_INVALID, "fw_restormer_run_block: unknown block '" + key + "'");
+    }
+    int rc = fw_restormer_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        int si = 0;
+        const RBlock* b = find_block(n, key, &si);
+        if (!b) throw Error(FW_ERR_INVALID, "fw_restormer_run_block: unknown block '" + key + "'");
+        const int level[8] = {0, 1, 2, 3, 2, 1, 0, 0};   // the forward in which this block sees H x W pixels has a frame of (H << level) x (W << level)
+        if (((long)H << level[si]) > 16384 || ((long)W << level[si]) > 16384) throw Error(FW_ERR_INVALID, "fw_restormer_run_block: size beyond the largest frame");
+        Arena P;
+        P.plan = true;
+        Sequencer(n, P, nullptr).block(*b, nullptr, H, W);
+        ensure_workspace(n->ws, P.peak);
+        Arena A;
+        A.base = (char*)n->ws.p;
+        Sequencer(n, A, st).block(*b, stream_f32, H, W, attn_out);
+    });
+}
+
+int fw_restormer_block_paths(fw_restormer* n, const char* key_c, int* flags) {
+    if (!n || !key_c || !flags) return fail(FW_ERR_INVALID, "fw_restormer_block_paths: NULL argument");
+    int rc = fw_restormer_finalize(n);
+    if (rc != FW_OK) return rc;
+    std::lock_guard<std::mutex> lk(n->mu);
+    int si = 0;
+    const RBlock* b = find_block(n, key_c, &si);
+    if (!b) return fail(FW_ERR_INVALID, std::string("fw_restormer_block_paths: unknown block '") + key_c + "'");
+    const BlockDispatch d = block_dispatch(n, *b);   // what Sequencer::block consults
+    *flags = (d.front_qkv ? FW_REST_PATH_FRONT_QKV : 0) | (d.front_ffn ? FW_REST_PATH_FRONT_FFN : 0) | (d.qk_direct ? FW_REST_PATH_QK_DIRECT : 0) |
+             (d.merge_proj ? FW_REST_PATH_MERGE_PROJ : 0) | (d.gemm16 ? FW_REST_PATH_GEMM16 : 0);
+    return FW_OK;
+}
+
+int fw_restormer_run_step(fw_restormer* n, const char* step_c, const float* src_f32, const float* skip_f32, int H, int W, float* dst_f32, void* stream) {
+    if (!n || !step_c || !src_f32 || !dst_f32) return fail(FW_ERR_INVALID, "fw_restormer_run_step: NULL argument");
+    int s = 0;
+    while (s < STEP_COUNT && std::string(step_c) != STEP_NAMES[s]) ++s;
+    if (s == STEP_COUNT) return fail(FW_ERR_INVALID, std::string("fw_restormer_run_step: unknown step '") + step_c + "'");
+    const bool down = s <= STEP_DOWN3_4, up = s >= STEP_UP4_3 && s <= STEP_UP2_1;
+    const int level[STEP_COUNT] = {0, 1, 2, 3, 2, 1, 0};   // of the source
+    if (H < 1 || W < 1 || ((long)H << level[s]) > 16384 || ((long)W << level[s]) > 16384) return fail(FW_ERR_INVALID, "fw_restormer_run_step: bad size");
+    if (down && ((H | W) & 1)) return fail(FW_ERR_INVALID, "fw_restormer_run_step: a down step needs even sides");
+    if (up && !skip_f32) return fail(FW_ERR_INVALID, "fw_restormer_run_step: an up step needs the skip stream");
+    int rc = fw_restormer_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        Arena P;
+        P.plan = true;
+        Sequencer(n, P, nullptr).step(s, nullptr, nullptr, H, W, nullptr);
+        ensure_workspace(n->ws, P.peak);
+        Arena A;
+        A.base = (char*)n->ws.p;
+        Sequencer(n, A, st).step(s, src_f32, skip_f32, H, W, dst_f32);
     });
 }
 

@@ -127,6 +127,78 @@ class RestormerEngine(Engine):
                                                      C.c_void_p(out.ctypes.data), _lib.FW_HOST, None, None))
         return out
 
+    # ---- single steps of a forward on the caller's buffers (tests, tools) ----
+    STEPS = ("down1_2", "down2_3", "down3_4", "up4_3", "up3_2", "up2_1", "output")
+
+    def _block_shape(self, key: str):
+        """(channels, heads) of the block ``key`` names ("encoder_level1.0.", "latent.0."), or None."""
+        for name, n, c, heads in _stages(self.args["dim"], self.args["num_blocks"], self.args["num_refinement_blocks"], self.args["heads"]):
+            if key.startswith(name + ".") and key[len(name) + 1:-1].isdigit() and key.endswith(".") and int(key[len(name) + 1:-1]) < n:
+                return c, heads
+        return None
+
+    @staticmethod
+    def _check_stream(t, what, shape=None):
+        import torch
+        if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{what} expects a contiguous float32 CUDA tensor H x W x channels" + (f" of shape {shape}" if shape else ""))
+
+    @_lib.on_tensor_device
+    def run_block(self, stream_f32, key: str, attn_out=None):
+        """One transformer block (``key`` as in the state dict: "encoder_level1.0.", "latent.0.") in place on a contiguous float32
+        CUDA tensor H x W x pad32(c) whose lanes behind c hold zeros, dispatched as in a forward; ``attn_out`` (float32 CUDA,
+        heads x c/heads x c/heads) receives the softmaxed attention matrix."""
+        import torch
+        self._check_stream(stream_f32, "run_block")
+        shape = self._block_shape(key)
+        if shape is None or int(stream_f32.shape[2]) != _pad(shape[0]):
+            raise ValueError(f"run_block: {key!r} does not name a block of a {int(stream_f32.shape[2])}-lane stream")
+        c, heads = shape
+        if attn_out is not None and (attn_out.dtype != torch.float32 or not attn_out.is_cuda or not attn_out.is_contiguous() or
+                                     attn_out.numel() < c * (c // heads)):
+            raise ValueError("attn_out must be a contiguous float32 CUDA tensor heads x c/heads x c/heads")
+        _lib.check(self._lib.fw_restormer_run_block(self._h, key.encode(), _lib.ptr(stream_f32), int(stream_f32.shape[0]),
+                                                    int(stream_f32.shape[1]), _lib.ptr(attn_out), _lib.stream_ptr(stream_f32.device)))
+        return stream_f32
+
+    def block_paths(self, key: str) -> int:
+        """FW_REST_PATH_* bits of the kernels that block dispatches to."""
+        flags = C.c_int(0)
+        _lib.check(self._lib.fw_restormer_block_paths(self._h, key.encode(), C.byref(flags)))
+        return flags.value
+
+    def step_shapes(self, step: str, h: int, w: int):
+        """(src, skip or None, dst) shapes of ``step`` on a source of h x w pixels."""
+        d = self.args["dim"]
+        if step not in self.STEPS:
+            raise ValueError(f"run_step: unknown step {step!r}")
+        i = self.STEPS.index(step)
+        if i < 3:
+            c = d << i
+            return (h, w, _pad(c)), None, (h // 2, w // 2, _pad(2 * c))
+        if i < 6:
+            c = d << (6 - i)                       # channels of the source: 8d, 4d, 2d
+            return (h, w, _pad(c)), (2 * h, 2 * w, _pad(c // 2)), (2 * h, 2 * w, _pad(c // 2 if i < 5 else c))
+        return (h, w, _pad(2 * d)), None, (h, w, 64)
+
+    @_lib.on_tensor_device
+    def run_step(self, step: str, src_f32, dst_f32, skip_f32=None):
+        """What a forward runs between two stages (``STEPS``; shapes: ``step_shapes``) from src into dst, contiguous float32 CUDA
+        tensors; the up steps also take the encoder's skip stream."""
+        h, w = int(src_f32.shape[0]), int(src_f32.shape[1])
+        src, skip, dst = self.step_shapes(step, h, w)
+        if skip is None and step != "output" and (h | w) & 1:
+            raise ValueError("run_step: a down step needs even sides")
+        self._check_stream(src_f32, "run_step", src)
+        self._check_stream(dst_f32, "run_step", dst)
+        if (skip is None) != (skip_f32 is None):
+            raise ValueError(f"run_step: {step} {'needs' if skip else 'takes no'} skip stream")
+        if skip is not None:
+            self._check_stream(skip_f32, "run_step", skip)
+        _lib.check(self._lib.fw_restormer_run_step(self._h, step.encode(), _lib.ptr(src_f32), _lib.ptr(skip_f32), h, w, _lib.ptr(dst_f32),
+                                                   _lib.stream_ptr(src_f32.device)))
+        return dst_f32
+
     def close(self) -> None:
         super().close()
         self._state = None
