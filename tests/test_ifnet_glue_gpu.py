@@ -352,6 +352,78 @@ def test_sigmoid_of_the_blend(hip_lib):
 
 
 # ---- bad arguments of the two new entries ----------------------------------------------------------------------------------------
+def test_entries_share_the_engine_launchers_6x10(hip_lib):
+    """Every glue entry that has a launcher twin in the engine (csrc/ifnet_ops.hip: the fw_* entry checks its arguments and calls the
+    launch_* that csrc/ifnet.hip sequences), on a 6 x 10 frame padded to 8 x 16: one block, a partial one.  The engine exposes no
+    intermediate tensor, so each entry is held to its kernel's float64 reference and bound of tests/ifnet_glue_ref.py, exact where the
+    kernel is a copy; at s = 1 the two accumulate forms must agree bit for bit, as in test_accumulate_and_accumulate_d2s."""
+    H, W, Hp, Wp = 6, 10, 8, 16
+    rng = np.random.default_rng(610)
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    d_img, rgb = dev(img), Out((Hp, Wp, 3), np.float32)
+    _lib.check(hip_lib.fw_u8_to_rgb_f32(P(d_img), H, W, Hp, Wp, rgb.ptr(), None))
+    got = rgb.take()
+    ref, bound = G.u8_to_rgb(img, Hp, Wp)
+    assert (got[H:] == 0).all() and (got[:, W:] == 0).all()
+    _ratio("6x10 u8_to_rgb", got[:H, :W], ref[:H, :W], bound[:H, :W] + G.TINY)
+
+    i0, i1 = G.make_images("noise", Hp, Wp, rng)
+    flow, mask = G.make_flow("rand6", Hp, Wp, rng), G.make_mask(Hp, Wp, rng)
+    d0, d1, df, dm = dev(i0), dev(i1), dev(flow), dev(mask)
+    X = Out((Hp, Wp, 8), np.float32)
+    _lib.check(hip_lib.fw_ifnet_build_x(P(d0), P(d1), P(df), P(dm), Hp, Wp, 0.5, X.ptr(), None))
+    x = X.take()
+    ref, bound = G.build_x(i0, i1, flow, mask, 0.5)
+    assert np.array_equal(x.reshape(-1, 8)[:, 6:].astype(np.float64), ref[:, 6:])
+    _ratio("6x10 build_x", x.reshape(-1, 8)[:, :6], ref[:, :6], bound[:, :6])
+
+    half = Out((Hp // 2, Wp // 2, 8), np.float32)
+    _lib.check(hip_lib.fw_resize_bilinear_f32(P(df), Hp, Wp, 4, half.ptr(), Hp // 2, Wp // 2, 8, 2, 0.5, 0.5, None))
+    h = half.take()
+    assert half.is_sentinel(h[..., :2]).all() and half.is_sentinel(h[..., 6:]).all()
+    ref, bound = G.resize_bilinear(flow, 0.5, 0.5)
+    _ratio("6x10 resize", h[..., 2:6].reshape(-1, 4), ref, bound)
+
+    for dtype in ("f16", "bf16"):
+        bits = G.to_bits(x, dtype).reshape(Hp, Wp, 8)
+        for typed, src in ((True, dev(bits.view(np.int16))), (False, dev(x))):
+            us = Out((Hp // 2, Wp // 2, 32), np.uint16)
+            _lib.check(hip_lib.fw_unshuffle2_cast(DT[dtype], P(src), 0 if typed else 1, Hp, Wp, 8, 8, us.ptr(), 32, None))
+            assert np.array_equal(us.take(), G.unshuffle2(bits, 8, 32))
+        for s_ in (1, 2):
+            si = Out((Hp // s_ // 2, Wp // s_ // 2, 64), np.uint16)
+            _lib.check(hip_lib.fw_ifnet_stage_input(DT[dtype], P(d0), P(d1), P(df), P(dm), Hp, Wp, 0.5, s_, si.ptr(), 64, None))
+            sb = si.take()
+            assert (sb[..., 48:] == 0).all()
+            ref, bound = G.stage_input(i0, i1, flow, mask, 0.5, s_, 64)
+            _ratio(f"6x10 stage_input s={s_} {dtype}", G.from_bits(sb.reshape(-1, 64), dtype)[:, :48], ref[:, :48],
+                   G.typed_allowance(ref, bound, dtype)[:, :48])
+
+    src96 = (rng.standard_normal((Hp // 4, Wp // 4, 96)) * 3).astype(np.float32)
+    tmp = G.depth_to_space4(src96)
+    d_src, tmp_d = dev(src96), Out((Hp, Wp, 6), np.float32)
+    _lib.check(hip_lib.fw_depth_to_space4_f32(P(d_src), Hp // 4, Wp // 4, 96, tmp_d.ptr(), None))
+    assert np.array_equal(tmp_d.take(), tmp)
+    rf, bf, rm, bm = G.accumulate(tmp, Hp, Wp, 1.0, flow, mask, False)
+    fa, ma = Out((Hp, Wp, 4), np.float32, flow), Out((Hp, Wp), np.float32, mask)
+    _lib.check(hip_lib.fw_ifnet_accumulate(tmp_d.ptr(), Hp, Wp, Hp, Wp, 1.0, fa.ptr(), ma.ptr(), 0, None))
+    d_t96 = dev(G.tmp_to_t96(tmp, cs=98, fill=np.float32(np.nan)))
+    fb, mb = Out((Hp, Wp, 4), np.float32, flow), Out((Hp, Wp), np.float32, mask)
+    _lib.check(hip_lib.fw_ifnet_accumulate_d2s(P(d_t96), Hp // 4, Wp // 4, 98, Hp, Wp, 1.0, fb.ptr(), mb.ptr(), 0, None))
+    ga, gma, gb, gmb = fa.take(), ma.take(), fb.take(), mb.take()
+    _ratio("6x10 accumulate flow", ga.reshape(-1, 4), rf, bf)
+    _ratio("6x10 accumulate mask", gma.reshape(-1), rm, bm)
+    assert np.array_equal(ga, gb) and np.array_equal(gma, gmb)
+
+    u8, out_rgb = Out((H, W, 3), np.uint8), Out((H, W, 3), np.float32)
+    _lib.check(hip_lib.fw_ifnet_blend(P(d0), P(d1), P(df), P(dm), Hp, Wp, H, W, u8.ptr(), out_rgb.ptr(), None))
+    ref, bound = G.blend(i0, i1, flow, mask, H, W)
+    _ratio("6x10 blend", out_rgb.take().reshape(-1, 3), ref, bound)
+    lo, hi, _ = G.u8_window(ref, bound)
+    g8 = u8.take().reshape(-1, 3)[:, ::-1].astype(np.int64)
+    assert ((g8 >= lo) & (g8 <= hi)).all()
+
+
 def test_stage_input_and_accumulate_d2s_reject_bad_arguments(hip_lib):
     H, W = 64, 96
     z = lambda *s: torch.zeros(s, device="cuda")

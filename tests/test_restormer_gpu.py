@@ -41,6 +41,19 @@ def test_layernorm(hip_lib, dtype, C_, ld):
     assert (got[:, C_:] == 0).all()
 
 
+def test_op_entries_refuse_bad_arguments(hip_lib):
+    """One refusal each of the two op entries whose message no other test reads: the status and the whole message, as the library gave
+    them before csrc/restormer_ops.hip took its status mapping from csrc/fw_status.h.  Nothing is launched."""
+    x, w, out = torch.zeros(8, 64, device="cuda"), torch.ones(64, device="cuda"), torch.zeros(8, 64, dtype=torch.float16, device="cuda")
+    F16 = _lib.DTYPES["f16"]
+    assert hip_lib.fw_layernorm_nhwc(F16, P(x), 32, 8, 48, P(w), None, 1e-5, P(out), 64, 64, None) == _lib.FW_ERR_INVALID     # C > ldx
+    assert hip_lib.fw_last_error() == b"fw_layernorm_nhwc: bad argument"
+    xt = torch.zeros(4, 4, 16, dtype=torch.float16, device="cuda")
+    wd = torch.ones(12, 9, device="cuda")
+    assert hip_lib.fw_dwconv3x3_nhwc(F16, P(xt), 16, 4, 4, 12, P(wd), 0, P(out), 16, None) == _lib.FW_ERR_INVALID           # channels % 8
+    assert hip_lib.fw_last_error() == b"fw_dwconv3x3_nhwc: bad argument"
+
+
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 @pytest.mark.parametrize("mode,Cc", [(0, 192), (1, 256), (0, 576), (0, 1152), (1, 1024), (1, 2048)])   # from 512 output channels: the channel-range kernel
 def test_dwconv3x3(hip_lib, dtype, mode, Cc):

@@ -2,8 +2,10 @@
 """Compare the gfx950 device code of csrc/*.hip files between two source trees, on the CPU.
 
 Every file is compiled on each side with build.py's flags plus --cuda-device-only -S and any -D given here; the lines that
-hold a __hip_cuid symbol (a hash of the compile's inputs) are dropped and the two texts compared whole.  Per file: `equal` or
-`differs`, and for every kernel symbol of each side the numbers the assembler writes into the code object's metadata.
+hold a __hip_cuid symbol (a hash of the compile's inputs) are dropped and the two texts compared whole.  Per file: `equal`,
+`reordered` (the same kernels with the same instructions, emitted in another order: host code decides the order in which
+templates are instantiated) or `differs`, and for every kernel symbol of each side the numbers the assembler writes into the
+code object's metadata.
 
     tools/kernel_text_diff.py                        # HEAD against the working tree, the files that include conv_common.h
     tools/kernel_text_diff.py -DFW_PAIR_STAMP conv3x3_pair.hip conv3x3_pair_slide.hip
@@ -68,6 +70,15 @@ def kernels(text: str) -> dict[str, dict[str, int]]:
     return res
 
 
+def bodies(text: str) -> dict[str, str]:
+    """Every function's instructions by symbol, its labels freed of the function's position in the file."""
+    res = {}
+    for m in re.finditer(r"^(\S+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.M | re.S):
+        body = re.sub(r"(BB|func_begin|func_end|tmp)\d+", r"\1", m.group(2))   # labels, and the comments that quote them
+        res[m.group(1)] = re.sub(r"[ \t]+;", " ;", body)
+    return res
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--a", default="HEAD", help="first side: directory or git revision (default HEAD)")
@@ -94,8 +105,8 @@ def main() -> int:
         elif ta is None or tb is None:
             verdict = "compiles on one side only: " + ("b" if ta is None else "a")
         else:
-            verdict = "equal" if ta == tb else "differs"
-        bad += verdict not in ("equal", "compiles on neither side")
+            verdict = "equal" if ta == tb else ("reordered" if bodies(ta) == bodies(tb) and kernels(ta) == kernels(tb) else "differs")
+        bad += verdict not in ("equal", "reordered", "compiles on neither side")
         if args.keep:
             Path(args.keep).mkdir(parents=True, exist_ok=True)
             for side, text in (("a", ta), ("b", tb)):

@@ -504,19 +504,9 @@ size_t f32_native_elems(int H, int W, int cout_tiles) {
 const void* conv_zero_page() { return zero_page(); }
 
 static int num_cus() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        // FW_CONV_GRID: persistent workgroups per launch (default one per CU); half of them lets two frames run side by side on
-        // two streams, each kernel on its own half of the CUs
-        if (const char* e = getenv("FW_CONV_GRID")) {
-            const int g = atoi(e);
-            if (g > 0 && g < v) v = g;
-        }
-        return v;
-    }();
+    // FW_CONV_GRID: persistent workgroups per launch (default one per CU); half of them lets two frames run side by side on
+    // two streams, each kernel on its own half of the CUs
+    static int n = device_cus("FW_CONV_GRID");
     return n;
 }
 

@@ -1,7 +1,8 @@
 // Host-side scaffolding shared by the six network sequencers (rrdbnet, nafnet, ifnet, restormer, srvgg, aesrgan .hip): device
 // buffers, the workspace and the hipGraph cache.  The lifetime and ordering rules of the library's host layer live here, once.
 // The status / last-error mapping of the C-ABI (fail, guarded) is fw_status.h, which the frame-stage files share through
-// stage_common.h.  No device code.
+// stage_common.h and the op files (restormer_ops, ifnet_ops .hip) include directly.  nafnet.hip holds fw_nafnet_* only: the C
+// entries of the frame ops (crop, tile blend, temporal average, resizes, ...) sit with their launchers in frame_ops.hip.  No device code.
 #pragma once
 #include <array>
 #include <string>

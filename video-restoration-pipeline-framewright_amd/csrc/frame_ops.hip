@@ -7,9 +7,9 @@
 // (basicsr RRDBNet.forward).
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
-#include "fw_internal.h"
-#include "stage_common.h"   // gray_bgr, reflect101
+#include "stage_common.h"   // gray_bgr, reflect101; fw_status.h
 #include "flow_accumulate.h"
 
 // The blend kernels below restate float32 numpy arithmetic bit for bit: a*b+c must round twice, so this translation
@@ -89,20 +89,18 @@ void launch_frame_to_nhwc(DType dt, const void* in_bgr, int bits, int H, int W, 
     const int Wo = unshuffle == 2 ? (W + 1) / 2 : W;
     if (unshuffle == 2 && (H < 2 || W < 2)) throw Error(1, "u8_to_nhwc: x2 model needs at least 2x2 input");
     const long n = (long)Ho * Wo;
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const int blocks = grid_1d(n, 2048);
     dim3 grid(blocks), block(256);
-#define FW_LAUNCH(T, U, IN) \
+#define FW_LAUNCH(U, IN) \
     hipLaunchKernelGGL((u8_to_nhwc_kernel<T, U, IN>), grid, block, 0, stream, (const IN*)in_bgr, H, W, (T*)out, out_cstride, Ho, Wo)
-#define FW_LAUNCH_T(T)                                                            \
-    do {                                                                          \
-        if (bits == 8) {                                                          \
-            if (unshuffle == 2) FW_LAUNCH(T, 2, uint8_t); else FW_LAUNCH(T, 1, uint8_t);    \
-        } else {                                                                  \
-            if (unshuffle == 2) FW_LAUNCH(T, 2, uint16_t); else FW_LAUNCH(T, 1, uint16_t);  \
-        }                                                                         \
-    } while (0)
-    if (dt == DT_BF16) FW_LAUNCH_T(__bf16); else FW_LAUNCH_T(_Float16);
-#undef FW_LAUNCH_T
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (bits == 8) {
+            if (unshuffle == 2) FW_LAUNCH(2, uint8_t); else FW_LAUNCH(1, uint8_t);
+        } else {
+            if (unshuffle == 2) FW_LAUNCH(2, uint16_t); else FW_LAUNCH(1, uint16_t);
+        }
+    });
 #undef FW_LAUNCH
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -145,14 +143,14 @@ __global__ __launch_bounds__(256) void flow_accumulate_finish_kernel(const doubl
 void launch_flow_accumulate(const uint8_t* frame, const float* fx, const float* fy, const float* wmap, double wscale,
                             const float* mag, float thr, int inverse, int H, int W, double* acc, double* wsum, hipStream_t st) {
     const long n = (long)H * W;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = grid_1d(n, 4096);
     hipLaunchKernelGGL(flow_accumulate_kernel, dim3(blocks), dim3(256), 0, st, frame, fx, fy, wmap, wscale, mag, thr, inverse, H, W,
                        acc, wsum);
     FW_HIP_CHECK(hipGetLastError());
 }
 
 void launch_flow_accumulate_finish(const double* acc, const double* wsum, long n, uint8_t* out, hipStream_t st) {
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = grid_1d(n, 4096);
     hipLaunchKernelGGL(flow_accumulate_finish_kernel, dim3(blocks), dim3(256), 0, st, acc, wsum, n, out);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -192,7 +190,7 @@ void launch_pixel_shuffle_add_bits(const float* conv, int cstride, const void* i
     if (scale < 1 || scale > 4 || cstride < 3 * scale * scale) throw Error(1, "pixel_shuffle_add: bad scale / channel stride");
     if (bits != 8 && bits != 16) throw Error(1, "pixel_shuffle_add: 8- or 16-bit samples expected");
     const long n = (long)H * scale * W * scale;
-    const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    const int blocks = grid_1d(n, 8192);
     if (bits == 8)
         hipLaunchKernelGGL((pixel_shuffle_add_kernel<uint8_t>), dim3(blocks), dim3(256), 0, st, conv, cstride, (const uint8_t*)in_bgr, H, W, scale,
                            (uint8_t*)out_bgr, out_rgb);
@@ -220,11 +218,11 @@ __global__ __launch_bounds__(256) void rgb_f32_to_nhwc_kernel(const float* __res
     }
 }
 void launch_rgb_f32_to_nhwc(DType dt, const float* x, long M, void* out, hipStream_t st) {
-    const int blocks = (int)((M + 255) / 256 < 2048 ? (M + 255) / 256 : 2048);
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((rgb_f32_to_nhwc_kernel<__bf16>), dim3(blocks), dim3(256), 0, st, x, M, (__bf16*)out);
-    else
-        hipLaunchKernelGGL((rgb_f32_to_nhwc_kernel<_Float16>), dim3(blocks), dim3(256), 0, st, x, M, (_Float16*)out);
+    const int blocks = grid_1d(M, 2048);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((rgb_f32_to_nhwc_kernel<T>), dim3(blocks), dim3(256), 0, st, x, M, (T*)out);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 __global__ __launch_bounds__(256) void take_rgb_f32_kernel(const float* __restrict__ src, int cstride, long M, float* out) {
@@ -235,7 +233,7 @@ __global__ __launch_bounds__(256) void take_rgb_f32_kernel(const float* __restri
 }
 void launch_take_rgb_f32(const float* src, int cstride, long M, float* out, hipStream_t st) {
     const long n = M * 3;
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = grid_1d(n, 4096);
     hipLaunchKernelGGL(take_rgb_f32_kernel, dim3(blocks), dim3(256), 0, st, src, cstride, M, out);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -266,12 +264,11 @@ __global__ __launch_bounds__(256) void u8_to_nhwc_padded_kernel(const uint8_t* _
 
 void launch_u8_to_nhwc_padded(DType dt, const uint8_t* in_bgr, int H, int W, int Hp, int Wp, void* out, hipStream_t st) {
     const long n = (long)Hp * Wp;
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((u8_to_nhwc_padded_kernel<__bf16>), dim3(blocks), dim3(256), 0, st, in_bgr, H, W, Hp, Wp, (__bf16*)out);
-    else
-        hipLaunchKernelGGL((u8_to_nhwc_padded_kernel<_Float16>), dim3(blocks), dim3(256), 0, st, in_bgr, H, W, Hp, Wp,
-                           (_Float16*)out);
+    const int blocks = grid_1d(n, 2048);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((u8_to_nhwc_padded_kernel<T>), dim3(blocks), dim3(256), 0, st, in_bgr, H, W, Hp, Wp, (T*)out);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 
@@ -301,7 +298,7 @@ __global__ __launch_bounds__(256) void tap_post_kernel(const uint8_t* __restrict
 void launch_tap_post(const uint8_t* in_bgr, const float* rgb, int H, int W, int Wp, int cs, uint8_t* out_bgr, float* out_rgb,
                      hipStream_t st) {
     const long n = (long)H * W;
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const int blocks = grid_1d(n, 2048);
     hipLaunchKernelGGL(tap_post_kernel, dim3(blocks), dim3(256), 0, st, in_bgr, rgb, H, W, Wp, cs, out_bgr, out_rgb);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -318,7 +315,7 @@ __global__ __launch_bounds__(256) void u8_crop_kernel(const uint8_t* __restrict_
 
 void launch_u8_crop(const uint8_t* src, int W, int y0, int x0, int th, int tw, uint8_t* dst, hipStream_t st) {
     const long n = (long)th * tw * 3;
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const int blocks = grid_1d(n, 2048);
     hipLaunchKernelGGL(u8_crop_kernel, dim3(blocks), dim3(256), 0, st, src, W, y0, x0, th, tw, dst);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -354,7 +351,7 @@ __global__ __launch_bounds__(256) void tile_blend_acc_kernel(float* acc, float* 
 void launch_tile_blend_acc(float* acc, float* wsum, int W, const uint8_t* tile, int y0, int x0, int th, int tw, int ov,
                            int top, int bottom, int left, int right, hipStream_t st) {
     const long n = (long)th * tw;
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const int blocks = grid_1d(n, 2048);
     hipLaunchKernelGGL(tile_blend_acc_kernel, dim3(blocks), dim3(256), 0, st, acc, wsum, W, tile, y0, x0, th, tw, ov, top,
                        bottom, left, right);
     FW_HIP_CHECK(hipGetLastError());
@@ -371,7 +368,7 @@ __global__ __launch_bounds__(256) void tile_blend_finish_kernel(const float* __r
 }
 
 void launch_tile_blend_finish(const float* acc, const float* wsum, long npix, uint8_t* out, hipStream_t st) {
-    const int blocks = (int)((npix + 255) / 256 < 2048 ? (npix + 255) / 256 : 2048);
+    const int blocks = grid_1d(npix, 2048);
     hipLaunchKernelGGL(tile_blend_finish_kernel, dim3(blocks), dim3(256), 0, st, acc, wsum, npix, out);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -401,7 +398,7 @@ void launch_temporal_average(const uint8_t* const* frames, const float* weights,
         a.frames[k] = frames[k];
         a.weights[k] = weights[k];
     }
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = grid_1d(n, 4096);
     hipLaunchKernelGGL(temporal_average_kernel, dim3(blocks), dim3(256), 0, st, a, n, out);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -415,7 +412,7 @@ __global__ __launch_bounds__(256) void strength_blend_kernel(const uint8_t* __re
 
 void launch_strength_blend(const uint8_t* orig, const uint8_t* den, float one_minus_s, float s, long n, uint8_t* out,
                            hipStream_t st) {
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = grid_1d(n, 4096);
     hipLaunchKernelGGL(strength_blend_kernel, dim3(blocks), dim3(256), 0, st, orig, den, one_minus_s, s, n, out);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -484,7 +481,10 @@ static void lanczos4_coeffs(float x, float* coeffs) {
     for (int i = 0; i < 8; i++) coeffs[i] *= sum;
 }
 
-static void lanczos4_tables(int ssize, int dsize, std::vector<int>& ofs, std::vector<short>& coef) {
+// per destination sample: the first source sample's offset and the 8 weights - OpenCV's fixed-point shorts (8-bit images) or the
+// normalised floats themselves (16-bit images)
+template <typename CT>
+static void lanczos4_tables(int ssize, int dsize, std::vector<int>& ofs, std::vector<CT>& coef) {
     const double inv_scale = (double)dsize / ssize, scale = 1. / inv_scale;
     ofs.resize(dsize);
     coef.resize((size_t)dsize * 8);
@@ -496,12 +496,42 @@ static void lanczos4_tables(int ssize, int dsize, std::vector<int>& ofs, std::ve
         float cbuf[8];
         lanczos4_coeffs(f, cbuf);
         for (int k = 0; k < 8; ++k) {
-            // saturate_cast<short>(float): round to nearest even, clamp
-            const float v = cbuf[k] * 2048.f;
-            long r = std::lrintf(v);
-            coef[(size_t)d * 8 + k] = (short)(r < -32768 ? -32768 : (r > 32767 ? 32767 : r));
+            if constexpr (std::is_same<CT, float>::value) {
+                coef[(size_t)d * 8 + k] = cbuf[k];
+            } else {
+                // saturate_cast<short>(float): round to nearest even, clamp
+                const float v = cbuf[k] * 2048.f;
+                long r = std::lrintf(v);
+                coef[(size_t)d * 8 + k] = (short)(r < -32768 ? -32768 : (r > 32767 ? 32767 : r));
+            }
         }
     }
+}
+
+// The tables of a separable resize on the device for one launch, as one block [xofs | yofs | x weights | y weights]:
+// launch(xofs, x weights, yofs, y weights) gets the four device pointers.  The tables live in pageable host memory and a per-call
+// device block, so the stream is synchronised before both go away (the once-per-frame tail of a non-default configuration and a
+// face region per call, not the hot path).  A failed copy or launch is raised before a failed synchronise.
+template <typename CT, typename Launch>
+static void with_resize_tables(const std::vector<int>& xofs, const std::vector<int>& yofs, const std::vector<CT>& wx, const std::vector<CT>& wy,
+                               hipStream_t st, Launch&& launch) {
+    const size_t xb = xofs.size() * sizeof(int), ob = xb + yofs.size() * sizeof(int), ab = wx.size() * sizeof(CT), bytes = ob + ab + wy.size() * sizeof(CT);
+    char* d = nullptr;
+    FW_HIP_CHECK(hipMalloc((void**)&d, bytes));
+    std::vector<char> h(bytes);
+    memcpy(h.data(), xofs.data(), xb);
+    memcpy(h.data() + xb, yofs.data(), ob - xb);
+    memcpy(h.data() + ob, wx.data(), ab);
+    memcpy(h.data() + ob + ab, wy.data(), bytes - ob - ab);
+    hipError_t e = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        launch(reinterpret_cast<const int*>(d), reinterpret_cast<const CT*>(d + ob), reinterpret_cast<const int*>(d + xb), reinterpret_cast<const CT*>(d + ob + ab));
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    FW_HIP_CHECK(e);
+    FW_HIP_CHECK(e2);
 }
 
 void launch_resize_lanczos4_u8(const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst, int Hd, int Wd, hipStream_t st) {
@@ -509,31 +539,9 @@ void launch_resize_lanczos4_u8(const uint8_t* src, int Hs, int Ws, int C, uint8_
     std::vector<short> ia, ib;
     lanczos4_tables(Ws, Wd, xofs, ia);
     lanczos4_tables(Hs, Hd, yofs, ib);
-    const size_t nx = (size_t)Wd, ny = (size_t)Hd;
-    // one device block: [xofs | yofs | ialpha | ibeta]
-    const size_t bytes = (nx + ny) * 4 + (nx + ny) * 16;
-    char* d = nullptr;
-    FW_HIP_CHECK(hipMalloc((void**)&d, bytes));
-    std::vector<char> h(bytes);
-    memcpy(h.data(), xofs.data(), nx * 4);
-    memcpy(h.data() + nx * 4, yofs.data(), ny * 4);
-    memcpy(h.data() + (nx + ny) * 4, ia.data(), nx * 16);
-    memcpy(h.data() + (nx + ny) * 4 + nx * 16, ib.data(), ny * 16);
-    hipError_t e = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const long total = (long)Hd * Wd;
-        const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-        hipLaunchKernelGGL(resize_lanczos4_u8_kernel, dim3(blocks), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd,
-                           reinterpret_cast<const int*>(d), reinterpret_cast<const short*>(d + (nx + ny) * 4),
-                           reinterpret_cast<const int*>(d + nx * 4), reinterpret_cast<const short*>(d + (nx + ny) * 4 + nx * 16));
-        e = hipGetLastError();
-    }
-    // the tables live in pageable host memory and a per-call device block: finish before both go away (this is the
-    // once-per-frame tail of a non-default configuration, not the hot path)
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    FW_HIP_CHECK(e);
-    FW_HIP_CHECK(e2);
+    with_resize_tables(xofs, yofs, ia, ib, st, [&](const int* dxofs, const short* dia, const int* dyofs, const short* dib) {
+        hipLaunchKernelGGL(resize_lanczos4_u8_kernel, dim3(grid_1d((long)Hd * Wd, 65535)), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd, dxofs, dia, dyofs, dib);
+    });
 }
 
 // The same resize on 16-bit images (RealESRGANer.enhance with outscale != netscale on a 16-bit frame).  OpenCV's path for ushort is
@@ -578,44 +586,13 @@ __global__ __launch_bounds__(256) void resize_lanczos4_u16_kernel(const uint16_t
 }
 
 void launch_resize_lanczos4_u16(const uint16_t* src, int Hs, int Ws, int C, uint16_t* dst, int Hd, int Wd, hipStream_t st) {
-    auto tables = [](int ssize, int dsize, std::vector<int>& ofs, std::vector<float>& coef) {
-        const double inv_scale = (double)dsize / ssize, scale = 1. / inv_scale;
-        ofs.resize(dsize);
-        coef.resize((size_t)dsize * 8);
-        for (int d = 0; d < dsize; ++d) {
-            float f = (float)((d + 0.5) * scale - 0.5);
-            const int s0 = (int)std::floor(f);
-            f -= s0;
-            ofs[d] = s0;
-            lanczos4_coeffs(f, coef.data() + (size_t)d * 8);
-        }
-    };
     std::vector<int> xofs, yofs;
     std::vector<float> fa, fb;
-    tables(Ws, Wd, xofs, fa);
-    tables(Hs, Hd, yofs, fb);
-    const size_t nx = (size_t)Wd, ny = (size_t)Hd;
-    const size_t bytes = (nx + ny) * 4 + (nx + ny) * 32;   // [xofs | yofs | alpha | beta]
-    char* d = nullptr;
-    FW_HIP_CHECK(hipMalloc((void**)&d, bytes));
-    std::vector<char> h(bytes);
-    memcpy(h.data(), xofs.data(), nx * 4);
-    memcpy(h.data() + nx * 4, yofs.data(), ny * 4);
-    memcpy(h.data() + (nx + ny) * 4, fa.data(), nx * 32);
-    memcpy(h.data() + (nx + ny) * 4 + nx * 32, fb.data(), ny * 32);
-    hipError_t e = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const long total = (long)Hd * Wd;
-        const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-        hipLaunchKernelGGL(resize_lanczos4_u16_kernel, dim3(blocks), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd,
-                           reinterpret_cast<const int*>(d), reinterpret_cast<const float*>(d + (nx + ny) * 4),
-                           reinterpret_cast<const int*>(d + nx * 4), reinterpret_cast<const float*>(d + (nx + ny) * 4 + nx * 32));
-        e = hipGetLastError();
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);   // tables in pageable host memory and a per-call device block (as for 8-bit)
-    (void)hipFree(d);
-    FW_HIP_CHECK(e);
-    FW_HIP_CHECK(e2);
+    lanczos4_tables(Ws, Wd, xofs, fa);
+    lanczos4_tables(Hs, Hd, yofs, fb);
+    with_resize_tables(xofs, yofs, fa, fb, st, [&](const int* dxofs, const float* dfa, const int* dyofs, const float* dfb) {
+        hipLaunchKernelGGL(resize_lanczos4_u16_kernel, dim3(grid_1d((long)Hd * Wd, 65535)), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd, dxofs, dfa, dyofs, dfb);
+    });
 }
 
 // ---- cv2.resize(img, (w, h)) with the default interpolation (INTER_LINEAR) on 8-bit images ------------------------------------
@@ -675,7 +652,7 @@ static void linear_tables(int ssize, int dsize, std::vector<int>& ofs, std::vect
 
 void launch_resize_linear_u8(const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst, int Hd, int Wd, hipStream_t st) {
     const long total = (long)Hd * Wd;
-    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    const int blocks = grid_1d(total, 65535);
     if (Hs == Hd && Ws == Wd) {
         FW_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)total * C, hipMemcpyDeviceToDevice, st));
         return;
@@ -689,27 +666,9 @@ void launch_resize_linear_u8(const uint8_t* src, int Hs, int Ws, int C, uint8_t*
     std::vector<short> ia, ib;
     linear_tables(Ws, Wd, xofs, ia);
     linear_tables(Hs, Hd, yofs, ib);
-    const size_t nx = (size_t)Wd, ny = (size_t)Hd;
-    const size_t bytes = (nx + ny) * 4 + (nx + ny) * 4;   // [xofs | yofs | ialpha | ibeta]
-    char* d = nullptr;
-    FW_HIP_CHECK(hipMalloc((void**)&d, bytes));
-    std::vector<char> h(bytes);
-    memcpy(h.data(), xofs.data(), nx * 4);
-    memcpy(h.data() + nx * 4, yofs.data(), ny * 4);
-    memcpy(h.data() + (nx + ny) * 4, ia.data(), nx * 4);
-    memcpy(h.data() + (nx + ny) * 4 + nx * 4, ib.data(), ny * 4);
-    hipError_t e = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(resize_linear_u8_kernel, dim3(blocks), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd, reinterpret_cast<const int*>(d),
-                           reinterpret_cast<const short*>(d + (nx + ny) * 4), reinterpret_cast<const int*>(d + nx * 4),
-                           reinterpret_cast<const short*>(d + (nx + ny) * 4 + nx * 4));
-        e = hipGetLastError();
-    }
-    // the tables live in pageable host memory and a per-call device block: finish before both go away (a face region per call)
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    FW_HIP_CHECK(e);
-    FW_HIP_CHECK(e2);
+    with_resize_tables(xofs, yofs, ia, ib, st, [&](const int* dxofs, const short* dia, const int* dyofs, const short* dib) {
+        hipLaunchKernelGGL(resize_linear_u8_kernel, dim3(blocks), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd, dxofs, dia, dyofs, dib);
+    });
 }
 
 // ---- the blend of `_paste_face_back` (aesrgan_face.py:556-584), float32 statement for statement -----------------------------------
@@ -745,7 +704,7 @@ void launch_face_paste_u8(uint8_t* frame, int H, int W, int x1, int y1, int x2, 
     if (rw <= 0 || rh <= 0 || x1 < 0 || y1 < 0 || x2 > W || y2 > H) throw Error(1, "face_paste: region outside the frame");
     const int feather = (rw < rh ? rw : rh) / 8;
     const long total = (long)rw * rh;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = grid_1d(total, 4096);
     hipLaunchKernelGGL(face_paste_u8_kernel, dim3(blocks), dim3(256), 0, st, frame, W, x1, y1, rw, rh, enh, strength, feather);
     FW_HIP_CHECK(hipGetLastError());
 }
@@ -824,7 +783,7 @@ void launch_grain_addback(const uint8_t* orig, const uint8_t* den, int H, int W,
                           hipStream_t st) {
     static const GrainKernel gk = grain_kernel19();
     const long n = (long)H * W;
-    const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    const int blocks = grid_1d(n, 8192);
     hipLaunchKernelGGL(grain_hblur_kernel, dim3(blocks), dim3(256), 0, st, orig, H, W, tmp, gk);
     hipLaunchKernelGGL(grain_add_kernel, dim3(blocks), dim3(256), 0, st, orig, tmp, den, H, W, factor, out, gk);
     FW_HIP_CHECK(hipGetLastError());
@@ -994,8 +953,6 @@ struct EdgeScratch {
     }
 };
 
-static int pixel_blocks(size_t n) { return (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); }
-
 // The edge map: Sobel, non-maximum suppression and the hysteresis to its fixed point.  2 marks an edge pixel.
 const uint8_t* launch_canny_edge_map(const uint8_t* bgr, int H, int W, int lo, int hi, void* scratch, hipStream_t st) {
     const size_t n = (size_t)H * W;
@@ -1003,7 +960,7 @@ const uint8_t* launch_canny_edge_map(const uint8_t* bgr, int H, int W, int lo, i
     short *dxy = e.dxy, *mag = e.mag;
     uint8_t* map = e.map;
     int* changed = e.changed;
-    const int blocks = pixel_blocks(n);
+    const int blocks = grid_1d((long)n, 8192);
     hipLaunchKernelGGL(pe_sobel_kernel, dim3(blocks), dim3(256), 0, st, bgr, H, W, dxy, mag);
     hipLaunchKernelGGL(pe_nms_kernel, dim3(blocks), dim3(256), 0, st, dxy, mag, H, W, lo, hi, map);
     const int tiles = ((W + 31) / 32) * ((H + 31) / 32);
@@ -1029,10 +986,114 @@ void launch_preserve_edges(const uint8_t* orig, const uint8_t* den, int H, int W
     const size_t n = (size_t)H * W;
     const uint8_t* map = launch_canny_edge_map(orig, H, W, lo, hi, scratch, st);
     float* rows = EdgeScratch(scratch, n).rows;
-    const int blocks = pixel_blocks(n);
+    const int blocks = grid_1d((long)n, 8192);
     hipLaunchKernelGGL(pe_mask_rows_kernel, dim3(blocks), dim3(256), 0, st, map, H, W, rows);
     hipLaunchKernelGGL(pe_blend_kernel, dim3(blocks), dim3(256), 0, st, orig, den, rows, H, W, out);
     FW_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace fw
+
+// ---- the C entries of the frame ops above ---------------------------------------------------------------------------------------
+using namespace fw;
+
+extern "C" {
+
+int fw_u8_to_nhwc_padded(int dtype, const uint8_t* in_bgr, int H, int W, int Hp, int Wp, void* out, void* stream) {
+    if (!in_bgr || !out || H < 1 || W < 1 || Hp < H || Wp < W) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc_padded: bad argument");
+    if (!operand_dtype_ok(dtype)) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc_padded: bad dtype");
+    return guarded([&] { launch_u8_to_nhwc_padded((DType)dtype, in_bgr, H, W, Hp, Wp, out, (hipStream_t)stream); });
+}
+
+// ---- K8: blend kernels of the TAP driver (tap_denoise.py:417-534, :614-618) ---------------------------------------
+int fw_u8_crop(const uint8_t* src, int height, int width, int y0, int x0, int th, int tw, uint8_t* dst, void* stream) {
+    if (!src || !dst || th < 1 || tw < 1 || y0 < 0 || x0 < 0 || y0 + th > height || x0 + tw > width)
+        return fail(FW_ERR_INVALID, "fw_u8_crop: window outside the frame");
+    return guarded([&] { launch_u8_crop(src, width, y0, x0, th, tw, dst, (hipStream_t)stream); });
+}
+
+int fw_tile_blend_accumulate(float* acc, float* wsum, int height, int width, const uint8_t* tile, int y0, int x0, int th,
+                             int tw, int overlap, void* stream) {
+    if (!acc || !wsum || !tile || th < 1 || tw < 1 || y0 < 0 || x0 < 0 || y0 + th > height || x0 + tw > width || overlap < 0 ||
+        overlap > th || overlap > tw)
+        return fail(FW_ERR_INVALID, "fw_tile_blend_accumulate: bad tile geometry");
+    return guarded([&] {
+        launch_tile_blend_acc(acc, wsum, width, tile, y0, x0, th, tw, overlap, y0 > 0, y0 + th < height, x0 > 0,
+                              x0 + tw < width, (hipStream_t)stream);
+    });
+}
+
+int fw_tile_blend_finish(const float* acc, const float* wsum, int height, int width, uint8_t* out, void* stream) {
+    if (!acc || !wsum || !out || height < 1 || width < 1) return fail(FW_ERR_INVALID, "fw_tile_blend_finish: bad argument");
+    return guarded([&] { launch_tile_blend_finish(acc, wsum, (long)height * width, out, (hipStream_t)stream); });
+}
+
+int fw_temporal_average_u8(const uint8_t* const* frames, const float* weights, int count, size_t nbytes, uint8_t* out,
+                           void* stream) {
+    if (!frames || !weights || !out || count < 1 || count > 16) return fail(FW_ERR_INVALID, "fw_temporal_average_u8: bad argument");
+    for (int k = 0; k < count; ++k)
+        if (!frames[k]) return fail(FW_ERR_INVALID, "fw_temporal_average_u8: NULL frame");
+    return guarded([&] { launch_temporal_average(frames, weights, count, (long)nbytes, out, (hipStream_t)stream); });
+}
+
+int fw_strength_blend_u8(const uint8_t* original, const uint8_t* denoised, double strength, size_t nbytes, uint8_t* out,
+                         void* stream) {
+    if (!original || !denoised || !out || !(strength >= 0.0 && strength <= 1.0))
+        return fail(FW_ERR_INVALID, "fw_strength_blend_u8: bad argument");
+    // (1 - s) is formed in double like the reference's Python float arithmetic, then rounded once to float32 (one subtraction, one
+    // conversion: nothing this file's -ffp-contract=off could keep from fusing)
+    const float oms = (float)(1.0 - strength);
+    const float sf = (float)strength;
+    return guarded([&] { launch_strength_blend(original, denoised, oms, sf, (long)nbytes, out, (hipStream_t)stream); });
+}
+
+int fw_grain_addback_u8(const uint8_t* original, const uint8_t* denoised, int height, int width, double factor,
+                        uint16_t* scratch, uint8_t* out, void* stream) {
+    if (!original || !denoised || !scratch || !out || height < 1 || width < 1 || !(factor >= 0.0) || factor > 1.0)
+        return fail(FW_ERR_INVALID, "fw_grain_addback_u8: bad argument");
+    return guarded([&] { launch_grain_addback(original, denoised, height, width, factor, scratch, out, (hipStream_t)stream); });
+}
+
+int fw_resize_lanczos4_u8(const uint8_t* src, int src_h, int src_w, int channels, uint8_t* dst, int dst_h, int dst_w, void* stream) {
+    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
+        return fail(FW_ERR_INVALID, "fw_resize_lanczos4_u8: bad argument");
+    return guarded([&] { launch_resize_lanczos4_u8(src, src_h, src_w, channels, dst, dst_h, dst_w, (hipStream_t)stream); });
+}
+
+int fw_resize_lanczos4_u16(const uint16_t* src, int src_h, int src_w, int channels, uint16_t* dst, int dst_h, int dst_w, void* stream) {
+    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
+        return fail(FW_ERR_INVALID, "fw_resize_lanczos4_u16: bad argument");
+    return guarded([&] { launch_resize_lanczos4_u16(src, src_h, src_w, channels, dst, dst_h, dst_w, (hipStream_t)stream); });
+}
+
+int fw_resize_linear_u8(const uint8_t* src, int src_h, int src_w, int channels, uint8_t* dst, int dst_h, int dst_w, void* stream) {
+    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
+        return fail(FW_ERR_INVALID, "fw_resize_linear_u8: bad argument");
+    return guarded([&] { launch_resize_linear_u8(src, src_h, src_w, channels, dst, dst_h, dst_w, (hipStream_t)stream); });
+}
+
+int fw_face_paste_u8(uint8_t* frame, int height, int width, int x1, int y1, int x2, int y2, const uint8_t* enhanced, double strength,
+                     void* stream) {
+    if (!frame || !enhanced || height < 1 || width < 1 || !(strength >= 0.0) || strength > 1.0)
+        return fail(FW_ERR_INVALID, "fw_face_paste_u8: bad argument");
+    return guarded([&] { launch_face_paste_u8(frame, height, width, x1, y1, x2, y2, enhanced, (float)strength, (hipStream_t)stream); });
+}
+
+size_t fw_preserve_edges_scratch_bytes(int height, int width) {
+    if (height < 1 || width < 1) return 0;
+    return preserve_edges_scratch_bytes(height, width);
+}
+
+int fw_preserve_edges_u8(const uint8_t* original, const uint8_t* denoised, int height, int width, double low_threshold,
+                         double high_threshold, void* scratch, uint8_t* out, void* stream) {
+    if (!original || !denoised || !scratch || !out || height < 1 || width < 1 || !(low_threshold >= 0) || !(high_threshold >= 0))
+        return fail(FW_ERR_INVALID, "fw_preserve_edges_u8: bad argument");
+    return guarded([&] {
+        double lo = low_threshold, hi = high_threshold;
+        if (lo > hi) std::swap(lo, hi);
+        // (floor is a single operation: -ffp-contract=off changes nothing here either)
+        launch_preserve_edges(original, denoised, height, width, (int)floor(lo), (int)floor(hi), scratch, out, (hipStream_t)stream);
+    });
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <stdexcept>
@@ -405,6 +406,39 @@ struct StreamOrder {
         have = false;
     }
 };
+
+// ---- launch-site helpers (host) ---------------------------------------------------------------------------------------------
+// The one bf16 / f16 branch of a launch site: f(OperandTag<__bf16>{}) or f(OperandTag<_Float16>{}), bf16 first so that the
+// kernels are instantiated in the order the two-armed `if` gave them.
+//     with_operand_type(dt, [&](auto tag) { using T = typename decltype(tag)::type;  hipLaunchKernelGGL((k<T>), ...); });
+template <typename T> struct OperandTag { using type = T; };
+// the refusing form, for the C-ABI's `int dtype`: an entry tests it together with its other arguments and keeps its own message
+inline bool operand_dtype_ok(int dtype) { return dtype == DT_BF16 || dtype == DT_F16; }
+template <typename F>
+void with_operand_type(DType dt, F&& f) {   // the throwing form, for launchers
+    if (dt == DT_BF16) f(OperandTag<__bf16>{});
+    else if (dt == DT_F16) f(OperandTag<_Float16>{});
+    else throw Error(1, "unknown operand dtype");
+}
+
+// blocks of 256 threads for n items, at least one and at most cap
+inline int grid_1d(long n, int cap) {
+    const long b = (n + 255) / 256;
+    return (int)(b < cap ? (b > 0 ? b : 1) : cap);
+}
+
+// CUs of the current device (256 where the query fails).  `override_env`, where given, names a variable that lowers the count.
+// Every caller latches its own result in a function-local static.
+inline int device_cus(const char* override_env = nullptr) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+        v = 256;
+    if (const char* e = override_env ? getenv(override_env) : nullptr) {
+        const int g = atoi(e);
+        if (g > 0 && g < v) v = g;
+    }
+    return v;
+}
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // GELU (exact form, 0.5 x (1 + erf(x / sqrt 2))) of two values, erf after Abramowitz & Stegun 7.1.28:

@@ -1,5 +1,6 @@
 // The C-ABI's status and last-error mapping, once: a code for the caller, the message for fw_last_error().  Included by
-// engine_common.h (the six network sequencers) and stage_common.h (the nine frame-stage files); host code only.
+// engine_common.h (the six network sequencers), stage_common.h (the frame-stage files, and frame_ops.hip with the C entries of its
+// frame ops) and the op files restormer_ops.hip and ifnet_ops.hip; host code only.
 #pragma once
 #include <new>
 #include <string>

@@ -5,8 +5,7 @@
 // src/framewright/processors/interpolation.py:628-650); the arithmetic restated here is IFNet_HDv3 v4.6 as recorded in
 // SURVEY.md §A.5 and in oracle/ifnet_ref.py ("parity vs upstream unpinned").  All tensors are fp32 NHWC with a handful
 // of channels (image 3, flow 4, mask 1): HBM-bound byte work, one thread per output pixel, no LDS.
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "fw_status.h"
 
 namespace fw {
 
@@ -347,8 +346,6 @@ __global__ __launch_bounds__(256) void ifnet_blend_kernel(const float* __restric
     }
 }
 
-static int grid_for(long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
-
 }  // namespace fw
 
 
@@ -391,49 +388,44 @@ __global__ void unsharp_finish_u8_kernel(const uint8_t* __restrict__ src, const 
 
 // ---- launchers used by the whole-model engine (ifnet.hip) -------------------------------------------------------------------
 namespace fw {
-static int ifn_grid(long n) { return (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
 void launch_ifnet_u8_to_rgb(const uint8_t* in_bgr, int H, int W, int Hp, int Wp, float* out, hipStream_t st) {
     // (four pixels per thread with 16-byte stores was slower: 14.3 against 10.7 us per 1080p frame)
-    hipLaunchKernelGGL(u8_to_rgb_f32_kernel, dim3(ifn_grid((long)Hp * Wp)), dim3(256), 0, st, in_bgr, H, W, Hp, Wp, out);
+    hipLaunchKernelGGL(u8_to_rgb_f32_kernel, dim3(grid_1d((long)Hp * Wp, 4096)), dim3(256), 0, st, in_bgr, H, W, Hp, Wp, out);
 }
 void launch_resize_bilinear(const float* src, int Hs, int Ws, int C, float* dst, int Hd, int Wd, int dst_cstride, int dst_coff,
                             float scale_factor, float mul, hipStream_t st) {
-    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(ifn_grid((long)Hd * Wd)), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd,
+    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid_1d((long)Hd * Wd, 4096)), dim3(256), 0, st, src, Hs, Ws, C, dst, Hd, Wd,
                        dst_cstride, dst_coff, 1.0f / scale_factor, mul);
 }
 void launch_ifnet_build_x(const float* i0, const float* i1, const float* flow, const float* mask, int H, int W, float timestep,
                           float* x, hipStream_t st) {
-    hipLaunchKernelGGL(ifnet_build_x_kernel, dim3(ifn_grid((long)H * W)), dim3(256), 0, st, i0, i1, flow, mask, H, W, timestep, x);
+    hipLaunchKernelGGL(ifnet_build_x_kernel, dim3(grid_1d((long)H * W, 4096)), dim3(256), 0, st, i0, i1, flow, mask, H, W, timestep, x);
 }
 void launch_unshuffle2_cast(DType dt, const void* src, bool src_f32, int h, int w, int C, int src_cstride, void* dst,
                             int dst_channels, hipStream_t st) {
-    dim3 g(ifn_grid((long)(h / 2) * (w / 2) * dst_channels)), b(256);
+    dim3 g(grid_1d((long)(h / 2) * (w / 2) * dst_channels, 4096)), b(256);
     if (!src_f32 && !(C & 1) && !(src_cstride & 1) && !(dst_channels & 7) && !((size_t)src & 3) && !((size_t)dst & 15)) {
-        const dim3 g8(ifn_grid((long)(h / 2) * (w / 2) * (dst_channels / 8)));
-        if (dt == DT_BF16)
-            hipLaunchKernelGGL((unshuffle_typed8_kernel<__bf16>), g8, b, 0, st, (const __bf16*)src, h, w, C, src_cstride, (__bf16*)dst, dst_channels);
-        else
-            hipLaunchKernelGGL((unshuffle_typed8_kernel<_Float16>), g8, b, 0, st, (const _Float16*)src, h, w, C, src_cstride, (_Float16*)dst, dst_channels);
+        const dim3 g8(grid_1d((long)(h / 2) * (w / 2) * (dst_channels / 8), 4096));
+        with_operand_type(dt, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((unshuffle_typed8_kernel<T>), g8, b, 0, st, (const T*)src, h, w, C, src_cstride, (T*)dst, dst_channels);
+        });
         return;
     }
-    if (dt == DT_BF16) {
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
         if (src_f32)
-            hipLaunchKernelGGL((unshuffle_cast_kernel<__bf16, float>), g, b, 0, st, (const float*)src, h, w, C, src_cstride, (__bf16*)dst, dst_channels);
+            hipLaunchKernelGGL((unshuffle_cast_kernel<T, float>), g, b, 0, st, (const float*)src, h, w, C, src_cstride, (T*)dst, dst_channels);
         else
-            hipLaunchKernelGGL((unshuffle_cast_kernel<__bf16, __bf16>), g, b, 0, st, (const __bf16*)src, h, w, C, src_cstride, (__bf16*)dst, dst_channels);
-    } else {
-        if (src_f32)
-            hipLaunchKernelGGL((unshuffle_cast_kernel<_Float16, float>), g, b, 0, st, (const float*)src, h, w, C, src_cstride, (_Float16*)dst, dst_channels);
-        else
-            hipLaunchKernelGGL((unshuffle_cast_kernel<_Float16, _Float16>), g, b, 0, st, (const _Float16*)src, h, w, C, src_cstride, (_Float16*)dst, dst_channels);
-    }
+            hipLaunchKernelGGL((unshuffle_cast_kernel<T, T>), g, b, 0, st, (const T*)src, h, w, C, src_cstride, (T*)dst, dst_channels);
+    });
 }
 void launch_depth_to_space4(const float* src, int h, int w, int cs, float* dst, hipStream_t st) {
-    hipLaunchKernelGGL(depth_to_space4_kernel, dim3(ifn_grid((long)h * w * 96)), dim3(256), 0, st, src, h, w, cs, dst);
+    hipLaunchKernelGGL(depth_to_space4_kernel, dim3(grid_1d((long)h * w * 96, 4096)), dim3(256), 0, st, src, h, w, cs, dst);
 }
 void launch_ifnet_accumulate(const float* tmp, int hs, int ws, int H, int W, float scale, float* flow, float* mask, int first,
                              hipStream_t st) {
-    hipLaunchKernelGGL(ifnet_accumulate_kernel, dim3(ifn_grid((long)H * W)), dim3(256), 0, st, tmp, hs, ws, H, W, scale, flow, mask, first);
+    hipLaunchKernelGGL(ifnet_accumulate_kernel, dim3(grid_1d((long)H * W, 4096)), dim3(256), 0, st, tmp, hs, ws, H, W, scale, flow, mask, first);
 }
 void launch_ifnet_stage_input(DType dt, const float* i0, const float* i1, const float* flow, const float* mask, int H, int W, float timestep,
                               int s, void* dst, int dst_channels, hipStream_t st) {
@@ -443,33 +435,31 @@ void launch_ifnet_stage_input(DType dt, const float* i0, const float* i1, const 
     const dim3 g((unsigned)(blocks < 8192 ? blocks : 8192)), b(256);
     const float inv_sf = 1.0f / (1.0f / s), fmul = 1.0f / s;
     if (flow && !mask) throw Error(1, "ifnet stage input: flow without mask");
-#define FW_SI(T, CIN) hipLaunchKernelGGL((ifnet_stage_input_kernel<T, CIN>), g, b, 0, st, i0, i1, flow, mask, H, W, timestep, inv_sf, fmul, hs, ws, (T*)dst, dst_channels)
-    if (dt == DT_BF16) { if (flow) FW_SI(__bf16, 12); else FW_SI(__bf16, 7); }
-    else { if (flow) FW_SI(_Float16, 12); else FW_SI(_Float16, 7); }
-#undef FW_SI
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((flow ? ifnet_stage_input_kernel<T, 12> : ifnet_stage_input_kernel<T, 7>), g, b, 0, st, i0, i1, flow, mask, H, W, timestep, inv_sf, fmul, hs, ws,
+                           (T*)dst, dst_channels);
+    });
 }
 void launch_ifnet_accumulate_d2s(const float* t96, int hf, int wf, int cs, int H, int W, float scale, float* flow, float* mask, int first, hipStream_t st) {
     if ((cs & 1) || ((size_t)t96 & 7) || ((size_t)flow & 15)) throw Error(1, "ifnet accumulate: t96 must be 8-byte aligned with an even channel stride, flow 16-byte aligned");
-    hipLaunchKernelGGL(ifnet_accumulate_d2s_kernel, dim3(ifn_grid((long)H * W)), dim3(256), 0, st, t96, hf, wf, cs, H, W, scale, flow, mask, first);
+    hipLaunchKernelGGL(ifnet_accumulate_d2s_kernel, dim3(grid_1d((long)H * W, 4096)), dim3(256), 0, st, t96, hf, wf, cs, H, W, scale, flow, mask, first);
 }
 void launch_ifnet_blend(const float* i0, const float* i1, const float* flow, const float* mask, int Hp, int Wp, int H, int W,
                         uint8_t* out_bgr, float* out_rgb, hipStream_t st) {
-    hipLaunchKernelGGL(ifnet_blend_kernel, dim3(ifn_grid((long)H * W)), dim3(256), 0, st, i0, i1, flow, mask, Hp, Wp, H, W, out_bgr, out_rgb);
+    hipLaunchKernelGGL(ifnet_blend_kernel, dim3(grid_1d((long)H * W, 4096)), dim3(256), 0, st, i0, i1, flow, mask, Hp, Wp, H, W, out_bgr, out_rgb);
 }
 }  // namespace fw
 
 using namespace fw;
 
 namespace {
-int fail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
+// an entry's launch through the launcher the engine uses: what the launcher throws, then the launch's own status
+template <typename F>
+int launched(const char* fn, F&& f) {
+    const int rc = guarded(f);
+    return rc != FW_OK ? rc : hip_status(fn, hipGetLastError());
 }
-#define FW_LAUNCHED()                                                            \
-    do {                                                                         \
-        hipError_t e_ = hipGetLastError();                                       \
-        if (e_ != hipSuccess) return fail(FW_ERR_HIP, hipGetErrorString(e_));    \
-    } while (0)
 }  // namespace
 
 extern "C" {
@@ -477,127 +467,110 @@ extern "C" {
 int fw_u8_to_rgb_f32(const uint8_t* in_bgr, int height, int width, int padded_height, int padded_width, float* out,
                      void* stream) {
     if (!in_bgr || !out || height < 1 || width < 1 || padded_height < height || padded_width < width)
-        return fail(FW_ERR_INVALID, "fw_u8_to_rgb_f32: bad argument");
-    fw::launch_ifnet_u8_to_rgb(in_bgr, height, width, padded_height, padded_width, out, (hipStream_t)stream);
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid("fw_u8_to_rgb_f32", "bad argument");
+    return launched("fw_u8_to_rgb_f32", [&] { launch_ifnet_u8_to_rgb(in_bgr, height, width, padded_height, padded_width, out, (hipStream_t)stream); });
 }
 
 int fw_resize_bilinear_f32(const float* src, int src_h, int src_w, int channels, float* dst, int dst_h, int dst_w,
                            int dst_cstride, int dst_coff, float scale_factor, float mul, void* stream) {
     if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || dst_cstride < dst_coff + channels ||
         !(scale_factor > 0.f))
-        return fail(FW_ERR_INVALID, "fw_resize_bilinear_f32: bad argument");
-    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid_for((long)dst_h * dst_w)), dim3(256), 0, (hipStream_t)stream, src,
-                       src_h, src_w, channels, dst, dst_h, dst_w, dst_cstride, dst_coff, 1.0f / scale_factor, mul);
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid("fw_resize_bilinear_f32", "bad argument");
+    return launched("fw_resize_bilinear_f32", [&] {
+        launch_resize_bilinear(src, src_h, src_w, channels, dst, dst_h, dst_w, dst_cstride, dst_coff, scale_factor, mul, (hipStream_t)stream);
+    });
 }
 
 int fw_ifnet_build_x(const float* img0, const float* img1, const float* flow, const float* mask, int height, int width,
                      float timestep, float* x, void* stream) {
     if (!img0 || !img1 || !x || height < 1 || width < 1 || ((flow == nullptr) != (mask == nullptr)))
-        return fail(FW_ERR_INVALID, "fw_ifnet_build_x: bad argument");
-    hipLaunchKernelGGL(ifnet_build_x_kernel, dim3(grid_for((long)height * width)), dim3(256), 0, (hipStream_t)stream, img0,
-                       img1, flow, mask, height, width, timestep, x);
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid("fw_ifnet_build_x", "bad argument");
+    return launched("fw_ifnet_build_x", [&] { launch_ifnet_build_x(img0, img1, flow, mask, height, width, timestep, x, (hipStream_t)stream); });
 }
 
 int fw_unshuffle2_cast(int dtype, const void* src, int src_is_f32, int height, int width, int channels, int src_cstride,
                        void* dst, int dst_channels, void* stream) {
     if (!src || !dst || height < 2 || width < 2 || (height & 1) || (width & 1) || channels < 1 || src_cstride < channels ||
-        dst_channels < 4 * channels || (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16))
-        return fail(FW_ERR_INVALID, "fw_unshuffle2_cast: bad argument");
+        dst_channels < 4 * channels || !operand_dtype_ok(dtype))
+        return invalid("fw_unshuffle2_cast", "bad argument");
     // the engine's own dispatch: a typed source with even channel counts takes unshuffle_typed8_kernel
-    fw::launch_unshuffle2_cast((DType)dtype, src, src_is_f32 != 0, height, width, channels, src_cstride, dst, dst_channels, (hipStream_t)stream);
-    FW_LAUNCHED();
-    return FW_OK;
+    return launched("fw_unshuffle2_cast", [&] {
+        launch_unshuffle2_cast((DType)dtype, src, src_is_f32 != 0, height, width, channels, src_cstride, dst, dst_channels, (hipStream_t)stream);
+    });
 }
 
 int fw_ifnet_stage_input(int dtype, const float* img0, const float* img1, const float* flow, const float* mask, int height, int width,
                          float timestep, int scale, void* dst, int dst_channels, void* stream) {
-    if (!img0 || !img1 || !dst || height < 1 || width < 1 || scale < 1 || (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16))
-        return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: bad argument");
+    const char* fn = "fw_ifnet_stage_input";
+    if (!img0 || !img1 || !dst || height < 1 || width < 1 || scale < 1 || !operand_dtype_ok(dtype)) return invalid(fn, "bad argument");
     if (dst_channels > 64 || (dst_channels & 7) || dst_channels < 4 * (flow ? 12 : 7) || height % (2 * scale) || width % (2 * scale))
-        return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: bad shape");
-    if ((flow == nullptr) != (mask == nullptr)) return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: flow and mask go together");
-    if (((size_t)flow & 15) || ((size_t)dst & 15)) return fail(FW_ERR_INVALID, "fw_ifnet_stage_input: flow and dst must be 16-byte aligned");
-    try {
-        fw::launch_ifnet_stage_input((DType)dtype, img0, img1, flow, mask, height, width, timestep, scale, dst, dst_channels, (hipStream_t)stream);
-    } catch (const fw::Error& e) {
-        return fail(FW_ERR_INVALID, e.what());
-    }
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid(fn, "bad shape");
+    if ((flow == nullptr) != (mask == nullptr)) return invalid(fn, "flow and mask go together");
+    if (((size_t)flow & 15) || ((size_t)dst & 15)) return invalid(fn, "flow and dst must be 16-byte aligned");
+    // (what the launcher still refuses it throws as Error(FW_ERR_INVALID, ...))
+    return launched(fn, [&] {
+        launch_ifnet_stage_input((DType)dtype, img0, img1, flow, mask, height, width, timestep, scale, dst, dst_channels, (hipStream_t)stream);
+    });
 }
 
 int fw_ifnet_accumulate_d2s(const float* t96, int feat_h, int feat_w, int src_cstride, int height, int width, float scale, float* flow,
                             float* mask, int first, void* stream) {
+    const char* fn = "fw_ifnet_accumulate_d2s";
     if (!t96 || !flow || !mask || feat_h < 1 || feat_w < 1 || height < 1 || width < 1 || src_cstride < 96 || !(scale >= 1.f))
-        return fail(FW_ERR_INVALID, "fw_ifnet_accumulate_d2s: bad argument");
+        return invalid(fn, "bad argument");
     if ((src_cstride & 1) || ((size_t)t96 & 7) || ((size_t)flow & 15))
-        return fail(FW_ERR_INVALID, "fw_ifnet_accumulate_d2s: t96 must be 8-byte aligned with an even channel stride, flow 16-byte aligned");
-    try {
-        fw::launch_ifnet_accumulate_d2s(t96, feat_h, feat_w, src_cstride, height, width, scale, flow, mask, first, (hipStream_t)stream);
-    } catch (const fw::Error& e) {
-        return fail(FW_ERR_INVALID, e.what());
-    }
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid(fn, "t96 must be 8-byte aligned with an even channel stride, flow 16-byte aligned");
+    return launched(fn, [&] {
+        launch_ifnet_accumulate_d2s(t96, feat_h, feat_w, src_cstride, height, width, scale, flow, mask, first, (hipStream_t)stream);
+    });
 }
 
 int fw_depth_to_space4_f32(const float* src, int height, int width, int src_cstride, float* dst, void* stream) {
-    if (!src || !dst || height < 1 || width < 1 || src_cstride < 96) return fail(FW_ERR_INVALID, "fw_depth_to_space4_f32: bad argument");
-    hipLaunchKernelGGL(depth_to_space4_kernel, dim3(grid_for((long)height * width * 96)), dim3(256), 0, (hipStream_t)stream,
-                       src, height, width, src_cstride, dst);
-    FW_LAUNCHED();
-    return FW_OK;
+    if (!src || !dst || height < 1 || width < 1 || src_cstride < 96) return invalid("fw_depth_to_space4_f32", "bad argument");
+    return launched("fw_depth_to_space4_f32", [&] { launch_depth_to_space4(src, height, width, src_cstride, dst, (hipStream_t)stream); });
 }
 
 int fw_ifnet_accumulate(const float* tmp, int tmp_h, int tmp_w, int height, int width, float scale, float* flow, float* mask,
                         int first, void* stream) {
     if (!tmp || !flow || !mask || tmp_h < 1 || tmp_w < 1 || height < 1 || width < 1 || !(scale >= 1.f))
-        return fail(FW_ERR_INVALID, "fw_ifnet_accumulate: bad argument");
-    hipLaunchKernelGGL(ifnet_accumulate_kernel, dim3(grid_for((long)height * width)), dim3(256), 0, (hipStream_t)stream, tmp,
-                       tmp_h, tmp_w, height, width, scale, flow, mask, first);
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid("fw_ifnet_accumulate", "bad argument");
+    return launched("fw_ifnet_accumulate", [&] {
+        launch_ifnet_accumulate(tmp, tmp_h, tmp_w, height, width, scale, flow, mask, first, (hipStream_t)stream);
+    });
 }
 
 int fw_ifnet_blend(const float* img0, const float* img1, const float* flow, const float* mask, int padded_height,
                    int padded_width, int height, int width, uint8_t* out_bgr, float* out_rgb_f32, void* stream) {
     if (!img0 || !img1 || !flow || !mask || (!out_bgr && !out_rgb_f32) || height < 1 || width < 1 || padded_height < height ||
         padded_width < width)
-        return fail(FW_ERR_INVALID, "fw_ifnet_blend: bad argument");
-    hipLaunchKernelGGL(ifnet_blend_kernel, dim3(grid_for((long)height * width)), dim3(256), 0, (hipStream_t)stream, img0, img1,
-                       flow, mask, padded_height, padded_width, height, width, out_bgr, out_rgb_f32);
-    FW_LAUNCHED();
-    return FW_OK;
+        return invalid("fw_ifnet_blend", "bad argument");
+    return launched("fw_ifnet_blend", [&] {
+        launch_ifnet_blend(img0, img1, flow, mask, padded_height, padded_width, height, width, out_bgr, out_rgb_f32, (hipStream_t)stream);
+    });
 }
 
 int fw_unsharp_mask_u8(const uint8_t* src, int height, int width, int channels, int box_radius, unsigned ww, unsigned fw_weight,
                        int passes, int percent, int threshold, uint8_t* scratch_a, uint8_t* scratch_b, uint8_t* out, void* stream) {
+    const char* fn = "fw_unsharp_mask_u8";
     if (!src || !scratch_a || !scratch_b || !out || height < 1 || width < 1 || channels < 1 || channels > 4 || box_radius < 0 ||
         box_radius > 1024 || passes < 1 || passes > 8 || percent < 0 || threshold < 0 ||
         (unsigned long long)ww * (2ull * box_radius + 1) + 2ull * fw_weight > (1ull << 24))
-        return fail(FW_ERR_INVALID, "fw_unsharp_mask_u8: bad argument");
+        return invalid(fn, "bad argument");
     const long n = (long)height * width * channels;
+    const dim3 grid(grid_1d(n, 4096));
     hipStream_t st = (hipStream_t)stream;
     const uint8_t* cur = src;
     uint8_t* bufs[2] = {scratch_a, scratch_b};
     int which = 0;
     for (int axis = 0; axis < 2; ++axis)
         for (int k = 0; k < passes; ++k) {
-            hipLaunchKernelGGL(box_blur_pass_u8_kernel, dim3(grid_for(n)), dim3(256), 0, st, cur, bufs[which], height, width, channels,
-                               axis, box_radius, ww, fw_weight);
-            FW_LAUNCHED();
+            hipLaunchKernelGGL(box_blur_pass_u8_kernel, grid, dim3(256), 0, st, cur, bufs[which], height, width, channels, axis, box_radius, ww, fw_weight);
+            if (const int rc = hip_status(fn, hipGetLastError())) return rc;
             cur = bufs[which];
             which ^= 1;
         }
-    hipLaunchKernelGGL(unsharp_finish_u8_kernel, dim3(grid_for(n)), dim3(256), 0, st, src, cur, n, percent, threshold, out);
-    FW_LAUNCHED();
-    return FW_OK;
+    hipLaunchKernelGGL(unsharp_finish_u8_kernel, grid, dim3(256), 0, st, src, cur, n, percent, threshold, out);
+    return hip_status(fn, hipGetLastError());
 }
 
 }  // extern "C"

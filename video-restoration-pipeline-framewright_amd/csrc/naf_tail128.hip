@@ -224,20 +224,17 @@ void launch_naf_tail128(DType dt, const NafTail128Params& p_in, const float* sca
     if (!p.x || !p.stream || !p.blocks || !p.w3_scratch || !sca || p.M < 1 || (p.ldx % 8) || (p.lds_ % 4))
         throw Error(1, "naf_tail128: bad argument");
     // conv3's two blocks with this forward's SCA factors
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((naf_tail128_scale_w3_kernel<__bf16>), dim3(9), dim3(256), 0, st, (const char*)p.blocks, sca, (char*)p.w3_scratch);
-    else
-        hipLaunchKernelGGL((naf_tail128_scale_w3_kernel<_Float16>), dim3(9), dim3(256), 0, st, (const char*)p.blocks, sca, (char*)p.w3_scratch);
+    const char* all_blocks = (const char*)p.blocks;
     p.w3_scaled = p.w3_scratch;
-    p.blocks = (const char*)p.blocks + 2 * T128_BLOCK;   // the kernel's blocks 2 .. 7
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    p.blocks = all_blocks + 2 * T128_BLOCK;   // the kernel's blocks 2 .. 7
+    const int cus = device_cus();             // of the current device, asked at every launch
     const long tiles = (p.M + T128_PX - 1) / T128_PX;
     const long grid = tiles < cus ? tiles : cus;
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((naf_tail128_kernel<__bf16>), dim3((unsigned)grid), dim3(512), 0, st, p);
-    else
-        hipLaunchKernelGGL((naf_tail128_kernel<_Float16>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((naf_tail128_scale_w3_kernel<T>), dim3(9), dim3(256), 0, st, all_blocks, sca, (char*)p.w3_scratch);
+        hipLaunchKernelGGL((naf_tail128_kernel<T>), dim3((unsigned)grid), dim3(512), 0, st, p);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 

@@ -589,12 +589,6 @@ int fw_nafnet_run_resample(fw_nafnet* n, int level, int up, const float* src_f32
     });
 }
 
-int fw_u8_to_nhwc_padded(int dtype, const uint8_t* in_bgr, int H, int W, int Hp, int Wp, void* out, void* stream) {
-    if (!in_bgr || !out || H < 1 || W < 1 || Hp < H || Wp < W) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc_padded: bad argument");
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc_padded: bad dtype");
-    return guarded([&] { launch_u8_to_nhwc_padded((DType)dtype, in_bgr, H, W, Hp, Wp, out, (hipStream_t)stream); });
-}
-
 double fw_nafnet_flops(const fw_nafnet* n, int H, int W) {
     if (!n || H < 1 || W < 1) return 0.0;
     const int mult = 1 << n->nlev;
@@ -618,79 +612,6 @@ double fw_nafnet_flops(const fw_nafnet* n, int H, int W) {
     }
     mac += px * 9 * n->width * 3;
     return 2.0 * mac;
-}
-
-// ---- K8: blend kernels of the TAP driver (tap_denoise.py:417-534, :614-618) ---------------------------------------
-int fw_u8_crop(const uint8_t* src, int height, int width, int y0, int x0, int th, int tw, uint8_t* dst, void* stream) {
-    if (!src || !dst || th < 1 || tw < 1 || y0 < 0 || x0 < 0 || y0 + th > height || x0 + tw > width)
-        return fail(FW_ERR_INVALID, "fw_u8_crop: window outside the frame");
-    return guarded([&] { launch_u8_crop(src, width, y0, x0, th, tw, dst, (hipStream_t)stream); });
-}
-
-int fw_tile_blend_accumulate(float* acc, float* wsum, int height, int width, const uint8_t* tile, int y0, int x0, int th,
-                             int tw, int overlap, void* stream) {
-    if (!acc || !wsum || !tile || th < 1 || tw < 1 || y0 < 0 || x0 < 0 || y0 + th > height || x0 + tw > width || overlap < 0 ||
-        overlap > th || overlap > tw)
-        return fail(FW_ERR_INVALID, "fw_tile_blend_accumulate: bad tile geometry");
-    return guarded([&] {
-        launch_tile_blend_acc(acc, wsum, width, tile, y0, x0, th, tw, overlap, y0 > 0, y0 + th < height, x0 > 0,
-                              x0 + tw < width, (hipStream_t)stream);
-    });
-}
-
-int fw_tile_blend_finish(const float* acc, const float* wsum, int height, int width, uint8_t* out, void* stream) {
-    if (!acc || !wsum || !out || height < 1 || width < 1) return fail(FW_ERR_INVALID, "fw_tile_blend_finish: bad argument");
-    return guarded([&] { launch_tile_blend_finish(acc, wsum, (long)height * width, out, (hipStream_t)stream); });
-}
-
-int fw_temporal_average_u8(const uint8_t* const* frames, const float* weights, int count, size_t nbytes, uint8_t* out,
-                           void* stream) {
-    if (!frames || !weights || !out || count < 1 || count > 16) return fail(FW_ERR_INVALID, "fw_temporal_average_u8: bad argument");
-    for (int k = 0; k < count; ++k)
-        if (!frames[k]) return fail(FW_ERR_INVALID, "fw_temporal_average_u8: NULL frame");
-    return guarded([&] { launch_temporal_average(frames, weights, count, (long)nbytes, out, (hipStream_t)stream); });
-}
-
-int fw_strength_blend_u8(const uint8_t* original, const uint8_t* denoised, double strength, size_t nbytes, uint8_t* out,
-                         void* stream) {
-    if (!original || !denoised || !out || !(strength >= 0.0 && strength <= 1.0))
-        return fail(FW_ERR_INVALID, "fw_strength_blend_u8: bad argument");
-    // (1 - s) is formed in double like the reference's Python float arithmetic, then rounded once to float32
-    const float oms = (float)(1.0 - strength);
-    const float sf = (float)strength;
-    return guarded([&] { launch_strength_blend(original, denoised, oms, sf, (long)nbytes, out, (hipStream_t)stream); });
-}
-
-int fw_grain_addback_u8(const uint8_t* original, const uint8_t* denoised, int height, int width, double factor,
-                        uint16_t* scratch, uint8_t* out, void* stream) {
-    if (!original || !denoised || !scratch || !out || height < 1 || width < 1 || !(factor >= 0.0) || factor > 1.0)
-        return fail(FW_ERR_INVALID, "fw_grain_addback_u8: bad argument");
-    return guarded([&] { launch_grain_addback(original, denoised, height, width, factor, scratch, out, (hipStream_t)stream); });
-}
-
-int fw_resize_lanczos4_u8(const uint8_t* src, int src_h, int src_w, int channels, uint8_t* dst, int dst_h, int dst_w, void* stream) {
-    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
-        return fail(FW_ERR_INVALID, "fw_resize_lanczos4_u8: bad argument");
-    return guarded([&] { launch_resize_lanczos4_u8(src, src_h, src_w, channels, dst, dst_h, dst_w, (hipStream_t)stream); });
-}
-
-int fw_resize_lanczos4_u16(const uint16_t* src, int src_h, int src_w, int channels, uint16_t* dst, int dst_h, int dst_w, void* stream) {
-    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
-        return fail(FW_ERR_INVALID, "fw_resize_lanczos4_u16: bad argument");
-    return guarded([&] { launch_resize_lanczos4_u16(src, src_h, src_w, channels, dst, dst_h, dst_w, (hipStream_t)stream); });
-}
-
-int fw_resize_linear_u8(const uint8_t* src, int src_h, int src_w, int channels, uint8_t* dst, int dst_h, int dst_w, void* stream) {
-    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
-        return fail(FW_ERR_INVALID, "fw_resize_linear_u8: bad argument");
-    return guarded([&] { launch_resize_linear_u8(src, src_h, src_w, channels, dst, dst_h, dst_w, (hipStream_t)stream); });
-}
-
-int fw_face_paste_u8(uint8_t* frame, int height, int width, int x1, int y1, int x2, int y2, const uint8_t* enhanced, double strength,
-                     void* stream) {
-    if (!frame || !enhanced || height < 1 || width < 1 || !(strength >= 0.0) || strength > 1.0)
-        return fail(FW_ERR_INVALID, "fw_face_paste_u8: bad argument");
-    return guarded([&] { launch_face_paste_u8(frame, height, width, x1, y1, x2, y2, enhanced, (float)strength, (hipStream_t)stream); });
 }
 
 int fw_nafnet_destroy(fw_nafnet* n) {
@@ -717,22 +638,6 @@ int fw_nafnet_destroy(fw_nafnet* n) {
     n->order.destroy();
     delete n;
     return FW_OK;
-}
-
-size_t fw_preserve_edges_scratch_bytes(int height, int width) {
-    if (height < 1 || width < 1) return 0;
-    return preserve_edges_scratch_bytes(height, width);
-}
-
-int fw_preserve_edges_u8(const uint8_t* original, const uint8_t* denoised, int height, int width, double low_threshold,
-                         double high_threshold, void* scratch, uint8_t* out, void* stream) {
-    if (!original || !denoised || !scratch || !out || height < 1 || width < 1 || !(low_threshold >= 0) || !(high_threshold >= 0))
-        return fail(FW_ERR_INVALID, "fw_preserve_edges_u8: bad argument");
-    return guarded([&] {
-        double lo = low_threshold, hi = high_threshold;
-        if (lo > hi) std::swap(lo, hi);
-        launch_preserve_edges(original, denoised, height, width, (int)floor(lo), (int)floor(hi), scratch, out, (hipStream_t)stream);
-    });
 }
 
 }  // extern "C"

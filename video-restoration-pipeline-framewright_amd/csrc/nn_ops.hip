@@ -714,14 +714,12 @@ void launch_pointwise(DType dt, const PointwiseParams& p, hipStream_t st) {
     if (p.gather2x2 && (p.Cin & 31)) throw Error(1, "pointwise: 2x2 gather needs Cin % 32 == 0");
     if (p.ln_w && (!p.ln_b || !p.a_f32 || p.gather2x2 || p.a_scale || p.K != 64 || p.lda != 64))
         throw Error(1, "pointwise: fused LayerNorm needs a plain fp32 [M][64] input");
-    if (pointwise_small_eligible(p)) {
-        if (dt == DT_BF16) launch_pw_small<__bf16>(p, st); else launch_pw_small<_Float16>(p, st);
-        return;
-    }
-    if (dt == DT_BF16)
-        launch_pw_typed<__bf16>(p, st);
-    else
-        launch_pw_typed<_Float16>(p, st);
+    const bool small = pointwise_small_eligible(p);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (small) launch_pw_small<T>(p, st);
+        else launch_pw_typed<T>(p, st);
+    });
 }
 
 // =====================================================================================================
@@ -960,13 +958,12 @@ void launch_naf_tail64(DType dt, const void* x, const float* a_scale, float* str
     NafTailParams p{x, a_scale, stream, M, w3, w4, w5, b3, b4, b5, beta, gamma, ln_w, ln_b, ln_eps};
     const long tiles = (M + PW_PX - 1) / PW_PX;
     // two workgroups per CU are resident (64 KB of LDS each): a grid of that many, each walking a contiguous range of tiles
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();   // of the current device, asked at every launch
     const long grid = tiles < 2L * cus ? tiles : 2L * cus;
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((naf_tail64_kernel<__bf16>), dim3((unsigned)grid), dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL((naf_tail64_kernel<_Float16>), dim3((unsigned)grid), dim3(256), 0, st, p);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((naf_tail64_kernel<T>), dim3((unsigned)grid), dim3(256), 0, st, p);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 
@@ -1066,13 +1063,11 @@ void launch_layernorm2d(DType dt, const float* x, long M, int C, const float* w,
     const int lpp = C <= 64 ? 16 : (C <= 128 ? 32 : 64);
     const long groups = (M + 64 / lpp - 1) / (64 / lpp);
     const long blocks = (groups + 3) / 4 < 4096 ? (groups + 3) / 4 : 4096;
-#define FW_LN(T, L) hipLaunchKernelGGL((layernorm2d_kernel<T, L>), dim3((unsigned)blocks), dim3(256), 0, st, x, M, C, w, b, (T*)out, 1e-6f)
-    if (dt == DT_BF16) {
-        if (lpp == 16) FW_LN(__bf16, 16); else if (lpp == 32) FW_LN(__bf16, 32); else FW_LN(__bf16, 64);
-    } else {
-        if (lpp == 16) FW_LN(_Float16, 16); else if (lpp == 32) FW_LN(_Float16, 32); else FW_LN(_Float16, 64);
-    }
-#undef FW_LN
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto k = lpp == 16 ? layernorm2d_kernel<T, 16> : (lpp == 32 ? layernorm2d_kernel<T, 32> : layernorm2d_kernel<T, 64>);
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, st, x, M, C, w, b, (T*)out, 1e-6f);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 
@@ -1318,9 +1313,7 @@ static int dwconv_wide_rows(int H, int W, int C) {
 
 int dwconv_blocks(int H, int W, int C) {
     if (C >= 256 && dwconv_wide()) return dwconv_wide_rows(H, W, C);
-    const long total = (long)((H + GATE_ROWS - 1) / GATE_ROWS) * W * (C / 8);
-    const long b = (total + 255) / 256;
-    return (int)(b < DW_MAX_BLOCKS ? b : DW_MAX_BLOCKS);
+    return grid_1d((long)((H + GATE_ROWS - 1) / GATE_ROWS) * W * (C / 8), DW_MAX_BLOCKS);
 }
 
 void launch_dwconv3x3_gate(DType dt, const void* x, int H, int W, int C, const float* wdw, const float* bdw, void* out,
@@ -1328,12 +1321,10 @@ void launch_dwconv3x3_gate(DType dt, const void* x, int H, int W, int C, const f
     if (C < 32 || (C & (C - 1)) || C > 1024) throw Error(1, "dwconv3x3_gate: C must be a power of two in [32, 1024]");
     if (C >= 256 && dwconv_wide()) {
         const int grid = dwconv_wide_rows(H, W, C) * (C / 256);
-        if (dt == DT_BF16)
-            hipLaunchKernelGGL((dwconv3x3_gate_wide_kernel<__bf16>), dim3((unsigned)grid), dim3(256), 0, st, (const __bf16*)x, H, W, C, wdw, bdw,
-                               (__bf16*)out, partial);
-        else
-            hipLaunchKernelGGL((dwconv3x3_gate_wide_kernel<_Float16>), dim3((unsigned)grid), dim3(256), 0, st, (const _Float16*)x, H, W, C, wdw, bdw,
-                               (_Float16*)out, partial);
+        with_operand_type(dt, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((dwconv3x3_gate_wide_kernel<T>), dim3((unsigned)grid), dim3(256), 0, st, (const T*)x, H, W, C, wdw, bdw, (T*)out, partial);
+        });
         FW_HIP_CHECK(hipGetLastError());
         return;
     }
@@ -1348,12 +1339,10 @@ void launch_dwconv3x3_gate(DType dt, const void* x, int H, int W, int C, const f
         return true;
     }();
     (void)attr_set;
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((dwconv3x3_gate_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), smem, st, (const __bf16*)x, H,
-                           W, C, wdw, bdw, (__bf16*)out, partial);
-    else
-        hipLaunchKernelGGL((dwconv3x3_gate_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), smem, st,
-                           (const _Float16*)x, H, W, C, wdw, bdw, (_Float16*)out, partial);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((dwconv3x3_gate_kernel<T>), dim3((unsigned)blocks), dim3(256), smem, st, (const T*)x, H, W, C, wdw, bdw, (T*)out, partial);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 
@@ -1418,13 +1407,11 @@ __global__ __launch_bounds__(256) void f32_to_planar_kernel(const float* __restr
 
 void launch_f32_to_planar(DType dt, const float* x, long M, int C, void* out, hipStream_t st) {
     if (C & 31) throw Error(1, "f32_to_planar: C must be a multiple of 32");
-    const long total = M * (C / 8);
-    const long blocks = (total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096;
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((f32_to_planar_kernel<__bf16>), dim3((unsigned)blocks), dim3(256), 0, st, x, M, C, (__bf16*)out);
-    else
-        hipLaunchKernelGGL((f32_to_planar_kernel<_Float16>), dim3((unsigned)blocks), dim3(256), 0, st, x, M, C,
-                           (_Float16*)out);
+    const int blocks = grid_1d(M * (C / 8), 4096);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((f32_to_planar_kernel<T>), dim3(blocks), dim3(256), 0, st, x, M, C, (T*)out);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 

@@ -243,12 +243,7 @@ __global__ __launch_bounds__(256) void pw16_scale_weights_kernel(const uint4* __
 }
 
 static int gemm_cus() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
+    static int n = device_cus();
     return n;
 }
 
@@ -268,37 +263,24 @@ void launch_pointwise_gemm(DType dt, const PointwiseParams& p, hipStream_t st) {
     const bool half = half_on && p.mode != PW_GATE && 2 * tiles <= gemm_cus();   // 256 x 256 tiles would leave half of the CUs idle
     if (half) tiles *= 2;
     dim3 grid((unsigned)(tiles < gemm_cus() ? tiles : gemm_cus())), block(512);
-#define FW_G(MODE)                                                                              \
-    do {                                                                                        \
-        if (dt == DT_BF16)                                                                      \
-            hipLaunchKernelGGL((pw_gemm_kernel<__bf16, MODE>), grid, block, 0, st, p);          \
-        else                                                                                    \
-            hipLaunchKernelGGL((pw_gemm_kernel<_Float16, MODE>), grid, block, 0, st, p);        \
-    } while (0)
-#define FW_GH(MODE)                                                                             \
-    do {                                                                                        \
-        if (dt == DT_BF16)                                                                      \
-            hipLaunchKernelGGL((pw_gemm_kernel<__bf16, MODE, 2>), grid, block, 0, st, p);       \
-        else                                                                                    \
-            hipLaunchKernelGGL((pw_gemm_kernel<_Float16, MODE, 2>), grid, block, 0, st, p);     \
-    } while (0)
-    if (half && p.mode == PW_STORE) FW_GH(PW_STORE);
-    else if (half) FW_GH(PW_RESIDUAL);
-    else if (p.mode == PW_STORE) FW_G(PW_STORE);
-    else if (p.mode == PW_GATE) FW_G(PW_GATE);
-    else FW_G(PW_RESIDUAL);
-#undef FW_G
-#undef FW_GH
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (half && p.mode == PW_STORE) hipLaunchKernelGGL((pw_gemm_kernel<T, PW_STORE, 2>), grid, block, 0, st, p);
+        else if (half) hipLaunchKernelGGL((pw_gemm_kernel<T, PW_RESIDUAL, 2>), grid, block, 0, st, p);
+        else if (p.mode == PW_STORE) hipLaunchKernelGGL((pw_gemm_kernel<T, PW_STORE>), grid, block, 0, st, p);
+        else if (p.mode == PW_GATE) hipLaunchKernelGGL((pw_gemm_kernel<T, PW_GATE>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((pw_gemm_kernel<T, PW_RESIDUAL>), grid, block, 0, st, p);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 
 void launch_pw16_scale_weights(DType dt, const void* src, const float* scale, int N, int K, void* dst, hipStream_t st) {
     const long frags = (long)(N / 16) * (K / 32);
-    const int blocks = (int)((frags * 64 + 255) / 256 < 2048 ? (frags * 64 + 255) / 256 : 2048);
-    if (dt == DT_BF16)
-        hipLaunchKernelGGL((pw16_scale_weights_kernel<__bf16>), dim3(blocks), dim3(256), 0, st, (const uint4*)src, scale, frags, K / G_KB, (uint4*)dst);
-    else
-        hipLaunchKernelGGL((pw16_scale_weights_kernel<_Float16>), dim3(blocks), dim3(256), 0, st, (const uint4*)src, scale, frags, K / G_KB, (uint4*)dst);
+    const int blocks = grid_1d(frags * 64, 2048);
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((pw16_scale_weights_kernel<T>), dim3(blocks), dim3(256), 0, st, (const uint4*)src, scale, frags, K / G_KB, (uint4*)dst);
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 

@@ -736,12 +736,7 @@ __global__ __launch_bounds__(512, 2) void pw_dw_mfma_kernel(const PwDwParams p) 
 }
 
 static int front_cus() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
+    static int n = device_cus();
     return n;
 }
 
@@ -769,29 +764,27 @@ void launch_pw_dw(DType dt, const PwDwParams& p, hipStream_t st) {
     // it inside one process)
     bool on_mfma = false;
     if (const char* e = getenv("FW_PW_DW_MFMA")) on_mfma = atoi(e) != 0;
-#define FW_F(CG, MODE)                                                                            \
-    do {                                                                                          \
-        if (on_mfma) {                                                                            \
-            if (dt == DT_BF16)                                                                    \
-                hipLaunchKernelGGL((pw_dw_mfma_kernel<__bf16, CG, MODE>), grid, block, 0, st, p); \
-            else                                                                                  \
-                hipLaunchKernelGGL((pw_dw_mfma_kernel<_Float16, CG, MODE>), grid, block, 0, st, p); \
-        } else if (dt == DT_BF16)                                                                 \
-            hipLaunchKernelGGL((pw_dw_kernel<__bf16, CG, MODE>), grid, block, 0, st, p);          \
-        else                                                                                      \
-            hipLaunchKernelGGL((pw_dw_kernel<_Float16, CG, MODE>), grid, block, 0, st, p);        \
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+#define FW_F(CG, MODE)                                                                  \
+    do {                                                                                \
+        if (on_mfma)                                                                    \
+            hipLaunchKernelGGL((pw_dw_mfma_kernel<T, CG, MODE>), grid, block, 0, st, p); \
+        else                                                                            \
+            hipLaunchKernelGGL((pw_dw_kernel<T, CG, MODE>), grid, block, 0, st, p);     \
     } while (0)
-    if (p.mode == PWDW_GATE_MUL) {
-        if (p.cin == 64) FW_F(4, PWDW_GATE_MUL);
-        else FW_F(8, PWDW_GATE_MUL);
-    } else if (p.mode == PWDW_NONE) {
-        if (p.cin == 48) FW_F(3, PWDW_NONE);
-        else FW_F(6, PWDW_NONE);
-    } else {
-        if (p.cin == 48) FW_F(3, PWDW_GATE_GELU);
-        else FW_F(6, PWDW_GATE_GELU);
-    }
+        if (p.mode == PWDW_GATE_MUL) {
+            if (p.cin == 64) FW_F(4, PWDW_GATE_MUL);
+            else FW_F(8, PWDW_GATE_MUL);
+        } else if (p.mode == PWDW_NONE) {
+            if (p.cin == 48) FW_F(3, PWDW_NONE);
+            else FW_F(6, PWDW_NONE);
+        } else {
+            if (p.cin == 48) FW_F(3, PWDW_GATE_GELU);
+            else FW_F(6, PWDW_GATE_GELU);
+        }
 #undef FW_F
+    });
     FW_HIP_CHECK(hipGetLastError());
 }
 

@@ -12,8 +12,7 @@
 //                        (fixed-order two-level reduction -> deterministic), temperature, softmax
 //   attn_apply           out[p][c1] = sum_c2 A[head][c1][c2] * v[p][c2]
 //   pixel_(un)shuffle2   fp32 NHWC
-#include "fw_internal.h"
-#include "../../include/framewright_hip.h"
+#include "fw_status.h"
 
 namespace fw {
 
@@ -831,79 +830,51 @@ __global__ __launch_bounds__(256) void pack_pointwise_t_kernel(const T* __restri
     }
 }
 
-static int blocks_for(long n, int cap) {
-    const long b = (n + 255) / 256;
-    return (int)(b < cap ? (b > 0 ? b : 1) : cap);
-}
-
 }  // namespace fw
 
 using namespace fw;
-
-namespace {
-int rfail(int code, const std::string& m) {
-    fw::last_error_ref() = m;
-    return code;
-}
-template <typename F>
-int rguard(F&& f) {
-    try {
-        f();
-        return FW_OK;
-    } catch (const fw::Error& e) {
-        return rfail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return rfail(FW_ERR_INTERNAL, e.what());
-    }
-}
-bool bad_dtype(int d) { return d != FW_DTYPE_BF16 && d != FW_DTYPE_F16; }
-}  // namespace
 
 extern "C" {
 
 int fw_layernorm_nhwc(int dtype, const float* x, long ldx, long M, int C, const float* weight, const float* bias, float eps,
                       void* out, long ldo, int zero_to, void* stream) {
-    if (bad_dtype(dtype) || !x || !weight || !out || M < 1 || C < 1 || C > 512 || zero_to > ldo || C > ldx)
-        return rfail(FW_ERR_INVALID, "fw_layernorm_nhwc: bad argument");
-    return rguard([&] {
+    if (!operand_dtype_ok(dtype) || !x || !weight || !out || M < 1 || C < 1 || C > 512 || zero_to > ldo || C > ldx)
+        return invalid("fw_layernorm_nhwc", "bad argument");
+    return guarded([&] {
         const int cz = zero_to > C ? zero_to : C;
         if (!(C & 3) && !(cz & 3) && !(ldx & 3) && !(ldo & 3) && !((size_t)x & 15) && !((size_t)out & 7)) {
             const int lanes = (cz + 3) / 4;   // lanes a pixel needs in one pass
             const int lpp = lanes <= 16 ? 16 : (lanes <= 32 ? 32 : 64);
-            const int blocks = blocks_for((M + 64 / lpp - 1) / (64 / lpp) * 64, 4096);
-#define FW_LNV(T, L) hipLaunchKernelGGL((layernorm_nhwc_vec_kernel<T, L>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, M, C, weight, bias, eps, (T*)out, ldo, cz)
-            if (dtype == FW_DTYPE_BF16) {
-                if (lpp == 16) FW_LNV(__bf16, 16); else if (lpp == 32) FW_LNV(__bf16, 32); else FW_LNV(__bf16, 64);
-            } else {
-                if (lpp == 16) FW_LNV(_Float16, 16); else if (lpp == 32) FW_LNV(_Float16, 32); else FW_LNV(_Float16, 64);
-            }
-#undef FW_LNV
+            const int blocks = grid_1d((M + 64 / lpp - 1) / (64 / lpp) * 64, 4096);
+            with_operand_type((DType)dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                const auto k = lpp == 16 ? layernorm_nhwc_vec_kernel<T, 16> : (lpp == 32 ? layernorm_nhwc_vec_kernel<T, 32> : layernorm_nhwc_vec_kernel<T, 64>);
+                hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, M, C, weight, bias, eps, (T*)out, ldo, cz);
+            });
             FW_HIP_CHECK(hipGetLastError());
             return;
         }
-        const int blocks = blocks_for(M * 64, 4096);
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((layernorm_nhwc_kernel<__bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, M, C, weight,
-                               bias, eps, (__bf16*)out, ldo, zero_to);
-        else
-            hipLaunchKernelGGL((layernorm_nhwc_kernel<_Float16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, M, C,
-                               weight, bias, eps, (_Float16*)out, ldo, zero_to);
+        const int blocks = grid_1d(M * 64, 4096);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((layernorm_nhwc_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, M, C, weight, bias, eps, (T*)out, ldo, zero_to);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
 
 size_t fw_pack_pointwise(int dtype, const float* weight, int cout, int k, void* dst) {
-    if (bad_dtype(dtype) || cout < 1 || k < 1 || (k & 31)) return 0;
+    if (!operand_dtype_ok(dtype) || cout < 1 || k < 1 || (k & 31)) return 0;
     return pack_pointwise_weights((DType)dtype, weight, cout, k, (uint16_t*)dst);
 }
 
 int fw_pointwise_nhwc(int dtype, const void* a, int a_is_f32, long lda, long M, int k, const void* packed_weight,
                       const float* bias, int cout_tiles, void* out_typed, long ldo, float* out_f32, long ldf,
                       const float* res_f32, const float* chan_scale, void* stream) {
-    if (bad_dtype(dtype) || !a || !packed_weight || (!out_typed && !out_f32))
-        return rfail(FW_ERR_INVALID, "fw_pointwise_nhwc: bad argument");
-    if (res_f32 && (!out_f32 || !chan_scale)) return rfail(FW_ERR_INVALID, "fw_pointwise_nhwc: residual needs out_f32 and chan_scale");
-    return rguard([&] {
+    if (!operand_dtype_ok(dtype) || !a || !packed_weight || (!out_typed && !out_f32))
+        return invalid("fw_pointwise_nhwc", "bad argument");
+    if (res_f32 && (!out_f32 || !chan_scale)) return invalid("fw_pointwise_nhwc", "residual needs out_f32 and chan_scale");
+    return guarded([&] {
         PointwiseParams p{};
         p.a = a;
         p.a_f32 = a_is_f32;
@@ -926,10 +897,10 @@ int fw_pointwise_nhwc(int dtype, const void* a, int a_is_f32, long lda, long M, 
 
 int fw_dwconv3x3_nhwc(int dtype, const void* x, long ldx, int H, int W, int channels, const float* weight, int mode, void* out,
                       long ldo, void* stream) {
-    if (bad_dtype(dtype) || !x || !weight || !out || H < 1 || W < 1 || channels < 8 || (channels & 7) || channels > 4096 ||
+    if (!operand_dtype_ok(dtype) || !x || !weight || !out || H < 1 || W < 1 || channels < 8 || (channels & 7) || channels > 4096 ||
         (mode != 0 && mode != 1) || (mode == 1 && (channels & 15)))
-        return rfail(FW_ERR_INVALID, "fw_dwconv3x3_nhwc: bad argument");
-    return rguard([&] {
+        return invalid("fw_dwconv3x3_nhwc", "bad argument");
+    return guarded([&] {
         const int co = mode == 1 ? channels / 2 : channels;
         const int strips = (H + fw::DW_ROWS - 1) / fw::DW_ROWS;
         static const bool wide_on = [] {   // FW_REST_DW_WIDE=0: one kernel for all widths (A/B)
@@ -947,14 +918,14 @@ int fw_dwconv3x3_nhwc(int dtype, const void* x, long ldx, int H, int W, int chan
             }
             const dim3 grid((unsigned)(ncb * ngr), (unsigned)by);
             hipStream_t st = (hipStream_t)stream;
-#define FW_DWW(T, MO) hipLaunchKernelGGL((dwconv3x3_nhwc_wide_kernel<T, MO>), grid, dim3(256), 0, st, (const T*)x, ldx, H, W, channels, weight, (T*)out, ldo)
-            if (dtype == FW_DTYPE_BF16) { if (mode) FW_DWW(__bf16, 1); else FW_DWW(__bf16, 0); }
-            else { if (mode) FW_DWW(_Float16, 1); else FW_DWW(_Float16, 0); }
-#undef FW_DWW
+            with_operand_type((DType)dtype, [&](auto tag) {
+                using T = typename decltype(tag)::type;
+                hipLaunchKernelGGL((mode ? dwconv3x3_nhwc_wide_kernel<T, 1> : dwconv3x3_nhwc_wide_kernel<T, 0>), grid, dim3(256), 0, st, (const T*)x, ldx, H, W, channels, weight, (T*)out, ldo);
+            });
             FW_HIP_CHECK(hipGetLastError());
             return;
         }
-        const int bx = blocks_for((long)W * (co / 8), 1024);
+        const int bx = grid_1d((long)W * (co / 8), 1024);
         const int by_cap = 512 / bx > 0 ? 512 / bx : 1;   // one round of the 512 resident blocks: every block stages the filters in LDS first, so few fat blocks
         const dim3 blocks(bx, strips < by_cap ? strips : by_cap);
         const size_t smem = (size_t)9 * channels * sizeof(float);
@@ -968,10 +939,10 @@ int fw_dwconv3x3_nhwc(int dtype, const void* x, long ldx, int H, int W, int chan
         }();
         (void)attr;
         hipStream_t st = (hipStream_t)stream;
-#define FW_DW(T, MO) hipLaunchKernelGGL((dwconv3x3_nhwc_kernel<T, MO>), blocks, dim3(256), smem, st, (const T*)x, ldx, H, W, channels, weight, (T*)out, ldo)
-        if (dtype == FW_DTYPE_BF16) { if (mode) FW_DW(__bf16, 1); else FW_DW(__bf16, 0); }
-        else { if (mode) FW_DW(_Float16, 1); else FW_DW(_Float16, 0); }
-#undef FW_DW
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((mode ? dwconv3x3_nhwc_kernel<T, 1> : dwconv3x3_nhwc_kernel<T, 0>), blocks, dim3(256), smem, st, (const T*)x, ldx, H, W, channels, weight, (T*)out, ldo);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
@@ -984,18 +955,18 @@ size_t fw_attn_workspace_floats(int heads, int ch) {
 int fw_attn_matrix(int dtype, const void* qkv, long ld, long M, int k_off, int heads, int ch, const float* temperature,
                    float* workspace, float* attn, void* stream) {
     const int dim = heads * ch;
-    if (bad_dtype(dtype) || !qkv || !temperature || !workspace || !attn || M < 1 || heads < 1 || (ch != 48 && ch != 96) ||
+    if (!operand_dtype_ok(dtype) || !qkv || !temperature || !workspace || !attn || M < 1 || heads < 1 || (ch != 48 && ch != 96) ||
         dim > 512 || heads * (ch / 3) * (ch / 3) > 8 * 256 || (ld & 7) || (k_off & 7) || ((size_t)qkv & 15))
-        return rfail(FW_ERR_INVALID, "fw_attn_matrix: bad argument (16-byte aligned rows expected)");
-    return rguard([&] {
+        return invalid("fw_attn_matrix", "bad argument (16-byte aligned rows expected)");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const long chunks = (M + GRAM_PX - 1) / GRAM_PX;
         const int nb = (int)(chunks < GRAM_MAX_BLOCKS ? chunks : GRAM_MAX_BLOCKS);
         const size_t smem = (size_t)2 * GRAM_PX * dim * sizeof(float);
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((attn_gram_kernel<__bf16>), dim3(nb), dim3(256), smem, st, (const __bf16*)qkv, ld, M, k_off, heads, ch, workspace);
-        else
-            hipLaunchKernelGGL((attn_gram_kernel<_Float16>), dim3(nb), dim3(256), smem, st, (const _Float16*)qkv, ld, M, k_off, heads, ch, workspace);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((attn_gram_kernel<T>), dim3(nb), dim3(256), smem, st, (const T*)qkv, ld, M, k_off, heads, ch, workspace);
+        });
         const long stride = (long)dim * ch + 2 * dim;
         const int G = nb < 32 ? 1 : 32;
         if (G > 1)
@@ -1013,29 +984,24 @@ size_t fw_attn_qk_scratch_elems(long pixels, int heads, int ch) {
 int fw_attn_matrix_mfma(int dtype, const void* qkv, long ld, long M, int k_off, int heads, int ch, const float* temperature,
                         float* workspace, void* qk_scratch, float* attn, void* stream) {
     const int dim = heads * ch;
-    if (bad_dtype(dtype) || !qkv || !temperature || !workspace || !qk_scratch || !attn || M < 1 || heads < 1 || (ch != 48 && ch != 96) ||
+    if (!operand_dtype_ok(dtype) || !qkv || !temperature || !workspace || !qk_scratch || !attn || M < 1 || heads < 1 || (ch != 48 && ch != 96) ||
         dim > 512 || (ld & 7) || (k_off & 7) || ((size_t)qkv & 15) || ((size_t)qk_scratch & 15))
-        return rfail(FW_ERR_INVALID, "fw_attn_matrix_mfma: bad argument");
-    return rguard([&] {
+        return invalid("fw_attn_matrix_mfma", "bad argument");
+    return guarded([&] {
         hipStream_t st = (hipStream_t)stream;
         const long Mp = (M + 31) / 32 * 32;
         const long steps = Mp / 32;
         long nbl = steps / 8;
         const int nb = (int)(nbl < 1 ? 1 : (nbl > GRAM_MAX_BLOCKS ? GRAM_MAX_BLOCKS : nbl));
-        const int tb = blocks_for((Mp / 8) * (dim / 8) * 2, 2048);
+        const int tb = grid_1d((Mp / 8) * (dim / 8) * 2, 2048);
         const size_t half = (size_t)Mp * dim;
-#define FW_GM(T)                                                                                                              \
-    do {                                                                                                                      \
-        T* qT = (T*)qk_scratch;                                                                                               \
-        T* kT = qT + half;                                                                                                    \
-        hipLaunchKernelGGL((qk_transpose_kernel<T>), dim3(tb), dim3(256), 0, st, (const T*)qkv, ld, M, Mp, k_off, dim, qT, kT); \
-        if (ch == 48)                                                                                                         \
-            hipLaunchKernelGGL((attn_gram_mfma_kernel<T, 3>), dim3(nb, heads), dim3(256), 0, st, (const T*)qT, (const T*)kT, Mp, heads, dim, workspace); \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((attn_gram_mfma_kernel<T, 6>), dim3(nb, heads), dim3(256), 0, st, (const T*)qT, (const T*)kT, Mp, heads, dim, workspace); \
-    } while (0)
-        if (dtype == FW_DTYPE_BF16) FW_GM(__bf16); else FW_GM(_Float16);
-#undef FW_GM
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            T* qT = (T*)qk_scratch;
+            T* kT = qT + half;
+            hipLaunchKernelGGL((qk_transpose_kernel<T>), dim3(tb), dim3(256), 0, st, (const T*)qkv, ld, M, Mp, k_off, dim, qT, kT);
+            hipLaunchKernelGGL((ch == 48 ? attn_gram_mfma_kernel<T, 3> : attn_gram_mfma_kernel<T, 6>), dim3(nb, heads), dim3(256), 0, st, (const T*)qT, (const T*)kT, Mp, heads, dim, workspace);
+        });
         const long stride = (long)dim * ch + 2 * dim;
         const int G = nb < 32 ? 1 : 32;
         if (G > 1)
@@ -1058,15 +1024,10 @@ void launch_attn_matrix_from_transposed(DType dt, const void* qT, const void* kT
     const long steps = Mp / 32;
     const long nbl = steps / 8;
     const int nb = (int)(nbl < 1 ? 1 : (nbl > GRAM_MAX_BLOCKS ? GRAM_MAX_BLOCKS : nbl));
-#define FW_GM(T)                                                                                                                        \
-    do {                                                                                                                                \
-        if (ch == 48)                                                                                                                   \
-            hipLaunchKernelGGL((attn_gram_mfma_kernel<T, 3>), dim3(nb, heads), dim3(256), 0, st, (const T*)qT, (const T*)kT, Mp, heads, ldc, workspace); \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((attn_gram_mfma_kernel<T, 6>), dim3(nb, heads), dim3(256), 0, st, (const T*)qT, (const T*)kT, Mp, heads, ldc, workspace); \
-    } while (0)
-    if (dt == DT_BF16) FW_GM(__bf16); else FW_GM(_Float16);
-#undef FW_GM
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((ch == 48 ? attn_gram_mfma_kernel<T, 3> : attn_gram_mfma_kernel<T, 6>), dim3(nb, heads), dim3(256), 0, st, (const T*)qT, (const T*)kT, Mp, heads, ldc, workspace);
+    });
     const long stride = (long)dim * ch + 2 * dim;
     const int G = nb < 32 ? 1 : 32;
     if (G > 1) hipLaunchKernelGGL(attn_reduce_kernel, dim3((unsigned)((stride + 255) / 256), G), dim3(256), 0, st, workspace, nb, stride, G);
@@ -1077,33 +1038,31 @@ void launch_attn_matrix_from_transposed(DType dt, const void* qT, const void* kT
 extern "C" {
 
 int fw_attn_pack(int dtype, const float* attn, int heads, int ch, int k_pad, void* packed, void* stream) {
-    if (bad_dtype(dtype) || !attn || !packed || heads < 1 || ch < 8 || k_pad < heads * ch || (k_pad & 31))
-        return rfail(FW_ERR_INVALID, "fw_attn_pack: bad argument");
-    return rguard([&] {
+    if (!operand_dtype_ok(dtype) || !attn || !packed || heads < 1 || ch < 8 || k_pad < heads * ch || (k_pad & 31))
+        return invalid("fw_attn_pack", "bad argument");
+    return guarded([&] {
         const long total = (long)(k_pad / 32) * 2 * (k_pad / 32) * 64 * 8;
-        const int blocks = blocks_for(total, 1024);
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((attn_pack_kernel<__bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, attn, heads, ch, k_pad, (__bf16*)packed);
-        else
-            hipLaunchKernelGGL((attn_pack_kernel<_Float16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, attn, heads, ch, k_pad, (_Float16*)packed);
+        const int blocks = grid_1d(total, 1024);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((attn_pack_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, attn, heads, ch, k_pad, (T*)packed);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
 
 int fw_attn_proj_pack(int dtype, const float* attn, const float* proj_weight, int heads, int ch, int k_pad, int cout_tiles, void* packed,
                       void* stream) {
-    if (bad_dtype(dtype) || !attn || !proj_weight || !packed || heads < 1 || ch < 8 || k_pad < heads * ch || (k_pad & 31) || cout_tiles < 1 ||
+    if (!operand_dtype_ok(dtype) || !attn || !proj_weight || !packed || heads < 1 || ch < 8 || k_pad < heads * ch || (k_pad & 31) || cout_tiles < 1 ||
         32 * cout_tiles < heads * ch)
-        return rfail(FW_ERR_INVALID, "fw_attn_proj_pack: bad argument");
-    return rguard([&] {
+        return invalid("fw_attn_proj_pack", "bad argument");
+    return guarded([&] {
         const long total = (long)(k_pad / 32) * 2 * cout_tiles * 64 * 8;
-        const int blocks = blocks_for(total, 1024);
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((attn_proj_pack_kernel<__bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, attn, proj_weight, heads, ch, k_pad,
-                               cout_tiles, (__bf16*)packed);
-        else
-            hipLaunchKernelGGL((attn_proj_pack_kernel<_Float16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, attn, proj_weight, heads, ch, k_pad,
-                               cout_tiles, (_Float16*)packed);
+        const int blocks = grid_1d(total, 1024);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((attn_proj_pack_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, attn, proj_weight, heads, ch, k_pad, cout_tiles, (T*)packed);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
@@ -1111,9 +1070,9 @@ int fw_attn_proj_pack(int dtype, const float* attn, const float* proj_weight, in
 int fw_attn_apply(int dtype, const void* qkv, long ld, long M, int v_off, int heads, int ch, const float* attn, void* out,
                   long ldo, int zero_to, void* stream) {
     const int dim = heads * ch;
-    if (bad_dtype(dtype) || !qkv || !attn || !out || M < 1 || (ch & 7) || (zero_to & 7) || zero_to < dim || zero_to > ldo)
-        return rfail(FW_ERR_INVALID, "fw_attn_apply: bad argument");
-    return rguard([&] {
+    if (!operand_dtype_ok(dtype) || !qkv || !attn || !out || M < 1 || (ch & 7) || (zero_to & 7) || zero_to < dim || zero_to > ldo)
+        return invalid("fw_attn_apply", "bad argument");
+    return guarded([&] {
         const size_t smem = (size_t)dim * ch * sizeof(float);
         static const bool attr = [] {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_apply_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
@@ -1121,55 +1080,51 @@ int fw_attn_apply(int dtype, const void* qkv, long ld, long M, int v_off, int he
             return true;
         }();
         (void)attr;
-        const int blocks = blocks_for(M * (zero_to / 8), 2048);
+        const int blocks = grid_1d(M * (zero_to / 8), 2048);
         hipStream_t st = (hipStream_t)stream;
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((attn_apply_kernel<__bf16>), dim3(blocks), dim3(256), smem, st, (const __bf16*)qkv, ld, M, v_off, heads, ch, attn, (__bf16*)out, ldo, zero_to);
-        else
-            hipLaunchKernelGGL((attn_apply_kernel<_Float16>), dim3(blocks), dim3(256), smem, st, (const _Float16*)qkv, ld, M, v_off, heads, ch, attn, (_Float16*)out, ldo, zero_to);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((attn_apply_kernel<T>), dim3(blocks), dim3(256), smem, st, (const T*)qkv, ld, M, v_off, heads, ch, attn, (T*)out, ldo, zero_to);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
 
 int fw_attn_softmax_rows(int dtype, const void* q, long q_stride, const void* k, long k_stride, long pixels, int d, void* p,
                          long p_stride, void* stream) {
-    if (bad_dtype(dtype) || !q || !k || !p || pixels < 1 || d < 1 || d > 8 || (q_stride & 7) || (k_stride & 7) || p_stride < pixels ||
+    if (!operand_dtype_ok(dtype) || !q || !k || !p || pixels < 1 || d < 1 || d > 8 || (q_stride & 7) || (k_stride & 7) || p_stride < pixels ||
         ((size_t)q & 15) || ((size_t)k & 15))
-        return rfail(FW_ERR_INVALID, "fw_attn_softmax_rows: bad argument");
-    return rguard([&] {
-        const int blocks = blocks_for(pixels * 64, 2048);
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((attn_softmax_rows_kernel<__bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)q, q_stride,
-                               (const __bf16*)k, k_stride, pixels, d, (__bf16*)p, p_stride);
-        else
-            hipLaunchKernelGGL((attn_softmax_rows_kernel<_Float16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16*)q,
-                               q_stride, (const _Float16*)k, k_stride, pixels, d, (_Float16*)p, p_stride);
+        return invalid("fw_attn_softmax_rows", "bad argument");
+    return guarded([&] {
+        const int blocks = grid_1d(pixels * 64, 2048);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((attn_softmax_rows_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)q, q_stride, (const T*)k, k_stride, pixels, d, (T*)p, p_stride);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
 
 int fw_pack_pointwise_transposed(int dtype, const void* src, long src_stride, long k_valid, int cout, int k_pad, void* packed,
                                  void* stream) {
-    if (bad_dtype(dtype) || !src || !packed || k_valid < 1 || cout < 1 || k_pad < k_valid || (k_pad & 31))
-        return rfail(FW_ERR_INVALID, "fw_pack_pointwise_transposed: bad argument");
-    return rguard([&] {
+    if (!operand_dtype_ok(dtype) || !src || !packed || k_valid < 1 || cout < 1 || k_pad < k_valid || (k_pad & 31))
+        return invalid("fw_pack_pointwise_transposed", "bad argument");
+    return guarded([&] {
         const long total = (long)(k_pad / 32) * 2 * ((cout + 31) / 32) * 64;
-        const int blocks = blocks_for(total, 2048);
-        if (dtype == FW_DTYPE_BF16)
-            hipLaunchKernelGGL((pack_pointwise_t_kernel<__bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16*)src,
-                               src_stride, k_valid, cout, k_pad, (__bf16*)packed);
-        else
-            hipLaunchKernelGGL((pack_pointwise_t_kernel<_Float16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16*)src,
-                               src_stride, k_valid, cout, k_pad, (_Float16*)packed);
+        const int blocks = grid_1d(total, 2048);
+        with_operand_type((DType)dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL((pack_pointwise_t_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)src, src_stride, k_valid, cout, k_pad, (T*)packed);
+        });
         FW_HIP_CHECK(hipGetLastError());
     });
 }
 
 int fw_pixel_shuffle2_f32(const float* src, long src_stride, int low_h, int low_w, int channels, float* dst, long dst_stride,
                           int dst_coff, int unshuffle, void* stream) {
-    if (!src || !dst || low_h < 1 || low_w < 1 || channels < 1) return rfail(FW_ERR_INVALID, "fw_pixel_shuffle2_f32: bad argument");
-    return rguard([&] {
-        const int blocks = blocks_for((long)low_h * low_w * channels * 4, 4096);
+    if (!src || !dst || low_h < 1 || low_w < 1 || channels < 1) return invalid("fw_pixel_shuffle2_f32", "bad argument");
+    return guarded([&] {
+        const int blocks = grid_1d((long)low_h * low_w * channels * 4, 4096);
         hipLaunchKernelGGL(pixel_shuffle2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, src_stride, low_h, low_w,
                            channels, dst, dst_stride, dst_coff, unshuffle);
         FW_HIP_CHECK(hipGetLastError());
@@ -1178,33 +1133,33 @@ int fw_pixel_shuffle2_f32(const float* src, long src_stride, int low_h, int low_
 
 int fw_copy_channels_f32(const float* src, long src_stride, long M, int channels, float* dst, long dst_stride, int dst_coff,
                          void* stream) {
-    if (!src || !dst || M < 1 || channels < 1) return rfail(FW_ERR_INVALID, "fw_copy_channels_f32: bad argument");
-    return rguard([&] {
-        hipLaunchKernelGGL(copy_channels_kernel, dim3(blocks_for(M * channels, 4096)), dim3(256), 0, (hipStream_t)stream, src,
+    if (!src || !dst || M < 1 || channels < 1) return invalid("fw_copy_channels_f32", "bad argument");
+    return guarded([&] {
+        hipLaunchKernelGGL(copy_channels_kernel, dim3(grid_1d(M * channels, 4096)), dim3(256), 0, (hipStream_t)stream, src,
                            src_stride, M, channels, dst, dst_stride, dst_coff);
         FW_HIP_CHECK(hipGetLastError());
     });
 }
 
 int fw_f32_to_planar(int dtype, const float* x, long M, int channels, void* out, void* stream) {
-    if (bad_dtype(dtype) || !x || !out || M < 1 || channels < 32 || (channels & 31))
-        return rfail(FW_ERR_INVALID, "fw_f32_to_planar: bad argument");
-    return rguard([&] { launch_f32_to_planar((DType)dtype, x, M, channels, out, (hipStream_t)stream); });
+    if (!operand_dtype_ok(dtype) || !x || !out || M < 1 || channels < 32 || (channels & 31))
+        return invalid("fw_f32_to_planar", "bad argument");
+    return guarded([&] { launch_f32_to_planar((DType)dtype, x, M, channels, out, (hipStream_t)stream); });
 }
 
 int fw_tap_post_u8(const uint8_t* in_bgr, const float* rgb, int H, int W, int padded_w, int rgb_cstride, uint8_t* out_bgr,
                    float* out_rgb_f32, void* stream) {
     if (!in_bgr || !rgb || (!out_bgr && !out_rgb_f32) || H < 1 || W < 1 || rgb_cstride < 3)
-        return rfail(FW_ERR_INVALID, "fw_tap_post_u8: bad argument");
-    return rguard([&] { launch_tap_post(in_bgr, rgb, H, W, padded_w, rgb_cstride, out_bgr, out_rgb_f32, (hipStream_t)stream); });
+        return invalid("fw_tap_post_u8", "bad argument");
+    return guarded([&] { launch_tap_post(in_bgr, rgb, H, W, padded_w, rgb_cstride, out_bgr, out_rgb_f32, (hipStream_t)stream); });
 }
 
 int fw_flow_accumulate_u8(const uint8_t* frame_bgr, const float* flow_x, const float* flow_y, const float* weight_map,
                           double weight_scale, const float* magnitude, float motion_threshold, int inverse, int H, int W,
                           double* accumulated, double* weight_sum, void* stream) {
     if (!frame_bgr || !accumulated || !weight_sum || H < 1 || W < 1 || (!flow_x != !flow_y))
-        return rfail(FW_ERR_INVALID, "fw_flow_accumulate_u8: bad argument");
-    return rguard([&] {
+        return invalid("fw_flow_accumulate_u8", "bad argument");
+    return guarded([&] {
         launch_flow_accumulate(frame_bgr, flow_x, flow_y, weight_map, weight_scale, magnitude, motion_threshold, inverse, H, W,
                                accumulated, weight_sum, (hipStream_t)stream);
     });
@@ -1212,8 +1167,8 @@ int fw_flow_accumulate_u8(const uint8_t* frame_bgr, const float* flow_x, const f
 
 int fw_flow_accumulate_finish_u8(const double* accumulated, const double* weight_sum, int H, int W, uint8_t* out_bgr,
                                  void* stream) {
-    if (!accumulated || !weight_sum || !out_bgr || H < 1 || W < 1) return rfail(FW_ERR_INVALID, "fw_flow_accumulate_finish_u8: bad argument");
-    return rguard([&] { launch_flow_accumulate_finish(accumulated, weight_sum, (long)H * W, out_bgr, (hipStream_t)stream); });
+    if (!accumulated || !weight_sum || !out_bgr || H < 1 || W < 1) return invalid("fw_flow_accumulate_finish_u8", "bad argument");
+    return guarded([&] { launch_flow_accumulate_finish(accumulated, weight_sum, (long)H * W, out_bgr, (hipStream_t)stream); });
 }
 
 }  // extern "C"
