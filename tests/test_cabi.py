@@ -82,7 +82,7 @@ def test_pack_rejects_bad_shapes(hip_lib):
 def test_phase_weight_packing_matches_its_fragment_map(hip_lib, dtype):
     """fw_pack_conv_up2x_phase: [row phase a][chunk c][step (tx, r, b) in use order][16-channel tile][lane][j] of the summed
     2x2 phase kernels of nearest-x2 + conv3x3 (csrc/conv_up2x_phase.hip), sums in fp64, rounded once."""
-    import torch
+    from conv_pair_ref import rnd64, to_bits
     rng = np.random.default_rng(7)
     w = rng.standard_normal((64, 64, 3, 3)).astype(np.float32)
     n = hip_lib.fw_pack_conv_up2x_phase(dtype, None, None)
@@ -94,11 +94,12 @@ def test_phase_weight_packing_matches_its_fragment_map(hip_lib, dtype):
     steps = [(0, 0, 0), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1), (2, 0, 1), (2, 1, 1)]   # (tx, r, b); column tap = tx - b
     want = np.empty((2, 2, 8, 4, 64, 8), np.uint16)
     lane = np.arange(64)
-    tdt = torch.bfloat16 if dtype == _lib.FW_DTYPE_BF16 else torch.float16
+    name = "bf16" if dtype == _lib.FW_DTYPE_BF16 else "f16"
     for a in range(2):
         for si, (tx, r, b) in enumerate(steps):
-            ws = w.astype(np.float64)[:, :, fold[a][r]][:, :, :, fold[b][tx - b]].sum(axis=(2, 3)).astype(np.float32)
-            bits = torch.from_numpy(ws).to(tdt).view(torch.int16).numpy().view(np.uint16)
+            ws = w.astype(np.float64)[:, :, fold[a][r]][:, :, :, fold[b][tx - b]].sum(axis=(2, 3))
+            # ONE rounding of the fp64 sum (through fp32 first, as this test once did, a sum that fp32 puts on a tie goes the wrong way)
+            bits = to_bits(rnd64(ws, name), name).reshape(64, 64)
             for c in range(2):
                 for wt in range(4):
                     co = 16 * wt + (lane & 15)

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from framewright_amd import _lib
+from conv_pair_ref import phase_weights_ref as _phase_weights_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -121,20 +122,6 @@ def test_conv_upsample2x(hip_lib, dtype):
     _, out_f32 = _run(hip_lib, dtype, x, 64, w, b, 2 * h, 2 * w_, act=1, ups=1, want_f32=True)
     ref = _ref(dtype, x, 64, w, b, act=1, ups=1)
     assert (out_f32 - ref).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
-
-
-def _phase_weights_ref(w):
-    """The four 2x2 phase kernels of nearest-x2 + conv3x3 (csrc/conv_up2x_phase.hip): phase 0 folds taps {0} / {1, 2} onto source
-    offsets 0 / 1, phase 1 folds {0, 1} / {2}.  Returns [a][b][cout][cin][2][2] in fp64."""
-    fold = {0: ([0], [1, 2]), 1: ([0, 1], [2])}
-    w = w.astype(np.float64)
-    out = np.zeros((2, 2) + w.shape[:2] + (2, 2))
-    for a in range(2):
-        for b in range(2):
-            for r in range(2):
-                for s in range(2):
-                    out[a, b, :, :, r, s] = w[:, :, fold[a][r]][:, :, :, fold[b][s]].sum(axis=(2, 3))
-    return out
 
 
 @pytest.mark.parametrize("dtype", [_lib.FW_DTYPE_BF16, _lib.FW_DTYPE_F16])

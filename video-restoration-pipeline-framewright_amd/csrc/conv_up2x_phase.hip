@@ -21,7 +21,9 @@
 // so that stage c holds chunk c, a stage's refill for the next tile goes out right after its last use and every DMA is issued
 // one item ahead of its use (the chunk read last in a tile is read first in the next one).  Weights: 32 fragments (32 KiB) per
 // item, double-buffered.  LDS: 2 x 40 KiB + 2 x 32 KiB = 144 KiB.
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "fw_internal.h"
 #include "conv_common.h"
@@ -300,6 +302,20 @@ void launch_conv_up2x_phase(DType dt, const ConvUpParams& p_in, hipStream_t stre
     FW_HIP_CHECK(hipGetLastError());
 }
 
+// fp64 -> fp32 rounded to ODD: truncated towards zero, the last bit set if anything was lost.  The RNE cast to an operand type that
+// follows drops 13 bits or more, the sticky bit among them, and so rounds the fp64 value ONCE (through a plain (float) cast a sum that
+// fp32 rounds onto a tie of the operand type went the wrong way: 7 of the 65536 f16 weights of a random conv_up were one ulp off).
+static float f64_to_f32_odd(double v) {
+    float f = (float)v;
+    if ((double)f == v || f != f) return f;
+    if (fabs((double)f) > fabs(v)) f = nextafterf(f, 0.0f);
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    u |= 1u;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
 // Fragment order: [row phase a][chunk c][step s = (tx, r, b) in use order][16-channel tile w][lane][j]; value = the sum of
 // w[cout][cin][dy][dx] over the taps that phase (a, b) folds onto source offset (r, s_col = tx - b):
 //   phase 0: tap 0 -> offset 0, taps 1, 2 -> offset 1;  phase 1: taps 0, 1 -> offset 0, tap 2 -> offset 1.
@@ -331,7 +347,7 @@ size_t pack_conv_up2x_phase_weights(DType dt, const float* w, uint16_t* dst) {
                             double v = 0.0;
                             for (int dy = y_lo; dy <= y_hi; ++dy)
                                 for (int dx = x_lo; dx <= x_hi; ++dx) v += (double)w[((size_t)co * 64 + ci) * 9 + dy * 3 + dx];
-                            dst[o++] = f32_to_operand(dt, (float)v);
+                            dst[o++] = f32_to_operand(dt, f64_to_f32_odd(v));
                         }
             }
     return n;

@@ -750,7 +750,10 @@ int fw_conv3x3_pair_nhwc(int dtype, const void* x, int in_cstride, long in_plane
         q.out_a = out_a;
         q.out_b = out_b;
         q.out_cstride = out_cstride;
-        if (q.in_pstride == 32 && in_cstride < 32 * in_chunks) throw Error(FW_ERR_INVALID, "fw_conv3x3_pair_nhwc: input too narrow");
+        // (a single pixel: the chunk-planar layout's plane stride H * W * 32 IS 32 and in_cstride addresses nothing, as in
+        // launch_conv_up2x_phase)
+        if (q.in_pstride == 32 && in_cstride < 32 * in_chunks && (long)H * W > 1)
+            throw Error(FW_ERR_INVALID, "fw_conv3x3_pair_nhwc: input too narrow");
         launch_conv3x3_pair((DType)dtype, q, (hipStream_t)stream);
     });
 }
