@@ -19,6 +19,110 @@ def test_header_and_binding_agree():
     assert _header_symbols() == sorted(_lib.EXPORTS)
 
 
+I32, I64, F32, F64, SZ, VP = C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t, C.c_void_p
+_NET = "typedef struct fw_net fw_net;\n"
+# one literal header per mapping rule of _lib._read_header: (text, host-array table, [(name, restype, argtypes)])
+READER_CASES = {
+    "scalars": ("int fw_a(int a, long b, float c, double d, size_t e, unsigned f, int64_t g, uint64_t h);\n"
+                "size_t fw_b(void);\ndouble fw_c();\nlong fw_d(const int n);", {},
+                [("fw_a", I32, [I32, I64, F32, F64, SZ, C.c_uint, C.c_int64, C.c_uint64]), ("fw_b", SZ, []), ("fw_c", F64, []),
+                 ("fw_d", I64, [I32])]),
+    "const_char": ("const char* fw_a(const char* key, const char *other);", {}, [("fw_a", C.c_char_p, [C.c_char_p, C.c_char_p])]),
+    "int_long_pointers": ("int fw_a(int* a, const int* b, long* c, const long* d);", {},
+                          [("fw_a", I32, [C.POINTER(I32), C.POINTER(I32), C.POINTER(I64), C.POINTER(I64)])]),
+    "pointer_to_pointer": (_NET + "int fw_a(fw_net** out, const uint8_t* const* frames, float** rows);", {},
+                           [("fw_a", I32, [C.POINTER(VP)] * 3)]),
+    "other_pointers": (_NET + "typedef struct fw_p {\n    float m[9];\n    int32_t a, b; /* fw_x(1) */\n} fw_p;\n"
+                       "int fw_a(fw_net* h, const fw_net* g, void* a, void** b, const void* const* c, const uint8_t* d, uint16_t* e,\n"
+                       "         const int32_t* f, float* p, const double* q, const fw_p* r, char* buf, int64_t* s);", {},
+                       [("fw_a", I32, [VP] * 13)]),
+    "host_array_table": ("int fw_a(const float* weights, const float* other, double* total);\nint fw_b(const float* weights);",
+                         {("fw_a", "weights"): C.POINTER(F32), ("fw_a", "total"): C.POINTER(F64)},
+                         [("fw_a", I32, [C.POINTER(F32), VP, C.POINTER(F64)]), ("fw_b", I32, [VP])]),
+    "three_lines": ("int fw_a(int dtype,\n         const void* x,   /* device */\n         long stride);\nint\nfw_b\n(void);", {},
+                    [("fw_a", I32, [I32, VP, I64]), ("fw_b", I32, [])]),
+    "comments": ("/* call fw_x(1) first;\n * then fw_y(2, 3); */\n// or int fw_w(int a);\nint fw_z(void); /* int fw_v(void); */", {},
+                 [("fw_z", I32, [])]),
+    "preprocessor": ('#ifndef FW_H\n#define FW_H\n#include <stddef.h>\n#ifdef __cplusplus\nextern "C" {\n#endif\n#define FW_A 3\n'
+                     "int fw_a(void);\n  #define FW_CALL(x) fw_x(x)\n#ifdef __cplusplus\n}\n#endif\n#endif", {}, [("fw_a", I32, [])]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(READER_CASES))
+def test_reader_maps_each_rule(case):
+    text, table, want = READER_CASES[case]
+    got = _lib._read_header(text, table)
+    assert [g[0] for g in got] == [w[0] for w in want]
+    for (name, restype, argtypes), (_, want_res, want_args) in zip(got, want):
+        assert restype is want_res, name
+        assert len(argtypes) == len(want_args) and all(a is b for a, b in zip(argtypes, want_args)), (name, argtypes)
+
+
+@pytest.mark.parametrize("text,names", [
+    ("int fw_ok(int a);\nint fw_bad(flaot x);", ("fw_bad", "flaot")),              # an unknown scalar
+    ("int fw_bad(flaot* x);", ("fw_bad", "flaot")),                                # an unknown pointee is not a void* either
+    ("int fw_bad(unsigned int x);", ("fw_bad", "unsigned int x")),                 # two-word types are not guessed at
+    ("void fw_bad(int x);", ("fw_bad", "void")),
+    ("int fw_bad(int*** x);", ("fw_bad", "x")),
+    ("int fw_bad(float m[9]);", ("fw_bad", "m[9]")),
+    ("int fw_bad(int (*cb)(int));", ("fw_bad",)),
+    ("int fw_bad(int);", ("fw_bad",)),                                             # a parameter without a name
+    ("int fw_ok(void);\nint fw_bad;", ("fw_bad", "not a prototype")),
+])
+def test_reader_refuses_what_it_does_not_know(text, names):
+    with pytest.raises(_lib.FramewrightHipError) as e:
+        _lib._read_header(text, {})
+    assert e.value.code == _lib.FW_ERR_INTERNAL
+    assert all(n in str(e.value) for n in names)
+
+
+@pytest.mark.parametrize("key", [("fw_a", "wieghts"), ("fw_missing", "weights")])
+def test_reader_refuses_a_table_key_the_header_lacks(key):
+    with pytest.raises(_lib.FramewrightHipError) as e:
+        _lib._read_header("int fw_a(const float* weights);", {key: C.POINTER(F32)})
+    assert e.value.code == _lib.FW_ERR_INTERNAL and key[0] in str(e.value) and key[1] in str(e.value)
+
+
+def test_constants_are_the_headers_defines():
+    assert (_lib.FW_OK, _lib.FW_ERR_INVALID, _lib.FW_ERR_OOM, _lib.FW_ERR_HIP, _lib.FW_ERR_INTERNAL) == (0, 1, 2, 3, 4)
+    assert (_lib.FW_HOST, _lib.FW_DEVICE, _lib.FW_DTYPE_BF16, _lib.FW_DTYPE_F16) == (0, 1, 0, 1)
+    assert (_lib.FW_NAF_PATH_FRONT, _lib.FW_NAF_PATH_TAIL128, _lib.FW_NAF_PATH_TAIL64, _lib.FW_NAF_PATH_GEMM,
+            _lib.FW_NAF_PATH_FUSE_LN) == (1, 2, 4, 8, 16)
+    assert (_lib.FW_REST_PATH_FRONT_QKV, _lib.FW_REST_PATH_FRONT_FFN, _lib.FW_REST_PATH_QK_DIRECT, _lib.FW_REST_PATH_MERGE_PROJ,
+            _lib.FW_REST_PATH_GEMM16) == (1, 2, 4, 8, 16)
+
+
+# full signatures written out by hand from the header's prototypes, not derived by the reader
+PINNED = {
+    "fw_last_error": (C.c_char_p, []),
+    "fw_rrdbnet_create": (I32, [I32, I32, I32, I32, C.POINTER(VP)]),
+    "fw_rrdbnet_workspace_bytes": (SZ, [VP, I32, I32]),
+    "fw_rrdbnet_profile_read": (I32, [VP, C.POINTER(I32), C.POINTER(F64), C.POINTER(F64)]),
+    "fw_conv3x3_nhwc": (I32, [I32, VP, I32, I64, I32, I32, I32, VP, VP, I32, I32, I32, VP, F32, VP, F32, VP, I32, I64, I32, VP, VP]),
+    "fw_conv3x3_split_nhwc": (I32, [I32, I32, VP, I32, I64, I32, I32, I32, VP, VP, F32, F32, I32, C.POINTER(I64), C.POINTER(F32), I32,
+                                    VP, VP, I32, I64, I32, VP]),
+    "fw_temporal_average_u8": (I32, [C.POINTER(VP), C.POINTER(F32), I32, SZ, VP, VP]),
+    "fw_hdr_convert": (I32, [VP, VP, I32, I32, I32, I32, VP, VP, VP, VP, VP, VP]),
+    "fw_qp_artifacts_u8": (I32, [VP, VP, I32, I32, I32, I32, VP, VP, VP, F64, I32, I32, VP, VP, C.c_uint64, VP, VP]),
+    "fw_unsharp_mask_u8": (I32, [VP, I32, I32, I32, I32, C.c_uint, C.c_uint, I32, I32, I32, VP, VP, VP, VP]),
+}
+
+
+def test_pinned_signatures():
+    table = {name: (restype, argtypes) for name, restype, argtypes in _lib._SIGNATURES}
+    assert len(table) == len(_lib.EXPORTS)      # no name twice
+    for name, (restype, argtypes) in PINNED.items():
+        got_res, got_args = table[name]
+        assert got_res is restype, name
+        assert len(got_args) == len(argtypes) and all(a is b for a, b in zip(got_args, argtypes)), (name, got_args)
+
+
+def test_loaded_library_carries_the_readers_signatures(hip_lib):
+    for name, restype, argtypes in _lib._SIGNATURES:
+        fn = getattr(hip_lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
 def test_library_exports_every_declared_symbol(hip_lib):
     for name in _header_symbols():
         assert hasattr(hip_lib, name), f"{name} declared in the header but not exported"

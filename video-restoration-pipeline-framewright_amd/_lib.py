@@ -6,65 +6,14 @@ CPU fallback on this path.
 from __future__ import annotations
 
 import ctypes as C
+import re
 import threading
 from pathlib import Path
 from typing import Optional
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / "lib" / "libframewright_hip.so"
-
-FW_OK, FW_ERR_INVALID, FW_ERR_OOM, FW_ERR_HIP, FW_ERR_INTERNAL = 0, 1, 2, 3, 4
-FW_HOST, FW_DEVICE = 0, 1
-FW_DTYPE_BF16, FW_DTYPE_F16 = 0, 1
-FW_NAF_PATH_FRONT, FW_NAF_PATH_TAIL128, FW_NAF_PATH_TAIL64, FW_NAF_PATH_GEMM, FW_NAF_PATH_FUSE_LN = 1, 2, 4, 8, 16
-FW_REST_PATH_FRONT_QKV, FW_REST_PATH_FRONT_FFN, FW_REST_PATH_QK_DIRECT, FW_REST_PATH_MERGE_PROJ, FW_REST_PATH_GEMM16 = 1, 2, 4, 8, 16
-DTYPES = {"bf16": FW_DTYPE_BF16, "bfloat16": FW_DTYPE_BF16, "f16": FW_DTYPE_F16, "fp16": FW_DTYPE_F16,
-          "float16": FW_DTYPE_F16, "half": FW_DTYPE_F16}
-
-# every symbol include/framewright_hip.h declares (tests/test_cabi.py checks the header against this list)
-EXPORTS = [
-    "fw_last_error", "fw_abi_version", "fw_device_count",
-    "fw_rrdbnet_create", "fw_rrdbnet_set_conv", "fw_rrdbnet_finalize", "fw_rrdbnet_upscale_u8", "fw_rrdbnet_upscale_u16",
-    "fw_rrdbnet_workspace_bytes", "fw_rrdbnet_flops", "fw_rrdbnet_profile_enable", "fw_rrdbnet_profile_read",
-    "fw_rrdbnet_destroy", "fw_pack_conv3x3", "fw_conv3x3_nhwc",
-    "fw_nafnet_create", "fw_nafnet_set_tensor", "fw_nafnet_finalize", "fw_nafnet_denoise_u8", "fw_nafnet_flops",
-    "fw_nafnet_destroy", "fw_nafnet_run_block", "fw_nafnet_block_paths", "fw_nafnet_run_resample", "fw_u8_to_nhwc_padded", "fw_u8_crop", "fw_tile_blend_accumulate", "fw_tile_blend_finish", "fw_temporal_average_u8",
-    "fw_strength_blend_u8",
-    "fw_conv3x3_nhwc_ex", "fw_conv3x3_pair_nhwc", "fw_pack_conv_up2x_phase", "fw_conv_up2x_phase_nhwc", "fw_u8_to_rgb_f32", "fw_resize_bilinear_f32", "fw_ifnet_build_x", "fw_unshuffle2_cast",
-    "fw_depth_to_space4_f32", "fw_ifnet_accumulate", "fw_ifnet_blend", "fw_unsharp_mask_u8",
-    "fw_ifnet_stage_input", "fw_ifnet_accumulate_d2s", "fw_ifnet_last_flow",
-    "fw_ifnet_create", "fw_ifnet_set_tensor", "fw_ifnet_finalize", "fw_ifnet_interp_u8", "fw_ifnet_workspace_bytes", "fw_ifnet_flops",
-    "fw_ifnet_destroy",
-    "fw_aesrgan_create", "fw_aesrgan_set_tensor", "fw_aesrgan_finalize", "fw_aesrgan_forward_rgb", "fw_aesrgan_workspace_bytes", "fw_aesrgan_destroy",
-    "fw_srvgg_create", "fw_srvgg_set_tensor", "fw_srvgg_finalize", "fw_srvgg_upscale_u8", "fw_srvgg_upscale_u16", "fw_resize_lanczos4_u16", "fw_srvgg_workspace_bytes", "fw_srvgg_flops",
-    "fw_srvgg_destroy",
-    "fw_restormer_create", "fw_restormer_set_tensor", "fw_restormer_finalize", "fw_restormer_denoise_u8",
-    "fw_restormer_workspace_bytes", "fw_restormer_destroy", "fw_restormer_run_block", "fw_restormer_block_paths", "fw_restormer_run_step", "fw_preserve_edges_scratch_bytes", "fw_preserve_edges_u8",
-    "fw_u8_to_nhwc", "fw_pixel_shuffle_add_u8",
-    "fw_layernorm_nhwc", "fw_pack_pointwise", "fw_pointwise_nhwc", "fw_dwconv3x3_nhwc", "fw_attn_workspace_floats",
-    "fw_attn_matrix", "fw_attn_apply", "fw_attn_pack", "fw_attn_proj_pack", "fw_pixel_shuffle2_f32", "fw_copy_channels_f32", "fw_f32_to_planar", "fw_tap_post_u8",
-    "fw_flow_accumulate_u8", "fw_flow_accumulate_finish_u8", "fw_resize_lanczos4_u8", "fw_resize_linear_u8", "fw_face_paste_u8", "fw_grain_addback_u8", "fw_attn_softmax_rows", "fw_pack_pointwise_transposed", "fw_attn_qk_scratch_elems", "fw_attn_matrix_mfma",
-    "fw_pack_conv3x3_wino", "fw_conv3x3_split_nhwc", "fw_conv3x3_wino_nhwc", "fw_conv3x3_wino_check_fields",
-    "fw_pack_conv_last_pointwise", "fw_conv3x3_hr_last_nhwc",
-    # csrc/aspect.hip.  In front of fw_farneback_scratch_bytes: from there on the list is the entries whose refusals
-    # tests/golden/stage_errors.json pins; these are held by tests/test_aspect_gpu.py.
-    "fw_aspect_bar_sums_u8", "fw_aspect_crop_u8", "fw_aspect_pad_u8", "fw_aspect_gauss99_u8",
-    "fw_quality_scratch_bytes", "fw_quality_stats_u8",    # csrc/quality.hip, held by tests/test_quality_gpu.py
-    "fw_hdr_scratch_bytes", "fw_hdr_convert", "fw_hdr_tonemap_f32", "fw_hdr_quantise_u8", "fw_hdr_clahe_u8", "fw_hdr_saturation_u8",
-    "fw_hdr_transfer_f32",                                # csrc/hdr.hip, held by tests/test_hdr_gpu.py
-    "fw_qp_artifacts_scratch_bytes", "fw_bilateral_u8c3", "fw_gaussian5_u8", "fw_qp_artifacts_u8",    # csrc/qp_artifacts.hip, held by tests/test_qp_artifacts_gpu.py
-    "fw_farneback_scratch_bytes", "fw_farneback_flow_u8", "fw_flow_stats_f32", "fw_flow_confidence_f32",
-    "fw_nlmeans_scratch_bytes", "fw_nlmeans_u8", "fw_nlmeans_colored_u8", "fw_nlmeans_weight_table", "fw_nlmeans_lab_tables",
-    "fw_frame_stats_u8", "fw_flow_accumulate_affine_u8", "fw_add_weighted_u8",
-    "fw_bgr_to_lab_u8", "fw_lab_to_bgr_u8", "fw_lab_l_sums_u8", "fw_deflicker_lab_u8", "fw_gamma_lab_tables",
-    "fw_scene_ssim_workspace_bytes", "fw_scene_ssim_u8", "fw_hist64x3_u8",
-    "fw_pil_lanczos_taps", "fw_pil_thumb_workspace_bytes", "fw_pil_thumb_u8", "fw_dhash_pack_u8",
-    "fw_lut3d_apply_u8", "fw_lut3d_apply_u16", "fw_table3_apply_u8",
-    "fw_deinterlace_u8", "fw_deinterlace_batch_u8", "fw_interlace_stats_u8", "fw_frame_absdiff_sum_u8",
-    "fw_vhs_gray_stats_u8", "fw_vhs_blend_rows_u8", "fw_vhs_rainbow_u8", "fw_vhs_box_gray_sums_u8", "fw_vhs_dropout_repair_u8",
-    "fw_vhs_edge_counts_u8", "fw_vhs_chroma_samples_u8", "fw_vhs_chroma_shift_u8", "fw_vhs_column_sums_u8", "fw_vhs_jitter_shifts_u8",
-    "fw_vhs_saturation_f64",
-]
+HEADER_PATH = PKG_DIR.parent / "include" / "framewright_hip.h"
 
 
 class FramewrightHipError(RuntimeError):
@@ -79,360 +28,79 @@ class FramewrightOutOfMemory(FramewrightHipError):
     """FW_ERR_OOM — message contains "memory" so reference restorer.py:1746 retries with a smaller tile."""
 
 
+_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "unsigned": C.c_uint, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
+# HOST arrays that the callers hand over as typed ctypes arrays: the header cannot tell them from device pointers of the same type
+_HOST_ARRAYS = {("fw_rrdbnet_profile_read", "total_ms"): C.POINTER(C.c_double),
+                ("fw_rrdbnet_profile_read", "total_flops"): C.POINTER(C.c_double),
+                ("fw_temporal_average_u8", "weights"): C.POINTER(C.c_float),
+                ("fw_conv3x3_split_nhwc", "id_scale"): C.POINTER(C.c_float)}
+
+
+def _read_header(text: str, host_arrays: dict = _HOST_ARRAYS) -> list:
+    """``(name, restype, argtypes)`` of every prototype of the header ``text``, in its order.  Scalars map to their ctypes scalar,
+    ``const char*`` to ``c_char_p``, ``int*`` / ``long*`` to ``POINTER`` of it, ``T**`` (T not void) to ``POINTER(c_void_p)``, every
+    other pointer to ``c_void_p``; ``host_arrays`` types single parameters by (function, parameter name).  Whatever does not fit
+    raises: nothing is guessed."""
+    def fail(entry, why):
+        raise FramewrightHipError(FW_ERR_INTERNAL, f"{HEADER_PATH.name}: {entry}: {why}")
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    text = re.sub(r"\{[^{}]*\}", " ", text)      # the members of typedef struct fw_hdr_params { ... }
+    statements = [" ".join(s.split()) for s in text.replace("}", " ").split(";")]
+    typedefs = {s.split()[-1] for s in statements if s.startswith("typedef ")}
+
+    def ctype(entry, decl, named):
+        toks = decl.replace("*", " * ").split()
+        words, stars = [t for t in toks if t not in ("*", "const")], toks.count("*")
+        if len(words) != 1 + named or not all(w.isidentifier() for w in words) or toks[-1] != words[-1] and named:
+            fail(entry, f"cannot split '{decl.strip()}'")
+        base = words[0]
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        known = base in _SCALARS or base in typedefs or base in ("void", "char") or re.fullmatch(r"u?int(8|16|32|64)_t", base)
+        if not known or not 1 <= stars <= 2:
+            fail(entry, f"unknown type in '{decl.strip()}'")
+        if stars == 2:
+            return C.c_void_p if base == "void" else C.POINTER(C.c_void_p)
+        if base == "char" and "const" in toks:
+            return C.c_char_p
+        return C.POINTER(_SCALARS[base]) if base in ("int", "long") else C.c_void_p
+
+    out, seen = [], set()
+    for s in statements:
+        if not s or s.startswith("typedef "):
+            continue
+        m = re.fullmatch(r"(.*?)\b(\w+) ?\((.*)\)", s)
+        if not m:
+            fail(s[:60], "not a prototype")
+        ret, name, params = m.groups()
+        argtypes = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            t, key = ctype(name, p, True), (name, p.replace("*", " ").split()[-1])
+            seen.add(key)
+            argtypes.append(host_arrays.get(key, t))
+        out.append((name, ctype(name, ret, False), argtypes))
+    for fn, param in sorted(host_arrays.keys() - seen):
+        fail(fn, f"the host-array table names the parameter '{param}', which the header does not have")
+    return out
+
+
+if not HEADER_PATH.exists():     # code 4 is FW_ERR_INTERNAL, which only the header that is missing names
+    raise FramewrightHipError(4, f"{HEADER_PATH} not found: the C-ABI is read from it; there is no second copy")
+_HEADER = HEADER_PATH.read_text()
+# FW_OK .. FW_ERR_INTERNAL, FW_HOST / FW_DEVICE, FW_DTYPE_*, FW_NAF_PATH_*, FW_REST_PATH_*: the header's `#define FW_<NAME> <integer>` lines
+globals().update({n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(FW_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*(?:/[/*].*)?$",
+                                                       _HEADER, re.M)})
+_SIGNATURES = _read_header(_HEADER)
+EXPORTS = [name for name, _, _ in _SIGNATURES]      # every symbol include/framewright_hip.h declares, in its order
+DTYPES = {"bf16": FW_DTYPE_BF16, "bfloat16": FW_DTYPE_BF16, "f16": FW_DTYPE_F16, "fp16": FW_DTYPE_F16,
+          "float16": FW_DTYPE_F16, "half": FW_DTYPE_F16}
+
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
-
-
-def _declare(lib: C.CDLL) -> None:
-    vp, i32, f32, f64, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
-    lib.fw_last_error.restype = C.c_char_p
-    lib.fw_last_error.argtypes = []
-    lib.fw_abi_version.restype = i32
-    lib.fw_abi_version.argtypes = []
-    lib.fw_device_count.restype = i32
-    lib.fw_device_count.argtypes = []
-    lib.fw_rrdbnet_create.restype = i32
-    lib.fw_rrdbnet_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
-    lib.fw_rrdbnet_set_conv.restype = i32
-    lib.fw_rrdbnet_set_conv.argtypes = [vp, C.c_char_p, vp, vp, i32, i32]
-    lib.fw_rrdbnet_finalize.restype = i32
-    lib.fw_rrdbnet_finalize.argtypes = [vp]
-    lib.fw_rrdbnet_upscale_u8.restype = i32
-    lib.fw_rrdbnet_upscale_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_rrdbnet_upscale_u16.restype = i32
-    lib.fw_rrdbnet_upscale_u16.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_rrdbnet_workspace_bytes.restype = sz
-    lib.fw_rrdbnet_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.fw_rrdbnet_flops.restype = f64
-    lib.fw_rrdbnet_flops.argtypes = [vp, i32, i32]
-    lib.fw_rrdbnet_profile_enable.restype = i32
-    lib.fw_rrdbnet_profile_enable.argtypes = [vp, i32]
-    lib.fw_rrdbnet_profile_read.restype = i32
-    lib.fw_rrdbnet_profile_read.argtypes = [vp, C.POINTER(i32), C.POINTER(f64), C.POINTER(f64)]
-    lib.fw_rrdbnet_destroy.restype = i32
-    lib.fw_rrdbnet_destroy.argtypes = [vp]
-    lib.fw_pack_conv3x3.restype = sz
-    lib.fw_pack_conv3x3.argtypes = [i32, vp, i32, i32, i32, i32, vp]
-    lib.fw_conv3x3_nhwc.restype = i32
-    lib.fw_conv3x3_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, i32, i32, i32, vp, f32, vp, f32, vp,
-                                    i32, C.c_long, i32, vp, vp]
-
-
-def _declare_tap(lib: C.CDLL) -> None:
-    vp, i32, f32, f64, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
-    lib.fw_nafnet_create.restype = i32
-    lib.fw_nafnet_create.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(vp)]
-    lib.fw_nafnet_set_tensor.restype = i32
-    lib.fw_nafnet_set_tensor.argtypes = [vp, C.c_char_p, vp, sz]
-    lib.fw_nafnet_finalize.restype = i32
-    lib.fw_nafnet_finalize.argtypes = [vp]
-    lib.fw_nafnet_denoise_u8.restype = i32
-    lib.fw_nafnet_denoise_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_nafnet_flops.restype = f64
-    lib.fw_nafnet_flops.argtypes = [vp, i32, i32]
-    lib.fw_nafnet_destroy.restype = i32
-    lib.fw_nafnet_destroy.argtypes = [vp]
-    lib.fw_nafnet_run_block.restype = i32
-    lib.fw_nafnet_run_block.argtypes = [vp, C.c_char_p, vp, i32, i32, vp, vp]
-    lib.fw_nafnet_block_paths.restype = i32
-    lib.fw_nafnet_block_paths.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
-    lib.fw_nafnet_run_resample.restype = i32
-    lib.fw_nafnet_run_resample.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp]
-    lib.fw_u8_to_nhwc_padded.restype = i32
-    lib.fw_u8_to_nhwc_padded.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp]
-    lib.fw_u8_crop.restype = i32
-    lib.fw_u8_crop.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.fw_tile_blend_accumulate.restype = i32
-    lib.fw_tile_blend_accumulate.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp]
-    lib.fw_tile_blend_finish.restype = i32
-    lib.fw_tile_blend_finish.argtypes = [vp, vp, i32, i32, vp, vp]
-    lib.fw_temporal_average_u8.restype = i32
-    lib.fw_temporal_average_u8.argtypes = [C.POINTER(vp), C.POINTER(f32), i32, sz, vp, vp]
-    lib.fw_strength_blend_u8.restype = i32
-    lib.fw_strength_blend_u8.argtypes = [vp, vp, f64, sz, vp, vp]
-    lib.fw_grain_addback_u8.restype = i32
-    lib.fw_grain_addback_u8.argtypes = [vp, vp, i32, i32, f64, vp, vp, vp]
-    lib.fw_resize_lanczos4_u8.restype = i32
-    lib.fw_resize_lanczos4_u8.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp]
-    lib.fw_resize_linear_u8.restype = i32
-    lib.fw_resize_linear_u8.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp]
-    lib.fw_face_paste_u8.restype = i32
-    lib.fw_face_paste_u8.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, f64, vp]
-
-
-def _declare_ifnet(lib: C.CDLL) -> None:
-    vp, i32, f32, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    lib.fw_conv3x3_nhwc_ex.restype = i32
-    lib.fw_conv3x3_nhwc_ex.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, i32, i32, i32, vp, f32, vp, f32, vp, i32,
-                                       i32, i32, vp, i32, C.c_long, i32, vp, vp]
-    lib.fw_pack_conv_up2x_phase.restype = sz
-    lib.fw_pack_conv_up2x_phase.argtypes = [i32, vp, vp]
-    lib.fw_conv_up2x_phase_nhwc.restype = i32
-    lib.fw_conv_up2x_phase_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, vp, vp, i32, vp, i32, C.c_long, vp]
-    lib.fw_pack_conv3x3_wino.restype = sz
-    lib.fw_pack_conv3x3_wino.argtypes = [i32, vp, i32, i32, i32, vp]
-    lib.fw_conv3x3_split_nhwc.restype = i32
-    lib.fw_conv3x3_split_nhwc.argtypes = [i32, i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, f32, f32, i32, C.POINTER(C.c_long),
-                                          C.POINTER(f32), i32, vp, vp, i32, C.c_long, i32, vp]
-    lib.fw_conv3x3_wino_nhwc.restype = i32
-    lib.fw_conv3x3_wino_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, i32, vp, i32, C.c_long, i32, vp]
-    lib.fw_conv3x3_wino_check_fields.restype = i32
-    lib.fw_conv3x3_wino_check_fields.argtypes = [C.POINTER(i32), i32]
-    lib.fw_pack_conv_last_pointwise.restype = sz
-    lib.fw_pack_conv_last_pointwise.argtypes = [i32, vp, vp]
-    lib.fw_conv3x3_hr_last_nhwc.restype = i32
-    lib.fw_conv3x3_hr_last_nhwc.argtypes = [i32, i32, vp, i32, C.c_long, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    lib.fw_conv3x3_pair_nhwc.restype = i32
-    lib.fw_conv3x3_pair_nhwc.argtypes = [i32, vp, i32, C.c_long, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.fw_u8_to_rgb_f32.restype = i32
-    lib.fw_u8_to_rgb_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.fw_resize_bilinear_f32.restype = i32
-    lib.fw_resize_bilinear_f32.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, f32, f32, vp]
-    lib.fw_ifnet_build_x.restype = i32
-    lib.fw_ifnet_build_x.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp, vp]
-    lib.fw_unshuffle2_cast.restype = i32
-    lib.fw_unshuffle2_cast.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp]
-    lib.fw_depth_to_space4_f32.restype = i32
-    lib.fw_depth_to_space4_f32.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.fw_ifnet_accumulate.restype = i32
-    lib.fw_ifnet_accumulate.argtypes = [vp, i32, i32, i32, i32, f32, vp, vp, i32, vp]
-    lib.fw_ifnet_stage_input.restype = i32
-    lib.fw_ifnet_stage_input.argtypes = [i32, vp, vp, vp, vp, i32, i32, f32, i32, vp, i32, vp]
-    lib.fw_ifnet_accumulate_d2s.restype = i32
-    lib.fw_ifnet_accumulate_d2s.argtypes = [vp, i32, i32, i32, i32, i32, f32, vp, vp, i32, vp]
-    lib.fw_ifnet_last_flow.restype = i32
-    lib.fw_ifnet_last_flow.argtypes = [vp, i32, i32, vp, vp, vp]
-    lib.fw_ifnet_blend.restype = i32
-    lib.fw_ifnet_blend.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.fw_aesrgan_create.restype = i32
-    lib.fw_aesrgan_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-    lib.fw_aesrgan_set_tensor.restype = i32
-    lib.fw_aesrgan_set_tensor.argtypes = [vp, C.c_char_p, vp, sz]
-    lib.fw_aesrgan_finalize.restype = i32
-    lib.fw_aesrgan_finalize.argtypes = [vp]
-    lib.fw_aesrgan_forward_rgb.restype = i32
-    lib.fw_aesrgan_forward_rgb.argtypes = [vp, vp, i32, i32, vp, vp]
-    lib.fw_aesrgan_workspace_bytes.restype = sz
-    lib.fw_aesrgan_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.fw_aesrgan_destroy.restype = i32
-    lib.fw_aesrgan_destroy.argtypes = [vp]
-    lib.fw_srvgg_create.restype = i32
-    lib.fw_srvgg_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-    lib.fw_srvgg_set_tensor.restype = i32
-    lib.fw_srvgg_set_tensor.argtypes = [vp, C.c_char_p, vp, sz]
-    lib.fw_srvgg_finalize.restype = i32
-    lib.fw_srvgg_finalize.argtypes = [vp]
-    lib.fw_srvgg_upscale_u8.restype = i32
-    lib.fw_srvgg_upscale_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_srvgg_upscale_u16.restype = i32
-    lib.fw_srvgg_upscale_u16.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_resize_lanczos4_u16.restype = i32
-    lib.fw_resize_lanczos4_u16.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp]
-    lib.fw_srvgg_workspace_bytes.restype = sz
-    lib.fw_srvgg_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.fw_srvgg_flops.restype = C.c_double
-    lib.fw_srvgg_flops.argtypes = [vp, i32, i32]
-    lib.fw_srvgg_destroy.restype = i32
-    lib.fw_srvgg_destroy.argtypes = [vp]
-    lib.fw_ifnet_create.restype = i32
-    lib.fw_ifnet_create.argtypes = [i32, i32, C.POINTER(vp)]
-    lib.fw_ifnet_set_tensor.restype = i32
-    lib.fw_ifnet_set_tensor.argtypes = [vp, C.c_char_p, vp, sz]
-    lib.fw_ifnet_finalize.restype = i32
-    lib.fw_ifnet_finalize.argtypes = [vp]
-    lib.fw_ifnet_interp_u8.restype = i32
-    lib.fw_ifnet_interp_u8.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, i32, vp, vp]
-    lib.fw_ifnet_workspace_bytes.restype = sz
-    lib.fw_ifnet_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.fw_ifnet_flops.restype = C.c_double
-    lib.fw_ifnet_flops.argtypes = [vp, i32, i32]
-    lib.fw_ifnet_destroy.restype = i32
-    lib.fw_ifnet_destroy.argtypes = [vp]
-    lib.fw_restormer_create.restype = i32
-    lib.fw_restormer_create.argtypes = [i32, i32, C.POINTER(i32), i32, C.POINTER(i32), C.c_double, i32, C.POINTER(vp)]
-    lib.fw_restormer_set_tensor.restype = i32
-    lib.fw_restormer_set_tensor.argtypes = [vp, C.c_char_p, vp, sz]
-    lib.fw_restormer_finalize.restype = i32
-    lib.fw_restormer_finalize.argtypes = [vp]
-    lib.fw_restormer_denoise_u8.restype = i32
-    lib.fw_restormer_denoise_u8.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_restormer_workspace_bytes.restype = sz
-    lib.fw_restormer_workspace_bytes.argtypes = [vp, i32, i32]
-    lib.fw_restormer_destroy.restype = i32
-    lib.fw_restormer_destroy.argtypes = [vp]
-    lib.fw_restormer_run_block.restype = i32
-    lib.fw_restormer_run_block.argtypes = [vp, C.c_char_p, vp, i32, i32, vp, vp]
-    lib.fw_restormer_block_paths.restype = i32
-    lib.fw_restormer_block_paths.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
-    lib.fw_restormer_run_step.restype = i32
-    lib.fw_restormer_run_step.argtypes = [vp, C.c_char_p, vp, vp, i32, i32, vp, vp]
-    lib.fw_preserve_edges_scratch_bytes.restype = sz
-    lib.fw_preserve_edges_scratch_bytes.argtypes = [i32, i32]
-    lib.fw_preserve_edges_u8.restype = i32
-    lib.fw_preserve_edges_u8.argtypes = [vp, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp]
-    lib.fw_unsharp_mask_u8.restype = i32
-    lib.fw_unsharp_mask_u8.argtypes = [vp, i32, i32, i32, i32, C.c_uint, C.c_uint, i32, i32, i32, vp, vp, vp, vp]
-    lib.fw_u8_to_nhwc.restype = i32
-    lib.fw_u8_to_nhwc.argtypes = [i32, vp, i32, i32, vp, i32, vp]
-    lib.fw_pixel_shuffle_add_u8.restype = i32
-    lib.fw_pixel_shuffle_add_u8.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp]
-    i64 = C.c_long
-    lib.fw_layernorm_nhwc.restype = i32
-    lib.fw_layernorm_nhwc.argtypes = [i32, vp, i64, i64, i32, vp, vp, f32, vp, i64, i32, vp]
-    lib.fw_pack_pointwise.restype = sz
-    lib.fw_pack_pointwise.argtypes = [i32, vp, i32, i32, vp]
-    lib.fw_pointwise_nhwc.restype = i32
-    lib.fw_pointwise_nhwc.argtypes = [i32, vp, i32, i64, i64, i32, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp]
-    lib.fw_dwconv3x3_nhwc.restype = i32
-    lib.fw_dwconv3x3_nhwc.argtypes = [i32, vp, i64, i32, i32, i32, vp, i32, vp, i64, vp]
-    lib.fw_attn_workspace_floats.restype = sz
-    lib.fw_attn_workspace_floats.argtypes = [i32, i32]
-    lib.fw_attn_matrix.restype = i32
-    lib.fw_attn_matrix.argtypes = [i32, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp]
-    lib.fw_attn_qk_scratch_elems.restype = sz
-    lib.fw_attn_qk_scratch_elems.argtypes = [i64, i32, i32]
-    lib.fw_attn_matrix_mfma.restype = i32
-    lib.fw_attn_matrix_mfma.argtypes = [i32, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.fw_attn_apply.restype = i32
-    lib.fw_attn_apply.argtypes = [i32, vp, i64, i64, i32, i32, i32, vp, vp, i64, i32, vp]
-    lib.fw_attn_pack.restype = i32
-    lib.fw_attn_pack.argtypes = [i32, vp, i32, i32, i32, vp, vp]
-    lib.fw_attn_proj_pack.restype = i32
-    lib.fw_attn_proj_pack.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.fw_pixel_shuffle2_f32.restype = i32
-    lib.fw_pixel_shuffle2_f32.argtypes = [vp, i64, i32, i32, i32, vp, i64, i32, i32, vp]
-    lib.fw_copy_channels_f32.restype = i32
-    lib.fw_copy_channels_f32.argtypes = [vp, i64, i64, i32, vp, i64, i32, vp]
-    lib.fw_attn_softmax_rows.restype = i32
-    lib.fw_attn_softmax_rows.argtypes = [i32, vp, i64, vp, i64, i64, i32, vp, i64, vp]
-    lib.fw_pack_pointwise_transposed.restype = i32
-    lib.fw_pack_pointwise_transposed.argtypes = [i32, vp, i64, i64, i32, i32, vp, vp]
-    lib.fw_f32_to_planar.restype = i32
-    lib.fw_f32_to_planar.argtypes = [i32, vp, i64, i32, vp, vp]
-    lib.fw_flow_accumulate_u8.restype = i32
-    lib.fw_flow_accumulate_u8.argtypes = [vp, vp, vp, vp, C.c_double, vp, f32, i32, i32, i32, vp, vp, vp]
-    lib.fw_flow_accumulate_finish_u8.restype = i32
-    lib.fw_flow_accumulate_finish_u8.argtypes = [vp, vp, i32, i32, vp, vp]
-    lib.fw_tap_post_u8.restype = i32
-    lib.fw_tap_post_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.fw_farneback_scratch_bytes.restype = sz
-    lib.fw_farneback_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.fw_farneback_flow_u8.restype = i32
-    lib.fw_farneback_flow_u8.argtypes = [vp, vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, C.c_double, i32, vp, vp, vp, vp]
-    lib.fw_flow_stats_f32.restype = i32
-    lib.fw_flow_stats_f32.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    lib.fw_flow_confidence_f32.restype = i32
-    lib.fw_flow_confidence_f32.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    lib.fw_nlmeans_scratch_bytes.restype = sz
-    lib.fw_nlmeans_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.fw_nlmeans_u8.restype = i32
-    lib.fw_nlmeans_u8.argtypes = [vp, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp]
-    lib.fw_nlmeans_colored_u8.restype = i32
-    lib.fw_nlmeans_colored_u8.argtypes = [vp, i32, i32, C.c_double, C.c_double, i32, i32, vp, vp, vp]
-    lib.fw_nlmeans_weight_table.restype = i32
-    lib.fw_nlmeans_weight_table.argtypes = [C.c_double, i32, i32, i32, vp, i32]
-    lib.fw_nlmeans_lab_tables.restype = i32
-    lib.fw_nlmeans_lab_tables.argtypes = [i32, vp, i32]
-    lib.fw_frame_stats_u8.restype = i32
-    lib.fw_frame_stats_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-    lib.fw_flow_accumulate_affine_u8.restype = i32
-    lib.fw_flow_accumulate_affine_u8.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp]
-    lib.fw_add_weighted_u8.restype = i32
-    lib.fw_add_weighted_u8.argtypes = [vp, C.c_double, vp, C.c_double, sz, vp, vp]
-    lib.fw_bgr_to_lab_u8.restype = i32
-    lib.fw_bgr_to_lab_u8.argtypes = [vp, C.c_int64, vp, vp]
-    lib.fw_lab_to_bgr_u8.restype = i32
-    lib.fw_lab_to_bgr_u8.argtypes = [vp, C.c_int64, vp, vp]
-    lib.fw_lab_l_sums_u8.restype = i32
-    lib.fw_lab_l_sums_u8.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.fw_deflicker_lab_u8.restype = i32
-    lib.fw_deflicker_lab_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-    lib.fw_gamma_lab_tables.restype = i32
-    lib.fw_gamma_lab_tables.argtypes = [i32, vp, i32]
-    lib.fw_scene_ssim_workspace_bytes.restype = sz
-    lib.fw_scene_ssim_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.fw_scene_ssim_u8.restype = i32
-    lib.fw_scene_ssim_u8.argtypes = [vp, vp, C.c_int64, i32, i32, i32, vp, vp, vp]
-    lib.fw_hist64x3_u8.restype = i32
-    lib.fw_hist64x3_u8.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.fw_pil_lanczos_taps.restype = i32
-    lib.fw_pil_lanczos_taps.argtypes = [i32, i32, vp, vp, vp, i32]
-    lib.fw_pil_thumb_workspace_bytes.restype = sz
-    lib.fw_pil_thumb_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
-    lib.fw_pil_thumb_u8.restype = i32
-    lib.fw_pil_thumb_u8.argtypes = [vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.fw_dhash_pack_u8.restype = i32
-    lib.fw_dhash_pack_u8.argtypes = [vp, i32, i32, vp, vp]
-    lib.fw_lut3d_apply_u8.restype = i32
-    lib.fw_lut3d_apply_u8.argtypes = [vp, C.c_int64, i32, i32, i32, vp, i32, i32, vp, C.c_int64, vp]
-    lib.fw_lut3d_apply_u16.restype = i32
-    lib.fw_lut3d_apply_u16.argtypes = [vp, C.c_int64, i32, i32, i32, vp, i32, i32, vp, C.c_int64, vp]
-    lib.fw_table3_apply_u8.restype = i32
-    lib.fw_table3_apply_u8.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp, C.c_int64, vp]
-    lib.fw_deinterlace_u8.restype = i32
-    lib.fw_deinterlace_u8.argtypes = [vp, vp, vp, vp, i32, C.c_int64, i32, i32, vp]
-    lib.fw_deinterlace_batch_u8.restype = i32
-    lib.fw_deinterlace_batch_u8.argtypes = [vp, i32, i32, C.c_int64, i32, i32, vp]
-    lib.fw_interlace_stats_u8.restype = i32
-    lib.fw_interlace_stats_u8.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.fw_frame_absdiff_sum_u8.restype = i32
-    lib.fw_frame_absdiff_sum_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.fw_vhs_gray_stats_u8.restype = i32
-    lib.fw_vhs_gray_stats_u8.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
-    lib.fw_vhs_blend_rows_u8.restype = i32
-    lib.fw_vhs_blend_rows_u8.argtypes = [vp, vp, i32, i32, C.c_int64, vp, vp, i32, vp]
-    lib.fw_vhs_rainbow_u8.restype = i32
-    lib.fw_vhs_rainbow_u8.argtypes = [vp, vp, i32, i32, i32, f32, f32, vp]
-    lib.fw_vhs_box_gray_sums_u8.restype = i32
-    lib.fw_vhs_box_gray_sums_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_vhs_dropout_repair_u8.restype = i32
-    lib.fw_vhs_dropout_repair_u8.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, i32, C.c_double, vp]
-    lib.fw_vhs_edge_counts_u8.restype = i32
-    lib.fw_vhs_edge_counts_u8.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.fw_vhs_chroma_samples_u8.restype = i32
-    lib.fw_vhs_chroma_samples_u8.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.fw_vhs_chroma_shift_u8.restype = i32
-    lib.fw_vhs_chroma_shift_u8.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    lib.fw_vhs_column_sums_u8.restype = i32
-    lib.fw_vhs_column_sums_u8.argtypes = [vp, i32, i32, vp, vp]
-    lib.fw_vhs_jitter_shifts_u8.restype = i32
-    lib.fw_vhs_jitter_shifts_u8.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.fw_vhs_saturation_f64.restype = i32
-    lib.fw_vhs_saturation_f64.argtypes = [vp, i32, i32, vp, vp]
-    lib.fw_aspect_bar_sums_u8.restype = i32
-    lib.fw_aspect_bar_sums_u8.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.fw_aspect_crop_u8.restype = i32
-    lib.fw_aspect_crop_u8.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.fw_aspect_pad_u8.restype = i32
-    lib.fw_aspect_pad_u8.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.fw_aspect_gauss99_u8.restype = i32
-    lib.fw_aspect_gauss99_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
-    lib.fw_quality_stats_u8.restype = i32
-    lib.fw_quality_stats_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.fw_quality_scratch_bytes.restype = sz
-    lib.fw_quality_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.fw_hdr_scratch_bytes.restype = sz
-    lib.fw_hdr_scratch_bytes.argtypes = [i32]
-    lib.fw_hdr_convert.restype = i32
-    lib.fw_hdr_convert.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.fw_hdr_tonemap_f32.restype = i32
-    lib.fw_hdr_tonemap_f32.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp]
-    lib.fw_hdr_quantise_u8.restype = i32
-    lib.fw_hdr_quantise_u8.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
-    lib.fw_hdr_clahe_u8.restype = i32
-    lib.fw_hdr_clahe_u8.argtypes = [vp, i32, i32, vp, vp, vp]
-    lib.fw_hdr_saturation_u8.restype = i32
-    lib.fw_hdr_saturation_u8.argtypes = [vp, C.c_int64, vp, f32, f32, vp, vp]
-    lib.fw_hdr_transfer_f32.restype = i32
-    lib.fw_hdr_transfer_f32.argtypes = [vp, C.c_int64, vp, vp, vp]
-    lib.fw_qp_artifacts_scratch_bytes.restype = sz
-    lib.fw_qp_artifacts_scratch_bytes.argtypes = [i32, i32]
-    lib.fw_bilateral_u8c3.restype = i32
-    lib.fw_bilateral_u8c3.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.fw_gaussian5_u8.restype = i32
-    lib.fw_gaussian5_u8.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.fw_qp_artifacts_u8.restype = i32
-    lib.fw_qp_artifacts_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, C.c_uint64, vp, vp]
 
 
 def load() -> C.CDLL:
@@ -456,9 +124,9 @@ def load() -> C.CDLL:
             lib = C.CDLL(str(LIB_PATH))
         except OSError as e:
             raise FramewrightHipError(FW_ERR_INTERNAL, f"cannot load {LIB_PATH}: {e}") from e
-        _declare(lib)
-        _declare_tap(lib)
-        _declare_ifnet(lib)
+        for name, restype, argtypes in _SIGNATURES:
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
