@@ -113,6 +113,28 @@ double fw_rrdbnet_flops(const fw_rrdbnet* net, int height, int width);
 int fw_rrdbnet_profile_enable(fw_rrdbnet* net, int on);
 int fw_rrdbnet_profile_read(fw_rrdbnet* net, int* launches, double* total_ms, double* total_flops);
 
+/* RRDBs of the trunk on their own, on the caller's device buffers (tests, tools): the same launches, workspace, mutex and stream
+ * ordering as fw_rrdbnet_upscale_u8 makes for those blocks, dispatched by the handle's own switches (FW_RRDB_* read at create,
+ * FW_PAIR_SLIDE per launch).
+ * run_rrdbs: RRDBs first_block .. first_block + count - 1 on a trunk of height x width pixels (the trunk's resolution; the model's
+ *   scale plays no part), starting with the concat buffer (3 * first_block mod the buffers in rotation) and the residual source a
+ *   forward holds on entering first_block.  trunk_in_f32: device fp32 [height][width][64], laid into the engine's representation -
+ *   split trunk: typed hi = T(x) in planes 0-1 and typed lo = T(x - float(hi)) in planes 6-7; fp32 trunk: the typed planes and the
+ *   fp32 buffer in the accumulator-native layout.  trunk_out_f32: device fp32 [height][width][64], the last RRDB's output
+ *   (float(hi) + float(lo), or the fp32 trunk).  growth_out (optional, device, operand-typed [4][height][width][32]): x1 .. x4 of the
+ *   last dense block run, planes 2-5 of its concat buffer.  FW_ERR_INVALID: a block range outside the net, a handle that is not
+ *   finalised, a non-positive size.
+ * block_paths: which kernel forms the RRDBs of this handle dispatch to, as FW_RRDB_PATH_* bits. */
+#define FW_RRDB_PATH_PAIR12 1         /* conv1 + conv2 in one launch */
+#define FW_RRDB_PATH_PAIR34 2         /* conv3 + conv4 in one launch */
+#define FW_RRDB_PATH_SPLIT_TRUNK 4    /* the trunk as typed hi + lo planes, residual adds on the matrix cores */
+#define FW_RRDB_PATH_RRDB_LO 8        /* lo planes behind rdb3 only: rdb1 / rdb2 hand on the typed planes alone */
+#define FW_RRDB_PATH_C5_WINO_RDB12 16 /* conv5 of rdb1 / rdb2 as row-wise Winograd F(2, 3) */
+#define FW_RRDB_PATH_C5_WINO_RDB3 32  /* conv5 of rdb3 in its residual-plane Winograd form */
+int fw_rrdbnet_run_rrdbs(fw_rrdbnet* net, int first_block, int count, const float* trunk_in_f32, int height, int width,
+                         float* trunk_out_f32, void* growth_out, void* stream);
+int fw_rrdbnet_block_paths(fw_rrdbnet* net, int* flags);
+
 /* Release device memory.  NULL is allowed. */
 int fw_rrdbnet_destroy(fw_rrdbnet* net);
 

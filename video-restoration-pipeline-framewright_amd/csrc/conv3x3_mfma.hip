@@ -389,7 +389,7 @@ __global__ __launch_bounds__(64 * NWAVES, WAVES_PER_SIMD) void conv3x3_mfma_kern
                             const int x = x0 + 16 * ph + q;
                             const bool inside = y < p.H && x < p.W;
                             const size_t pix = (size_t)y * p.W + x;
-                            const size_t nat = ((((((size_t)t * NWAVES + wave) * RPW + row) * NW + w) * 2 + ph) * 64 + lane) * 4;
+                            const size_t nat = f32_native_offset(t, wave, row, w, ph, lane, NW);
                             const size_t lin = pix * (p.f32_cstride ? p.f32_cstride : NC) + p.f32_coff + 16 * w + 4 * sl;
                             const size_t fo = p.f32_native ? nat : lin;
                             const bool fok = p.f32_native || inside;
@@ -499,6 +499,67 @@ static const void* zero_page() {
 size_t f32_native_elems(int H, int W, int cout_tiles) {
     const size_t tiles = (size_t)((W + TILE_W - 1) / TILE_W) * ((H + TILE_H - 1) / TILE_H);
     return tiles * (TILE_H * TILE_W) * 32 * cout_tiles;
+}
+
+// ---- a 64-channel fp32 NHWC map <-> the trunk representations of the RRDB engine (fw_rrdbnet_run_rrdbs: tests and tools) ----------
+// One thread per pixel of the padded 16 x 32 tile grid and 4-channel group.  Typed planes: [2][H][W][32], `pstride` elements apart.
+template <typename T>
+__global__ void trunk_from_f32_kernel(const float* __restrict__ src, int H, int W, long pstride, T* hi, T* lo, float* native) {
+    const int Wp = (W + TILE_W - 1) / TILE_W * TILE_W, Hp = (H + TILE_H - 1) / TILE_H * TILE_H;
+    const long n = (long)Hp * Wp * 16;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int g = (int)(i & 15);
+        const long pix = i >> 4;
+        const int y = (int)(pix / Wp), x = (int)(pix - (long)y * Wp);
+        const bool inside = y < H && x < W;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (inside) v = *reinterpret_cast<const f32x4*>(src + ((size_t)y * W + x) * 64 + 4 * g);
+        if (native) *reinterpret_cast<f32x4*>(native + f32_native_offset_of(y, x, g, H, W, 4)) = v;   // zeros in the padding
+        if (!inside) continue;
+        const size_t to = (size_t)(g >> 3) * pstride + ((size_t)y * W + x) * 32 + 4 * (g & 7);
+        const uint2 h = Op<T>::pack4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<uint2*>(hi + to) = h;
+        if (lo) {   // lo = T(x - float(hi)), as the conv epilogue's second pass defines out_lo
+            const f32x4 r = v - Op<T>::unpack4(h);
+            *reinterpret_cast<uint2*>(lo + to) = Op<T>::pack4(r[0], r[1], r[2], r[3]);
+        }
+    }
+}
+
+template <typename T>
+__global__ void trunk_to_f32_kernel(const T* hi, const T* lo, const float* native, int H, int W, long pstride, float* __restrict__ dst) {
+    const long n = (long)H * W * 16;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int g = (int)(i & 15);
+        const long pix = i >> 4;
+        const int y = (int)(pix / W), x = (int)(pix - (long)y * W);
+        f32x4 v;
+        if (native) {
+            v = *reinterpret_cast<const f32x4*>(native + f32_native_offset_of(y, x, g, H, W, 4));
+        } else {
+            const size_t to = (size_t)(g >> 3) * pstride + (size_t)pix * 32 + 4 * (g & 7);
+            v = Op<T>::unpack4(*reinterpret_cast<const uint2*>(hi + to)) + Op<T>::unpack4(*reinterpret_cast<const uint2*>(lo + to));
+        }
+        *reinterpret_cast<f32x4*>(dst + (size_t)pix * 64 + 4 * g) = v;
+    }
+}
+
+void launch_trunk_from_f32(DType dt, const float* src, int H, int W, long pstride, void* hi, void* lo, float* native, hipStream_t st) {
+    const long n = (long)((H + TILE_H - 1) / TILE_H * TILE_H) * ((W + TILE_W - 1) / TILE_W * TILE_W) * 16;
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((trunk_from_f32_kernel<T>), dim3(grid_1d(n, 4096)), dim3(256), 0, st, src, H, W, pstride, (T*)hi, (T*)lo, native);
+    });
+    FW_HIP_CHECK(hipGetLastError());
+}
+
+void launch_trunk_to_f32(DType dt, const void* hi, const void* lo, const float* native, int H, int W, long pstride, float* dst, hipStream_t st) {
+    with_operand_type(dt, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((trunk_to_f32_kernel<T>), dim3(grid_1d((long)H * W * 16, 4096)), dim3(256), 0, st, (const T*)hi, (const T*)lo, native, H, W,
+                           pstride, dst);
+    });
+    FW_HIP_CHECK(hipGetLastError());
 }
 
 const void* conv_zero_page() { return zero_page(); }

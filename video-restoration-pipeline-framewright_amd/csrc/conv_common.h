@@ -134,6 +134,25 @@ __device__ __forceinline__ void tile_pos(int t, int tiles_x, int tiles_y, int* t
     }
 }
 
+// its inverse: the linear index of tile (ty, tx)
+__host__ __device__ constexpr int tile_index(int ty, int tx, int tiles_x, int tiles_y) {
+    return FW_TILE_ORDER == 0 ? ty * tiles_x + tx : tx * tiles_y + ty;
+}
+
+// Accumulator-native fp32 side buffers (ConvParams::f32_native, f32_native_elems): the fragment order
+// [tile][wave][row][w][ph][lane][4] of conv3x3_mfma_kernel - tile t's wave `wave` holds, for its output row `row`, 16-channel
+// tile w (of nw) and half row ph, the four channels 16 w + 4 (lane >> 4) .. + 3 of pixel 16 ph + (lane & 15) in lane `lane`.
+// The float offset of those four: the one statement of the layout, for the conv epilogue and for the NHWC <-> native copies.
+__host__ __device__ constexpr size_t f32_native_offset(int t, int wave, int row, int w, int ph, int lane, int nw) {
+    return ((((((size_t)t * NWAVES + wave) * RPW + row) * nw + w) * 2 + ph) * 64 + lane) * 4;
+}
+// the same for the channel group [4 g, 4 g + 4) of pixel (y, x) of an H x W map with 16 nw channels
+__host__ __device__ constexpr size_t f32_native_offset_of(int y, int x, int g, int H, int W, int nw) {
+    const int ry = y % TILE_H, rx = x % TILE_W;
+    return f32_native_offset(tile_index(y / TILE_H, x / TILE_W, (W + TILE_W - 1) / TILE_W, (H + TILE_H - 1) / TILE_H), ry / RPW, ry % RPW,
+                             g >> 2, rx >> 4, 16 * (g & 3) + (rx & 15), nw);
+}
+
 __host__ __device__ constexpr int halo_swz(int px) { return ((px >> 2) & 1) << 1; }
 
 // Persistent workgroups: each owns a contiguous share of a kernel's linear tile (or item) index.  Blocks b and b+8 share an XCD

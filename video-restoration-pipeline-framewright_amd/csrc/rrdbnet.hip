@@ -214,6 +214,176 @@ void run_pair(fw_rrdbnet* n, const ConvLayer& a, const ConvLayer& b, const ConvP
     timed(n, st, conv_flops(a, (size_t)q.H * q.W) + conv_flops(b, (size_t)q.H * q.W), [&] { launch_conv3x3_pair(n->dt, q, st); });
 }
 
+// The trunk of a forward in the handle's workspace, as forward() and fw_rrdbnet_run_rrdbs see it
+struct Trunk {
+    int Ht = 0, Wt = 0;
+    int ncat = 2;       // concat buffers in rotation: 3 on the split trunk (the RRDB input stays alive until rdb3's second residual)
+    long PL = 0;        // elements of one plane: a 192-channel concat buffer is 6 planes of [Ht][Wt][32] (+ planes 6-7: the lo part of x)
+    void* cat[3] = {};
+    float *F = nullptr, *R = nullptr, *tA = nullptr, *tB = nullptr;   // fp32 trunk buffers, accumulator-native layout
+    ConvParams base{};  // what every conv of the trunk starts from
+};
+
+void* plane(void* buf, int chunk, long pl) { return (void*)((char*)buf + (size_t)chunk * pl * 2); }
+
+Trunk make_trunk(const fw_rrdbnet* n, const Plan& pl, int Ht, int Wt) {
+    char* ws = (char*)n->ws.p;
+    Trunk T;
+    T.Ht = Ht;
+    T.Wt = Wt;
+    T.ncat = n->split_trunk ? 3 : 2;
+    T.PL = (long)Ht * Wt * 32;
+    T.cat[0] = ws + pl.cat0;
+    T.cat[1] = ws + pl.cat1;
+    T.cat[2] = ws + pl.cat2;
+    T.F = (float*)(ws + pl.F);
+    T.R = (float*)(ws + pl.R);
+    T.tA = (float*)(ws + pl.tA);
+    T.tB = (float*)(ws + pl.tB);
+    T.base.H = Ht;
+    T.base.W = Wt;
+    T.base.s1 = 1.f;
+    T.base.s2 = 1.f;
+    T.base.in_cstride = 32;
+    T.base.in_pstride = T.PL;
+    T.base.out_cstride = 32;
+    T.base.out_pstride = T.PL;
+    T.base.f32_native = 1;
+    return T;
+}
+
+// whether conv c + 1 and conv c + 2 of a dense block (c = 0, 2) run as one launch
+bool pair_fused(const fw_rrdbnet* n, int c) { return n->fuse_pairs && (n->fuse_mask >> (c >> 1) & 1); }
+
+// residual planes of rdb k's conv5 on the split trunk: x lo (unless the lo planes are kept at RRDB granularity) and, for rdb3, R hi + R lo
+int c5_planes(const fw_rrdbnet* n, int k) { return n->rrdb_lo ? (k == 2 ? 4 : 0) : (k == 2 ? 6 : 2); }
+
+// whether a conv5 with n_id residual planes takes the Winograd kernel: the one place that decides it, for run_rrdb and for
+// fw_rrdbnet_block_paths
+bool c5_on_wino(const fw_rrdbnet* n, int n_id, const ConvLayer& c5) {
+    return n->c5_wino && n->dt == DT_F16 && (n_id == 0 || n->c5_wino >= 2) && c5.d_wwino && !(n->abl_alias & 2) && !n->abl_rdb3;
+}
+
+// RRDB b of the trunk.  cur: the concat buffer whose planes 0-1 (split trunk: + 6-7) hold its input, on return the one that holds its
+// output; Rin: the fp32 trunk buffer of its input (fp32 trunk only; the output goes to R).
+void run_rrdb(fw_rrdbnet* n, const Trunk& T, int b, const float* Rin, int& cur, hipStream_t st) {
+    void* const* cat = T.cat;
+    const int ncat = T.ncat, Ht = T.Ht, Wt = T.Wt;
+    const long PL = T.PL;
+    const ConvParams& base = T.base;
+    float *R = T.R, *tA = T.tA, *tB = T.tB;
+    const int rrdb_in = cur;  // split trunk: planes 0-1 of this buffer stay the RRDB input until rdb3 overwrites them
+    for (int k = 0; k < 3; ++k) {
+        const ConvLayer* L = &n->body[((size_t)b * 3 + k) * 5];
+        // conv1..conv4: growth channels, LeakyReLU(0.2), written into the next plane    (:184-187);
+        // fused in pairs (conv1+conv2, conv3+conv4): the shared input chunks leave HBM once per pair
+        for (int c = 0; c < 4; c += 2) {
+            if (pair_fused(n, c)) {
+                ConvPairParams q{};
+                q.in = cat[cur];
+                q.in_cstride = 32;
+                q.in_pstride = (n->abl_alias & 1) ? 40 : PL;
+                q.na = 2 + c;
+                q.H = Ht;
+                q.W = Wt;
+                q.wpk_a = L[c].d_w;
+                q.bias_a = L[c].d_b;
+                q.wpk_b = L[c + 1].d_w;
+                q.bias_b = L[c + 1].d_b;
+                q.out_a = plane(cat[cur], 2 + c, PL);
+                q.out_b = plane(cat[cur], 3 + c, PL);
+                q.out_cstride = 32;
+                run_pair(n, L[c], L[c + 1], q, st);
+            } else {
+                for (int cc = c; cc < c + 2; ++cc) {
+                    ConvParams p = base;
+                    p.in = cat[cur];
+                    p.out = plane(cat[cur], 2 + cc, PL);
+                    p.act = 1;
+                    run_conv(n, L[cc], EPI_STORE, p, st);
+                }
+            }
+        }
+        // conv5 + residual(s): x5*0.2 + x  (:188-189); after rdb3 additionally *0.2 + rrdb_in (:204)
+        ConvParams p = base;
+        const int nxt = (cur + 1) % ncat;
+        p.in = cat[cur];
+        p.out = cat[nxt];
+        p.s1 = 0.2f;
+        if (n->abl_alias & 2) p.in_pstride = 40;
+        if (n->split_trunk) {
+            // y = 0.2*conv5 + x           = 0.2  * (conv5 + 5*x)            x = planes 0,1 (hi) + 6,7 (lo) of cat[cur]
+            // y = (0.2*conv5 + x)*0.2 + R = 0.04 * (conv5 + 5*x + 25*R)     R = the same planes of cat[rrdb_in]
+            // x hi is added from conv chunks 0,1 while they sit in LDS; residual planes: x lo (6,7) [, R hi (0,1), R lo
+            // (6,7)].  Each tile consumes its residual pixels before it stores, so rdb3 updates the RRDB input in place
+            // (nxt == rrdb_in).
+            const long PB = PL * 2;  // bytes per plane
+            const long r_off = (char*)cat[rrdb_in] - (char*)cat[cur];
+            p.in_id_scale = 5.f;
+            if (n->rrdb_lo) {
+                // lo planes at RRDB granularity: rdb1 / rdb2 carry their output as the typed planes alone (what they lose
+                // - half an ulp of the operand type, once each - reaches the RRDB output scaled by 0.2), and only the
+                // RRDB-level trunk R keeps hi + lo.  rdb1 takes its residual from R hi (the centre tap in LDS), rdb3
+                // adds R hi + R lo and writes hi + lo.  Per RRDB 4 lo-plane transfers instead of 16; measured against
+                // the fp32 oracle the f16 path moves from 3.0-3.7e-4 to 3.4-3.8e-4 max-abs.
+                p.n_id = c5_planes(n, k);
+                if (k == 2) {
+                    p.out_lo = plane(cat[nxt], 6, PL);
+                    p.chunk_off[0] = r_off;              // R hi
+                    p.chunk_off[1] = r_off + PB;
+                    p.chunk_off[2] = r_off + 6 * PB;     // R lo
+                    p.chunk_off[3] = r_off + 7 * PB;
+                    for (int i = 0; i < 4; ++i) p.id_scale[i] = 25.f;
+                    if (n->abl_rdb3 & 1) {
+                        p.out_lo = nullptr;
+                    }
+                    if (n->abl_rdb3 & 2) p.n_id = 2;
+                    if ((n->abl_rdb3 & 6) == 6) p.n_id = 0;
+                    else if (n->abl_rdb3 & 4) {
+                        p.n_id = 2;
+                        p.chunk_off[0] = p.chunk_off[2];
+                        p.chunk_off[1] = p.chunk_off[3];
+                    }
+                }
+            } else {
+                p.out_lo = plane(cat[nxt], 6, PL);
+                p.n_id = c5_planes(n, k);
+                p.chunk_off[0] = 6 * PB;
+                p.chunk_off[1] = 7 * PB;
+                p.id_scale[0] = p.id_scale[1] = 5.f;
+                if (k == 2) {
+                    p.chunk_off[2] = r_off;              // R hi
+                    p.chunk_off[3] = r_off + PB;
+                    p.chunk_off[4] = r_off + 6 * PB;     // R lo
+                    p.chunk_off[5] = r_off + 7 * PB;
+                    for (int i = 2; i < 6; ++i) p.id_scale[i] = 25.f;
+                }
+            }
+            p.s1 = (k == 2) ? 0.2f * 0.2f : 0.2f;
+            if (c5_on_wino(n, p.n_id, L[4])) {
+                p.cin_chunks = L[4].chunks;
+                p.wpk = L[4].d_wwino;
+                p.bias = L[4].d_b;
+                // algorithmic FLOPs: the nine-tap count
+                timed(n, st, conv_flops(L[4], (size_t)p.H * p.W), [&] { launch_conv3x3_wino_split(p, st); });
+            } else {
+                run_conv(n, L[4], EPI_RESIDUAL_SPLIT, p, st);
+            }
+        } else {
+            p.res1 = (k == 0) ? Rin : (k == 1 ? tA : tB);
+            if (k == 2) {
+                p.res2 = Rin;
+                p.s2 = 0.2f;
+                p.out_f32 = R;
+            } else {
+                p.out_f32 = (k == 0) ? tA : tB;
+            }
+            run_conv(n, L[4], EPI_RESIDUAL, p, st);
+        }
+        cur = nxt;
+    }
+}
+
 // bits = 8: d_in / d_out are uint8 BGR; bits = 16: uint16 BGR (range 65535)
 void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_out, float* d_rgb, hipStream_t st) {
     int Ht, Wt;
@@ -221,32 +391,18 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     const Plan pl = make_plan(n, H, W);
     char* ws = (char*)n->ws.p;
     void* in32 = ws + pl.in32;
-    void* cat[3] = {ws + pl.cat0, ws + pl.cat1, ws + pl.cat2};
-    const int ncat = n->split_trunk ? 3 : 2;
-
-    float* F = (float*)(ws + pl.F);
-    float* R = (float*)(ws + pl.R);
-    float* tA = (float*)(ws + pl.tA);
-    float* tB = (float*)(ws + pl.tB);
+    const Trunk T = make_trunk(n, pl, Ht, Wt);
+    void* const* cat = T.cat;
+    const int ncat = T.ncat;
+    float* F = T.F;
     void* U1 = ws + pl.U1;
     void* U2 = ws + pl.U2;
     void* U3 = ws + pl.U3;
 
     launch_frame_to_nhwc(n->dt, d_in, bits, H, W, in32, 32, n->scale == 2 ? 2 : 1, st);
 
-    // chunk-planar activations: a 192-channel concat buffer is 6 planes of [Ht][Wt][32]
-    const long PL = (long)Ht * Wt * 32;
-    auto plane = [&](void* buf, int chunk, long pl) { return (void*)((char*)buf + (size_t)chunk * pl * 2); };
-    ConvParams base{};
-    base.H = Ht;
-    base.W = Wt;
-    base.s1 = 1.f;
-    base.s2 = 1.f;
-    base.in_cstride = 32;
-    base.in_pstride = PL;
-    base.out_cstride = 32;
-    base.out_pstride = PL;
-    base.f32_native = 1;
+    const long PL = T.PL;
+    const ConvParams& base = T.base;
 
     // conv_first -> concat buffer 0 [0:64] + fp32 trunk F          (aesrgan_face.py:250)
     {
@@ -259,120 +415,7 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     }
 
     int cur = 0;
-    for (int b = 0; b < n->num_block; ++b) {
-        const float* Rin = (b == 0) ? F : R;
-        const int rrdb_in = cur;  // split trunk: planes 0-1 of this buffer stay the RRDB input until rdb3 overwrites them
-        for (int k = 0; k < 3; ++k) {
-            const ConvLayer* L = &n->body[((size_t)b * 3 + k) * 5];
-            // conv1..conv4: growth channels, LeakyReLU(0.2), written into the next plane    (:184-187);
-            // fused in pairs (conv1+conv2, conv3+conv4): the shared input chunks leave HBM once per pair
-            for (int c = 0; c < 4; c += 2) {
-                if (n->fuse_pairs && (n->fuse_mask >> (c >> 1) & 1)) {
-                    ConvPairParams q{};
-                    q.in = cat[cur];
-                    q.in_cstride = 32;
-                    q.in_pstride = (n->abl_alias & 1) ? 40 : PL;
-                    q.na = 2 + c;
-                    q.H = Ht;
-                    q.W = Wt;
-                    q.wpk_a = L[c].d_w;
-                    q.bias_a = L[c].d_b;
-                    q.wpk_b = L[c + 1].d_w;
-                    q.bias_b = L[c + 1].d_b;
-                    q.out_a = plane(cat[cur], 2 + c, PL);
-                    q.out_b = plane(cat[cur], 3 + c, PL);
-                    q.out_cstride = 32;
-                    run_pair(n, L[c], L[c + 1], q, st);
-                } else {
-                    for (int cc = c; cc < c + 2; ++cc) {
-                        ConvParams p = base;
-                        p.in = cat[cur];
-                        p.out = plane(cat[cur], 2 + cc, PL);
-                        p.act = 1;
-                        run_conv(n, L[cc], EPI_STORE, p, st);
-                    }
-                }
-            }
-            // conv5 + residual(s): x5*0.2 + x  (:188-189); after rdb3 additionally *0.2 + rrdb_in (:204)
-            ConvParams p = base;
-            const int nxt = (cur + 1) % ncat;
-            p.in = cat[cur];
-            p.out = cat[nxt];
-            p.s1 = 0.2f;
-            if (n->abl_alias & 2) p.in_pstride = 40;
-            if (n->split_trunk) {
-                // y = 0.2*conv5 + x           = 0.2  * (conv5 + 5*x)            x = planes 0,1 (hi) + 6,7 (lo) of cat[cur]
-                // y = (0.2*conv5 + x)*0.2 + R = 0.04 * (conv5 + 5*x + 25*R)     R = the same planes of cat[rrdb_in]
-                // x hi is added from conv chunks 0,1 while they sit in LDS; residual planes: x lo (6,7) [, R hi (0,1), R lo
-                // (6,7)].  Each tile consumes its residual pixels before it stores, so rdb3 updates the RRDB input in place
-                // (nxt == rrdb_in).
-                const long PB = PL * 2;  // bytes per plane
-                const long r_off = (char*)cat[rrdb_in] - (char*)cat[cur];
-                p.in_id_scale = 5.f;
-                if (n->rrdb_lo) {
-                    // lo planes at RRDB granularity: rdb1 / rdb2 carry their output as the typed planes alone (what they lose
-                    // - half an ulp of the operand type, once each - reaches the RRDB output scaled by 0.2), and only the
-                    // RRDB-level trunk R keeps hi + lo.  rdb1 takes its residual from R hi (the centre tap in LDS), rdb3
-                    // adds R hi + R lo and writes hi + lo.  Per RRDB 4 lo-plane transfers instead of 16; measured against
-                    // the fp32 oracle the f16 path moves from 3.0-3.7e-4 to 3.4-3.8e-4 max-abs.
-                    p.n_id = 0;
-                    if (k == 2) {
-                        p.out_lo = plane(cat[nxt], 6, PL);
-                        p.n_id = 4;
-                        p.chunk_off[0] = r_off;              // R hi
-                        p.chunk_off[1] = r_off + PB;
-                        p.chunk_off[2] = r_off + 6 * PB;     // R lo
-                        p.chunk_off[3] = r_off + 7 * PB;
-                        for (int i = 0; i < 4; ++i) p.id_scale[i] = 25.f;
-                        if (n->abl_rdb3 & 1) {
-                            p.out_lo = nullptr;
-                        }
-                        if (n->abl_rdb3 & 2) p.n_id = 2;
-                        if ((n->abl_rdb3 & 6) == 6) p.n_id = 0;
-                        else if (n->abl_rdb3 & 4) {
-                            p.n_id = 2;
-                            p.chunk_off[0] = p.chunk_off[2];
-                            p.chunk_off[1] = p.chunk_off[3];
-                        }
-                    }
-                } else {
-                    p.out_lo = plane(cat[nxt], 6, PL);
-                    p.n_id = (k == 2) ? 6 : 2;
-                    p.chunk_off[0] = 6 * PB;
-                    p.chunk_off[1] = 7 * PB;
-                    p.id_scale[0] = p.id_scale[1] = 5.f;
-                    if (k == 2) {
-                        p.chunk_off[2] = r_off;              // R hi
-                        p.chunk_off[3] = r_off + PB;
-                        p.chunk_off[4] = r_off + 6 * PB;     // R lo
-                        p.chunk_off[5] = r_off + 7 * PB;
-                        for (int i = 2; i < 6; ++i) p.id_scale[i] = 25.f;
-                    }
-                }
-                p.s1 = (k == 2) ? 0.2f * 0.2f : 0.2f;
-                if (n->c5_wino && n->dt == DT_F16 && (p.n_id == 0 || n->c5_wino >= 2) && L[4].d_wwino && !(n->abl_alias & 2) && !n->abl_rdb3) {
-                    p.cin_chunks = L[4].chunks;
-                    p.wpk = L[4].d_wwino;
-                    p.bias = L[4].d_b;
-                    // algorithmic FLOPs: the nine-tap count
-                    timed(n, st, conv_flops(L[4], (size_t)p.H * p.W), [&] { launch_conv3x3_wino_split(p, st); });
-                } else {
-                    run_conv(n, L[4], EPI_RESIDUAL_SPLIT, p, st);
-                }
-            } else {
-                p.res1 = (k == 0) ? Rin : (k == 1 ? tA : tB);
-                if (k == 2) {
-                    p.res2 = Rin;
-                    p.s2 = 0.2f;
-                    p.out_f32 = R;
-                } else {
-                    p.out_f32 = (k == 0) ? tA : tB;
-                }
-                run_conv(n, L[4], EPI_RESIDUAL, p, st);
-            }
-            cur = nxt;
-        }
-    }
+    for (int b = 0; b < n->num_block; ++b) run_rrdb(n, T, b, b == 0 ? F : T.R, cur, st);
 
     // feat + conv_body(body_feat)                                                  (:256-257)
     {
@@ -480,6 +523,8 @@ const char* fw_last_error(void) { return fw::last_error_ref().c_str(); }
 int fw_abi_version(void) { return 4; }  // 2: + upscale_u16, resize_lanczos4, grain_addback, attention (softmax rows, transposed pack, MFMA Gram)
                                          // 3 (round 2, additive): + fw_ifnet_*, fw_restormer_*, fw_srvgg_*, fw_unsharp_mask_u8, fw_preserve_edges_*, fw_attn_proj_pack
                                          // 4 (additive): + fw_pack_conv3x3_wino, fw_conv3x3_split_nhwc, fw_conv3x3_wino_nhwc, fw_conv3x3_wino_check_fields
+                                         // still 4 (additive entries no longer bump it): + the single-step test hooks fw_nafnet_run_block, fw_restormer_run_block /
+                                         // run_step, fw_rrdbnet_run_rrdbs and their *_block_paths
 
 int fw_device_count(void) {
     int n = 0;
@@ -658,6 +703,57 @@ int fw_rrdbnet_upscale_u8(fw_rrdbnet* n, const uint8_t* in_bgr, int in_loc, int 
 int fw_rrdbnet_upscale_u16(fw_rrdbnet* n, const uint16_t* in_bgr, int in_loc, int H, int W, uint16_t* out_bgr,
                            int out_loc, float* out_rgb_f32, void* stream) {
     return upscale_any(n, in_bgr, in_loc, 16, H, W, out_bgr, out_loc, out_rgb_f32, stream, "fw_rrdbnet_upscale_u16");
+}
+
+// ---- RRDBs of the trunk on their own, for tests and tools: the launches a forward makes for them, on a caller's fp32 trunk ----
+int fw_rrdbnet_run_rrdbs(fw_rrdbnet* n, int first_block, int count, const float* trunk_in_f32, int Ht, int Wt, float* trunk_out_f32,
+                         void* growth_out, void* stream) {
+    if (!n || !trunk_in_f32 || !trunk_out_f32) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_rrdbs: NULL argument");
+    const int fs = n->scale == 2 ? 2 : 1;   // frame pixels per trunk pixel and side (the x2 model's trunk is half its frame)
+    if (Ht < 1 || Wt < 1 || Ht > 16384 / fs || Wt > 16384 / fs) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_rrdbs: bad trunk size");
+    if (first_block < 0 || count < 1 || first_block >= n->num_block || count > n->num_block - first_block)
+        return fail(FW_ERR_INVALID, "fw_rrdbnet_run_rrdbs: blocks " + std::to_string(first_block) + " .. " + std::to_string((long)first_block + count - 1) +
+                                        " are not all inside a net of " + std::to_string(n->num_block));
+    int rc = fw_rrdbnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        // the workspace of the forward whose trunk has Ht x Wt pixels
+        const Plan pl = make_plan(n, fs * Ht, fs * Wt);
+        ensure_workspace(n->ws, pl.total, &n->graphs);
+        const Trunk T = make_trunk(n, pl, Ht, Wt);
+        // what a forward holds on entering first_block: three RDBs per RRDB, each moving on by one buffer
+        int cur = 3 * first_block % T.ncat;
+        float* Rin = first_block == 0 ? T.F : T.R;
+        launch_trunk_from_f32(n->dt, trunk_in_f32, Ht, Wt, T.PL, T.cat[cur], n->split_trunk ? plane(T.cat[cur], 6, T.PL) : nullptr,
+                              n->split_trunk ? nullptr : Rin, st);
+        int last = cur;
+        for (int b = first_block; b < first_block + count; ++b) {
+            run_rrdb(n, T, b, b == 0 ? T.F : T.R, cur, st);
+            last = (cur + T.ncat - 1) % T.ncat;   // rdb3 ran in the buffer in front of the one it wrote to
+        }
+        launch_trunk_to_f32(n->dt, T.cat[cur], n->split_trunk ? plane(T.cat[cur], 6, T.PL) : nullptr, n->split_trunk ? nullptr : T.R, Ht, Wt, T.PL,
+                            trunk_out_f32, st);
+        if (growth_out)   // x1 .. x4 of the last RDB: planes 2-5 of its concat buffer, contiguous
+            FW_HIP_CHECK(hipMemcpyAsync(growth_out, plane(T.cat[last], 2, T.PL), (size_t)4 * T.PL * 2, hipMemcpyDeviceToDevice, st));
+    });
+}
+
+int fw_rrdbnet_block_paths(fw_rrdbnet* n, int* flags) {
+    if (!n || !flags) return fail(FW_ERR_INVALID, "fw_rrdbnet_block_paths: NULL argument");
+    int rc = fw_rrdbnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    std::lock_guard<std::mutex> lk(n->mu);
+    const ConvLayer* c5 = &n->body[4];   // conv5 of body.0.rdb1; every dense block has the same form
+    // pair_fused, c5_planes and c5_on_wino are what run_rrdb consults
+    *flags = (pair_fused(n, 0) ? FW_RRDB_PATH_PAIR12 : 0) | (pair_fused(n, 2) ? FW_RRDB_PATH_PAIR34 : 0) | (n->split_trunk ? FW_RRDB_PATH_SPLIT_TRUNK : 0) |
+             (n->split_trunk && n->rrdb_lo ? FW_RRDB_PATH_RRDB_LO : 0) |
+             (n->split_trunk && c5_on_wino(n, c5_planes(n, 0), c5[0]) ? FW_RRDB_PATH_C5_WINO_RDB12 : 0) |
+             (n->split_trunk && c5_on_wino(n, c5_planes(n, 2), c5[10]) ? FW_RRDB_PATH_C5_WINO_RDB3 : 0);
+    return FW_OK;
 }
 
 int fw_rrdbnet_profile_enable(fw_rrdbnet* n, int on) {

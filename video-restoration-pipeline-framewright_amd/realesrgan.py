@@ -199,6 +199,36 @@ class RRDBNetEngine(Engine):
             pending.append((k, ev_d))
         yield from drain(0)
 
+    # -- single steps of a forward (tests, tools) -----------------------------------------------------
+    @_lib.on_tensor_device
+    def run_rrdbs(self, trunk_in_f32, first_block: int, count: int, trunk_out_f32=None, growth_out=None):
+        """RRDBs ``first_block .. first_block + count - 1`` of the trunk on a contiguous float32 CUDA tensor H x W x 64, launched as
+        in a forward; returns the trunk behind them (float32 H x W x 64).  ``growth_out`` (int16 / float16 / bfloat16 CUDA,
+        4 x H x W x 32) receives x1 .. x4 of the last dense block in the operand type."""
+        import torch
+        for t, last in ((trunk_in_f32, 64), (trunk_out_f32, 64)):
+            if t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or t.shape[2] != last or not t.is_contiguous()):
+                raise ValueError("run_rrdbs expects contiguous float32 CUDA tensors H x W x 64")
+        h, w = int(trunk_in_f32.shape[0]), int(trunk_in_f32.shape[1])
+        if trunk_out_f32 is None:
+            trunk_out_f32 = torch.empty_like(trunk_in_f32)
+        if tuple(trunk_out_f32.shape) != (h, w, 64):
+            raise ValueError("run_rrdbs: trunk_out_f32 of the wrong shape")
+        if growth_out is not None and (not growth_out.is_cuda or not growth_out.is_contiguous() or growth_out.element_size() != 2 or
+                                       growth_out.numel() != 4 * h * w * 32):
+            raise ValueError("growth_out must be a contiguous 16-bit CUDA tensor 4 x H x W x 32")
+        with self._handle() as hd:
+            _lib.check(self._lib.fw_rrdbnet_run_rrdbs(hd, int(first_block), int(count), _lib.ptr(trunk_in_f32), h, w, _lib.ptr(trunk_out_f32),
+                                                      _lib.ptr(growth_out), _lib.stream_ptr(trunk_in_f32.device)))
+        return trunk_out_f32
+
+    def block_paths(self) -> int:
+        """FW_RRDB_PATH_* bits of the kernel forms this engine's RRDBs dispatch to."""
+        flags = C.c_int(0)
+        with self._handle() as hd:
+            _lib.check(self._lib.fw_rrdbnet_block_paths(hd, C.byref(flags)))
+        return flags.value
+
     # -- introspection ------------------------------------------------------------------------------
     def flops(self, height: int, width: int) -> float:
         with self._handle() as hd:
