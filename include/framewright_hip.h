@@ -135,6 +135,35 @@ int fw_rrdbnet_run_rrdbs(fw_rrdbnet* net, int first_block, int count, const floa
                          float* trunk_out_f32, void* growth_out, void* stream);
 int fw_rrdbnet_block_paths(fw_rrdbnet* net, int* flags);
 
+/* The two ends of a forward on their own, on the caller's device buffers (tests, tools): the same launches, workspace, mutex and
+ * stream ordering as fw_rrdbnet_upscale_u8 / _u16 makes in front of RRDB 0 and behind the last RRDB.  run_head, run_rrdbs over
+ * every block and run_tail together are the forward.
+ * run_head: frame -> NHWC (bits 8: uint8 BGR / 255; bits 16: uint16 BGR / 65535; the x2 model's reflect mod-pad and pixel-unshuffle)
+ *   and conv_first on a device frame of height x width pixels.  trunk_out_f32: device fp32 [Ht][Wt][64] at the trunk's resolution
+ *   (the frame's; the x2 model's: ceil(height / 2) x ceil(width / 2)), what RRDB 0 reads - float(hi) + float(lo) of the typed planes,
+ *   or the fp32 trunk.  feat_out_f32: the same shape, conv_first's fp32 output as conv_body adds it later.
+ * run_tail: conv_body + feat, the two up-convs, conv_hr and conv_last from a trunk of trunk_height x trunk_width pixels.  trunk_f32:
+ *   device fp32 [trunk_height][trunk_width][64], laid into the concat buffer a forward holds behind its last RRDB (3 * num_block mod
+ *   the buffers in rotation) as run_rrdbs lays in - or NULL: that buffer is read as it stands, which after a run_rrdbs through the
+ *   last block on a trunk of the same size (same handle, nothing in between; the uncropped image only, whose frame's workspace
+ *   run_rrdbs works in) is the trunk itself, typed pair for typed pair: the fp32
+ *   sum of hi + lo does not say which pair it was where it lies half-way between two numbers of the operand type, and conv_body
+ *   reads hi alone.  feat_f32: the same shape, laid into conv_first's fp32 buffer.  img_height x
+ *   img_width: the image, scale x a frame whose trunk has that size (the x2 model crops its mod-pad: 4 * trunk - 2 or 4 * trunk per
+ *   side).  out_bgr: device, uint8 (bits 8) or uint16 (bits 16) BGR [img_height][img_width][3]; out_rgb_f32: device fp32 RGB of the
+ *   same shape, the un-clamped network output; either may be NULL, not both.
+ * tail_paths: which kernel forms the tail dispatches to on a trunk of that size, as FW_RRDB_TAIL_* bits.
+ * FW_ERR_INVALID: NULL arguments, a handle that is not finalised, bits other than 8 or 16, a size outside a forward's range, an x2
+ *   frame under 2 x 2, an image that is not the output of a frame with that trunk. */
+#define FW_RRDB_TAIL_UP_PHASE 1   /* conv_up1 / conv_up2 as four 2x2 phase convolutions on the source grid */
+#define FW_RRDB_TAIL_FUSED 2      /* conv_hr + conv_last in one launch (depends on the size when FW_RRDB_HR_LAST is unset) */
+#define FW_RRDB_TAIL_HR_WINO 4    /* conv_hr as row-wise Winograd F(2, 3) */
+int fw_rrdbnet_run_head(fw_rrdbnet* net, const void* in_bgr, int bits, int height, int width, float* trunk_out_f32,
+                        float* feat_out_f32, void* stream);
+int fw_rrdbnet_run_tail(fw_rrdbnet* net, const float* feat_f32, const float* trunk_f32, int trunk_height, int trunk_width,
+                        int img_height, int img_width, int bits, void* out_bgr, float* out_rgb_f32, void* stream);
+int fw_rrdbnet_tail_paths(fw_rrdbnet* net, int trunk_height, int trunk_width, int* flags);
+
 /* Release device memory.  NULL is allowed. */
 int fw_rrdbnet_destroy(fw_rrdbnet* net);
 

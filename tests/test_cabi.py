@@ -92,6 +92,7 @@ def test_constants_are_the_headers_defines():
             _lib.FW_REST_PATH_GEMM16) == (1, 2, 4, 8, 16)
     assert (_lib.FW_RRDB_PATH_PAIR12, _lib.FW_RRDB_PATH_PAIR34, _lib.FW_RRDB_PATH_SPLIT_TRUNK, _lib.FW_RRDB_PATH_RRDB_LO,
             _lib.FW_RRDB_PATH_C5_WINO_RDB12, _lib.FW_RRDB_PATH_C5_WINO_RDB3) == (1, 2, 4, 8, 16, 32)
+    assert (_lib.FW_RRDB_TAIL_UP_PHASE, _lib.FW_RRDB_TAIL_FUSED, _lib.FW_RRDB_TAIL_HR_WINO) == (1, 2, 4)
 
 
 # full signatures written out by hand from the header's prototypes, not derived by the reader
@@ -102,6 +103,9 @@ PINNED = {
     "fw_rrdbnet_profile_read": (I32, [VP, C.POINTER(I32), C.POINTER(F64), C.POINTER(F64)]),
     "fw_rrdbnet_run_rrdbs": (I32, [VP, I32, I32, VP, I32, I32, VP, VP, VP]),
     "fw_rrdbnet_block_paths": (I32, [VP, C.POINTER(I32)]),
+    "fw_rrdbnet_run_head": (I32, [VP, VP, I32, I32, I32, VP, VP, VP]),
+    "fw_rrdbnet_run_tail": (I32, [VP, VP, VP, I32, I32, I32, I32, I32, VP, VP, VP]),
+    "fw_rrdbnet_tail_paths": (I32, [VP, I32, I32, C.POINTER(I32)]),
     "fw_conv3x3_nhwc": (I32, [I32, VP, I32, I64, I32, I32, I32, VP, VP, I32, I32, I32, VP, F32, VP, F32, VP, I32, I64, I32, VP, VP]),
     "fw_conv3x3_split_nhwc": (I32, [I32, I32, VP, I32, I64, I32, I32, I32, VP, VP, F32, F32, I32, C.POINTER(I64), C.POINTER(F32), I32,
                                     VP, VP, I32, I64, I32, VP]),

@@ -5,7 +5,8 @@ FW_RRDB_HR_LAST (1 against 0, against the fp32 oracle, and replayed from a hipGr
 Op-level bound on the float planes: |fused - unfused| <= 2^-17 S per sample, S = |b| + sum |W_last| |h| in float64 from the
 unfused call's own 64-channel map h.  Each path rounds fewer than 64 partial sums, each bounded by S, to fp32 (2^-24 relative
 each); two fp32 orders of this sum on the CPU differ by at most 0.034 of the bound.  One f16 rounding flip in h moves a term by
-2^-11 of its size and breaks it, so the bound also says that conv_hr's K loop kept its summation order."""
+2^-11 of its size and breaks it, so the bound also says that conv_hr's K loop kept its summation order.  The unfused form, the
+reference here, gets a float64 reference of its own in tests/test_rrdb_tail_ops_gpu.py."""
 import ctypes as C
 
 import numpy as np

@@ -515,7 +515,7 @@ __global__ void trunk_from_f32_kernel(const float* __restrict__ src, int H, int 
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (inside) v = *reinterpret_cast<const f32x4*>(src + ((size_t)y * W + x) * 64 + 4 * g);
         if (native) *reinterpret_cast<f32x4*>(native + f32_native_offset_of(y, x, g, H, W, 4)) = v;   // zeros in the padding
-        if (!inside) continue;
+        if (!inside || !hi) continue;   // (hi == NULL: the fp32 buffer alone)
         const size_t to = (size_t)(g >> 3) * pstride + ((size_t)y * W + x) * 32 + 4 * (g & 7);
         const uint2 h = Op<T>::pack4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<uint2*>(hi + to) = h;

@@ -80,8 +80,8 @@ struct ConvParams {
 // Number of floats of an accumulator-native fp32 side buffer for an H x W problem with 32*cout_tiles channels:
 // [tile][wave][row][ct][g][lane][4] over the padded 16x32 tile grid.
 size_t f32_native_elems(int H, int W, int cout_tiles);
-// A 64-channel fp32 NHWC map into / out of the RRDB trunk's representations (conv3x3_mfma.hip; fw_rrdbnet_run_rrdbs).  hi / lo: typed
-// planes [2][H][W][32], pstride elements apart, hi = T(x), lo = T(x - float(hi)) as the conv epilogue defines out_lo (lo may be null);
+// A 64-channel fp32 NHWC map into / out of the RRDB trunk's representations (conv3x3_mfma.hip; fw_rrdbnet_run_rrdbs, run_head, run_tail).  hi / lo: typed
+// planes [2][H][W][32], pstride elements apart, hi = T(x), lo = T(x - float(hi)) as the conv epilogue defines out_lo (lo may be null; hi too, for the fp32 buffer alone);
 // native: an accumulator-native fp32 buffer of f32_native_elems(H, W, 2) floats (may be null), zeros in its padding.
 void launch_trunk_from_f32(DType dt, const float* src, int H, int W, long pstride, void* hi, void* lo, float* native, hipStream_t st);
 // dst = native where given, else float(hi) + float(lo)

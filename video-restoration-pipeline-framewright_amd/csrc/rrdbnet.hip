@@ -384,39 +384,51 @@ void run_rrdb(fw_rrdbnet* n, const Trunk& T, int b, const float* Rin, int& cur, 
     }
 }
 
-// bits = 8: d_in / d_out are uint8 BGR; bits = 16: uint16 BGR (range 65535)
-void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_out, float* d_rgb, hipStream_t st) {
-    int Ht, Wt;
-    trunk_size(n, H, W, &Ht, &Wt);
-    const Plan pl = make_plan(n, H, W);
+// The two ends of a forward in the handle's workspace, as forward(), fw_rrdbnet_run_head and fw_rrdbnet_run_tail see them
+struct Ends {
+    void *in32 = nullptr, *U1 = nullptr, *U2 = nullptr, *U3 = nullptr;
+};
+
+Ends make_ends(const fw_rrdbnet* n, const Plan& pl) {
     char* ws = (char*)n->ws.p;
-    void* in32 = ws + pl.in32;
-    const Trunk T = make_trunk(n, pl, Ht, Wt);
+    Ends E;
+    E.in32 = ws + pl.in32;
+    E.U1 = ws + pl.U1;
+    E.U2 = ws + pl.U2;
+    E.U3 = ws + pl.U3;
+    return E;
+}
+
+// whether an up-conv runs as four 2x2 phase convolutions, conv_hr in the Winograd form, and conv_hr + conv_last as one launch on a
+// trunk of Ht x Wt pixels: the one place that decides each, for run_tail and for fw_rrdbnet_tail_paths
+bool up_on_phase(const fw_rrdbnet* n, const ConvLayer& l) { return n->up_phase && l.d_wphase; }
+bool hr_on_wino(const fw_rrdbnet* n) { return n->c5_wino && n->dt == DT_F16 && n->conv_hr.d_wwino && n->hr_wino; }
+bool tail_fused(const fw_rrdbnet* n, int Ht, int Wt) {
+    return !hr_on_wino(n) && (n->hr_last < 0 ? hr_last_default(4 * Ht, 4 * Wt) : n->hr_last != 0);
+}
+
+// The head of a forward: frame -> NHWC, conv_first -> concat buffer 0 [0:64] (split trunk: + its lo planes) and the fp32 trunk F.
+// bits = 8: d_in is uint8 BGR; bits = 16: uint16 BGR (range 65535)
+void run_head(fw_rrdbnet* n, const Trunk& T, const Ends& E, const void* d_in, int bits, int H, int W, hipStream_t st) {
+    launch_frame_to_nhwc(n->dt, d_in, bits, H, W, E.in32, 32, n->scale == 2 ? 2 : 1, st);
+    // conv_first -> concat buffer 0 [0:64] + fp32 trunk F          (aesrgan_face.py:250)
+    ConvParams p = T.base;
+    p.in = E.in32;
+    p.out = T.cat[0];
+    p.out_f32 = T.F;
+    if (n->split_trunk) p.out_lo = plane(T.cat[0], 6, T.PL);
+    run_conv(n, n->conv_first, EPI_STORE, p, st);
+}
+
+// The tail of a forward: from the trunk behind the last RRDB in concat buffer `cur` and conv_first's fp32 output F to the image of
+// img_H x img_W pixels (bits = 8: d_out is uint8 BGR; bits = 16: uint16 BGR) and / or the float RGB plane.
+void run_tail(fw_rrdbnet* n, const Trunk& T, const Ends& E, int cur, int bits, int img_H, int img_W, void* d_out, float* d_rgb, hipStream_t st) {
     void* const* cat = T.cat;
-    const int ncat = T.ncat;
-    float* F = T.F;
-    void* U1 = ws + pl.U1;
-    void* U2 = ws + pl.U2;
-    void* U3 = ws + pl.U3;
-
-    launch_frame_to_nhwc(n->dt, d_in, bits, H, W, in32, 32, n->scale == 2 ? 2 : 1, st);
-
+    const int ncat = T.ncat, Ht = T.Ht, Wt = T.Wt;
     const long PL = T.PL;
     const ConvParams& base = T.base;
-
-    // conv_first -> concat buffer 0 [0:64] + fp32 trunk F          (aesrgan_face.py:250)
-    {
-        ConvParams p = base;
-        p.in = in32;
-        p.out = cat[0];
-        p.out_f32 = F;
-        if (n->split_trunk) p.out_lo = plane(cat[0], 6, PL);
-        run_conv(n, n->conv_first, EPI_STORE, p, st);
-    }
-
-    int cur = 0;
-    for (int b = 0; b < n->num_block; ++b) run_rrdb(n, T, b, b == 0 ? F : T.R, cur, st);
-
+    float* F = T.F;
+    void *U1 = E.U1, *U2 = E.U2, *U3 = E.U3;
     // feat + conv_body(body_feat)                                                  (:256-257)
     {
         ConvParams p = base;
@@ -429,7 +441,7 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     }
     // lrelu(conv_up1(nearest x2)), lrelu(conv_up2(nearest x2))                    (:260-266)
     auto run_up = [&](const ConvLayer& l, const void* src, long src_pstride, int Hs, int Ws, void* dst, long dst_pstride) {
-        if (n->up_phase && l.d_wphase) {
+        if (up_on_phase(n, l)) {
             ConvUpParams u{};
             u.in = src;
             u.in_cstride = 32;
@@ -473,10 +485,10 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     else
         img.out_u8 = (uint8_t*)d_out;
     img.out_rgb = d_rgb;
-    img.img_H = n->scale * H;  // crops the mod-pad of the x2 model
-    img.img_W = n->scale * W;
-    const bool hr_wino = n->c5_wino && n->dt == DT_F16 && n->conv_hr.d_wwino && n->hr_wino;
-    if (!hr_wino && (n->hr_last < 0 ? hr_last_default(hr.H, hr.W) : n->hr_last != 0)) {
+    img.img_H = img_H;  // crops the mod-pad of the x2 model
+    img.img_W = img_W;
+    const bool hr_wino = hr_on_wino(n);
+    if (tail_fused(n, Ht, Wt)) {
         // one launch, U3 never written: the algorithmic FLOPs of both convs
         ConvParams p = hr;
         p.out_u8 = img.out_u8;
@@ -514,6 +526,19 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
     }
 }
 
+// bits = 8: d_in / d_out are uint8 BGR; bits = 16: uint16 BGR (range 65535)
+void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_out, float* d_rgb, hipStream_t st) {
+    int Ht, Wt;
+    trunk_size(n, H, W, &Ht, &Wt);
+    const Plan pl = make_plan(n, H, W);
+    const Trunk T = make_trunk(n, pl, Ht, Wt);
+    const Ends E = make_ends(n, pl);
+    run_head(n, T, E, d_in, bits, H, W, st);
+    int cur = 0;
+    for (int b = 0; b < n->num_block; ++b) run_rrdb(n, T, b, b == 0 ? T.F : T.R, cur, st);
+    run_tail(n, T, E, cur, bits, n->scale * H, n->scale * W, d_out, d_rgb, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -524,7 +549,7 @@ int fw_abi_version(void) { return 4; }  // 2: + upscale_u16, resize_lanczos4, gr
                                          // 3 (round 2, additive): + fw_ifnet_*, fw_restormer_*, fw_srvgg_*, fw_unsharp_mask_u8, fw_preserve_edges_*, fw_attn_proj_pack
                                          // 4 (additive): + fw_pack_conv3x3_wino, fw_conv3x3_split_nhwc, fw_conv3x3_wino_nhwc, fw_conv3x3_wino_check_fields
                                          // still 4 (additive entries no longer bump it): + the single-step test hooks fw_nafnet_run_block, fw_restormer_run_block /
-                                         // run_step, fw_rrdbnet_run_rrdbs and their *_block_paths
+                                         // run_step, fw_rrdbnet_run_rrdbs / run_head / run_tail and their *_paths
 
 int fw_device_count(void) {
     int n = 0;
@@ -753,6 +778,84 @@ int fw_rrdbnet_block_paths(fw_rrdbnet* n, int* flags) {
              (n->split_trunk && n->rrdb_lo ? FW_RRDB_PATH_RRDB_LO : 0) |
              (n->split_trunk && c5_on_wino(n, c5_planes(n, 0), c5[0]) ? FW_RRDB_PATH_C5_WINO_RDB12 : 0) |
              (n->split_trunk && c5_on_wino(n, c5_planes(n, 2), c5[10]) ? FW_RRDB_PATH_C5_WINO_RDB3 : 0);
+    return FW_OK;
+}
+
+// ---- the two ends of a forward on their own, for tests and tools: the launches a forward makes in front of RRDB 0 and behind the last ----
+int fw_rrdbnet_run_head(fw_rrdbnet* n, const void* in_bgr, int bits, int H, int W, float* trunk_out_f32, float* feat_out_f32, void* stream) {
+    if (!n || !in_bgr || !trunk_out_f32 || !feat_out_f32) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_head: NULL argument");
+    if (bits != 8 && bits != 16) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_head: 8- or 16-bit samples expected");
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_head: bad frame size");
+    if (n->scale == 2 && (H < 2 || W < 2)) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_head: x2 needs >= 2x2 input");
+    int rc = fw_rrdbnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        int Ht, Wt;
+        trunk_size(n, H, W, &Ht, &Wt);
+        const Plan pl = make_plan(n, H, W);
+        ensure_workspace(n->ws, pl.total, &n->graphs);
+        const Trunk T = make_trunk(n, pl, Ht, Wt);
+        run_head(n, T, make_ends(n, pl), in_bgr, bits, H, W, st);
+        // what RRDB 0 reads: the planes of concat buffer 0, or the fp32 trunk F; and F itself, which conv_body adds later
+        launch_trunk_to_f32(n->dt, T.cat[0], n->split_trunk ? plane(T.cat[0], 6, T.PL) : nullptr, n->split_trunk ? nullptr : T.F, Ht, Wt, T.PL,
+                            trunk_out_f32, st);
+        launch_trunk_to_f32(n->dt, nullptr, nullptr, T.F, Ht, Wt, T.PL, feat_out_f32, st);
+    });
+}
+
+int fw_rrdbnet_run_tail(fw_rrdbnet* n, const float* feat_f32, const float* trunk_f32, int Ht, int Wt, int img_H, int img_W, int bits, void* out_bgr,
+                        float* out_rgb_f32, void* stream) {
+    if (!n || !feat_f32) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_tail: NULL argument");
+    if (!out_bgr && !out_rgb_f32) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_tail: no output requested");
+    if (bits != 8 && bits != 16) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_tail: 8- or 16-bit samples expected");
+    const int fs = n->scale == 2 ? 2 : 1;   // frame pixels per trunk pixel and side
+    if (Ht < 1 || Wt < 1 || Ht > 16384 / fs || Wt > 16384 / fs) return fail(FW_ERR_INVALID, "fw_rrdbnet_run_tail: bad trunk size");
+    // the image of a frame whose trunk has Ht x Wt pixels: scale x the frame, and the x2 model's frame may be one short of 2 x its trunk
+    const int H = img_H / n->scale, W = img_W / n->scale;
+    int Hc = 0, Wc = 0;
+    if (img_H >= n->scale && img_W >= n->scale && (n->scale != 2 || (H >= 2 && W >= 2))) trunk_size(n, H, W, &Hc, &Wc);
+    if (img_H < 1 || img_W < 1 || img_H % n->scale || img_W % n->scale || Hc != Ht || Wc != Wt)
+        return fail(FW_ERR_INVALID, "fw_rrdbnet_run_tail: bad image size: " + std::to_string(img_H) + " x " + std::to_string(img_W) +
+                                        " is not the output of a frame whose trunk has " + std::to_string(Ht) + " x " + std::to_string(Wt) + " pixels");
+    // run_rrdbs works in the workspace of the frame that fills its trunk: only that frame's tail finds the trunk where it was left
+    if (!trunk_f32 && (img_H != 4 * Ht || img_W != 4 * Wt))
+        return fail(FW_ERR_INVALID, "fw_rrdbnet_run_tail: the trunk left by run_rrdbs serves the uncropped image alone (bad image size)");
+    int rc = fw_rrdbnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(n->mu);
+        DevGuard dg(n->device);
+        hipStream_t st = (hipStream_t)stream;
+        StreamOrder::Scope in_order(n->order, st);
+        const Plan pl = make_plan(n, H, W);
+        ensure_workspace(n->ws, pl.total, &n->graphs);
+        const Trunk T = make_trunk(n, pl, Ht, Wt);
+        // the buffer a forward holds behind its last RRDB: three RDBs per RRDB, each moving on by one buffer
+        const int cur = 3 * n->num_block % T.ncat;
+        // (trunk_f32 == NULL: the buffer as fw_rrdbnet_run_rrdbs through the last block left it - the typed planes themselves, where the
+        // fp32 sum of a hi + lo pair cannot say which pair it was when it lies half-way between two numbers of the operand type)
+        if (trunk_f32)
+            launch_trunk_from_f32(n->dt, trunk_f32, Ht, Wt, T.PL, T.cat[cur], n->split_trunk ? plane(T.cat[cur], 6, T.PL) : nullptr,
+                                  n->split_trunk ? nullptr : T.R, st);
+        launch_trunk_from_f32(n->dt, feat_f32, Ht, Wt, T.PL, nullptr, nullptr, T.F, st);   // conv_first's fp32 output alone
+        run_tail(n, T, make_ends(n, pl), cur, bits, img_H, img_W, out_bgr, out_rgb_f32, st);
+    });
+}
+
+int fw_rrdbnet_tail_paths(fw_rrdbnet* n, int Ht, int Wt, int* flags) {
+    if (!n || !flags) return fail(FW_ERR_INVALID, "fw_rrdbnet_tail_paths: NULL argument");
+    const int fs = n->scale == 2 ? 2 : 1;
+    if (Ht < 1 || Wt < 1 || Ht > 16384 / fs || Wt > 16384 / fs) return fail(FW_ERR_INVALID, "fw_rrdbnet_tail_paths: bad trunk size");
+    int rc = fw_rrdbnet_finalize(n);
+    if (rc != FW_OK) return rc;
+    std::lock_guard<std::mutex> lk(n->mu);
+    // up_on_phase, tail_fused and hr_on_wino are what run_tail consults
+    *flags = (up_on_phase(n, n->conv_up1) && up_on_phase(n, n->conv_up2) ? FW_RRDB_TAIL_UP_PHASE : 0) | (tail_fused(n, Ht, Wt) ? FW_RRDB_TAIL_FUSED : 0) |
+             (hr_on_wino(n) ? FW_RRDB_TAIL_HR_WINO : 0);
     return FW_OK;
 }
 

@@ -229,6 +229,60 @@ class RRDBNetEngine(Engine):
             _lib.check(self._lib.fw_rrdbnet_block_paths(hd, C.byref(flags)))
         return flags.value
 
+    @_lib.on_tensor_device
+    def run_head(self, frame_bgr, trunk_out_f32=None, feat_out_f32=None):
+        """What a forward runs in front of RRDB 0 on a contiguous uint8 or int16 / uint16 (16-bit samples) CUDA frame H x W x 3:
+        returns (what RRDB 0 reads, conv_first's fp32 output), both float32 Ht x Wt x 64 at the trunk's resolution."""
+        import torch
+        if not frame_bgr.is_cuda or frame_bgr.dim() != 3 or frame_bgr.shape[2] != 3 or not frame_bgr.is_contiguous() or \
+                frame_bgr.dtype not in (torch.uint8, torch.int16, torch.uint16):
+            raise ValueError("run_head expects a contiguous uint8, int16 or uint16 CUDA frame H x W x 3")
+        h, w = int(frame_bgr.shape[0]), int(frame_bgr.shape[1])
+        ht, wt = ((h + 1) // 2, (w + 1) // 2) if self.scale == 2 else (h, w)
+        outs = []
+        for t in (trunk_out_f32, feat_out_f32):
+            if t is None:
+                t = torch.empty((ht, wt, 64), dtype=torch.float32, device=frame_bgr.device)
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (ht, wt, 64):
+                raise ValueError(f"run_head writes contiguous float32 CUDA tensors {ht} x {wt} x 64")
+            outs.append(t)
+        with self._handle() as hd:
+            _lib.check(self._lib.fw_rrdbnet_run_head(hd, _lib.ptr(frame_bgr), 8 * frame_bgr.element_size(), h, w, _lib.ptr(outs[0]), _lib.ptr(outs[1]),
+                                                     _lib.stream_ptr(frame_bgr.device)))
+        return outs[0], outs[1]
+
+    @_lib.on_tensor_device
+    def run_tail(self, feat_f32, trunk_f32, img_height: int, img_width: int, out_bgr=None, out_rgb_f32=None):
+        """What a forward runs behind its last RRDB, on contiguous float32 CUDA tensors Ht x Wt x 64 (conv_first's output, the trunk):
+        the image ``out_bgr`` (uint8, or int16 / uint16 for 16-bit samples, img_height x img_width x 3) and / or the float RGB plane.
+        ``trunk_f32`` None: the trunk as a ``run_rrdbs`` through the last block, just before on this engine at this size, left it."""
+        import torch
+        for t in (feat_f32,) if trunk_f32 is None else (feat_f32, trunk_f32):
+            if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or t.shape[2] != 64 or not t.is_contiguous() or t.shape != feat_f32.shape:
+                raise ValueError("run_tail expects contiguous float32 CUDA tensors Ht x Wt x 64")
+        if out_bgr is None and out_rgb_f32 is None:
+            out_rgb_f32 = torch.empty((img_height, img_width, 3), dtype=torch.float32, device=feat_f32.device)
+        n = int(img_height) * int(img_width) * 3
+        if out_bgr is not None and (not out_bgr.is_cuda or not out_bgr.is_contiguous() or out_bgr.dtype not in (torch.uint8, torch.int16, torch.uint16) or
+                                    out_bgr.numel() != n):
+            raise ValueError("out_bgr must be a contiguous uint8, int16 or uint16 CUDA tensor img_height x img_width x 3")
+        if out_rgb_f32 is not None and (out_rgb_f32.dtype != torch.float32 or not out_rgb_f32.is_cuda or not out_rgb_f32.is_contiguous() or
+                                        out_rgb_f32.numel() != n):
+            raise ValueError("out_rgb_f32 must be a contiguous float32 CUDA tensor img_height x img_width x 3")
+        bits = 8 * out_bgr.element_size() if out_bgr is not None else 8
+        with self._handle() as hd:
+            _lib.check(self._lib.fw_rrdbnet_run_tail(hd, _lib.ptr(feat_f32), _lib.ptr(trunk_f32), int(feat_f32.shape[0]), int(feat_f32.shape[1]),
+                                                     int(img_height), int(img_width), bits, _lib.ptr(out_bgr), _lib.ptr(out_rgb_f32),
+                                                     _lib.stream_ptr(feat_f32.device)))
+        return out_bgr if out_bgr is not None else out_rgb_f32
+
+    def tail_paths(self, trunk_height: int, trunk_width: int) -> int:
+        """FW_RRDB_TAIL_* bits of the kernel forms this engine's tail dispatches to on a trunk of that size."""
+        flags = C.c_int(0)
+        with self._handle() as hd:
+            _lib.check(self._lib.fw_rrdbnet_tail_paths(hd, int(trunk_height), int(trunk_width), C.byref(flags)))
+        return flags.value
+
     # -- introspection ------------------------------------------------------------------------------
     def flops(self, height: int, width: int) -> float:
         with self._handle() as hd:
