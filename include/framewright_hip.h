@@ -1070,6 +1070,38 @@ int fw_qp_artifacts_u8(const uint8_t* frame, uint8_t* out, int height, int width
                        const float* gauss15, double strength, int block_size, int type_mask, const float* noise, const float* noise_table,
                        uint64_t noise_key, void* scratch, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Missing-frame generation (csrc/frame_generation.hip, DESIGN K22): the frame methods of the reference's
+ * processors/frame_generation.py on uint8 BGR H x W x 3 DEVICE frames; tests/frame_generation_ref.py is the contract, byte for
+ * byte.  Device pointers, caller-owned scratch, explicit stream; nothing is allocated and nothing synchronises.
+ *   fw_framegen_warp_blend_u8: one frame of `_generate_optical_flow` behind its two Farneback flows (float32 H x W planes, cv2's
+ *     convention): map = grid + flow * t in float32 (product, then sum), the other frame with 1 - t; both sampled with the 1 / 32
+ *     pixel INTER_LINEAR arithmetic and BORDER_REFLECT at any distance; out = addWeighted(warped_before, 1 - t, warped_after, t).
+ *   fw_framegen_grain_std_u8: *std_out = the population standard deviation of gray - GaussianBlur(gray, (0, 0), 2) in float32 (17
+ *     taps, REFLECT_101, rows then columns, acc += p[k] * c[k] left to right), reduced in float64 through per-workgroup partials in a
+ *     fixed order (no atomics: the same bits on every run) and rounded once.  gauss17: HOST float32 [17].  scratch:
+ *     fw_framegen_grain_scratch_bytes(height, width) bytes, 8-byte aligned.  Sides of 16 pixels or more.
+ *   fw_framegen_finish_u8: the grain (ref_std, cur_std: DEVICE float32 scalars, both NULL: no grain step), where *cur_std > 0 and
+ *     *ref_std > *cur_std: trunc(clip(float32(v) + z * float64(*ref_std - *cur_std), 0, 255)) with one z a pixel for its three
+ *     channels, z = draws[pixel] (DEVICE float64 H x W) where draws is not NULL, else quantiles[mix64(noise_key + pixel) >> 48]
+ *     (DEVICE float64 [65536], standard-normal quantiles at (k + 0.5) / 65536); then addWeighted(before, 1 - alpha_before, v,
+ *     alpha_before) where before is not NULL, then the same against after.  out may be generated itself.
+ *   fw_framegen_extrapolate_u8: one frame of `_extrapolate_frames`: trunc(clip(float32(reference) + noise, 0, 255)); noise (float32
+ *     H x W x 3) where it is not NULL, else noise_table[mix64(noise_key + pixel * 3 + channel) >> 48] (float32 [65536]: 2 x the
+ *     quantiles).
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, a side outside 1 .. 16384 (16 .. 16384 for the
+ * statistic), t outside (0, 1), a non-finite alpha of a blend that is due, misaligned float buffers, an out that overlaps a source
+ * frame (other than fw_framegen_finish_u8's out == generated).  fw_framegen_grain_scratch_bytes returns 0 on invalid arguments. */
+int fw_framegen_warp_blend_u8(const uint8_t* before, const uint8_t* after, const float* fwd_x, const float* fwd_y, const float* bwd_x,
+                              const float* bwd_y, int height, int width, double t, uint8_t* out, void* stream);
+size_t fw_framegen_grain_scratch_bytes(int height, int width);
+int fw_framegen_grain_std_u8(const uint8_t* frame, int height, int width, const float* gauss17, void* scratch, float* std_out, void* stream);
+int fw_framegen_finish_u8(const uint8_t* generated, uint8_t* out, int height, int width, const float* ref_std, const float* cur_std,
+                          const double* draws, const double* quantiles, uint64_t noise_key, const uint8_t* before, double alpha_before,
+                          const uint8_t* after, double alpha_after, void* stream);
+int fw_framegen_extrapolate_u8(const uint8_t* reference, uint8_t* out, int height, int width, const float* noise, const float* noise_table,
+                               uint64_t noise_key, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

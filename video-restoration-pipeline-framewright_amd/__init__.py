@@ -16,3 +16,5 @@ from .hdr import (ColorSpace, DeviceHDRConverter, HDRConfig, HDRConversionResult
                   create_hdr_converter)
 from .qp_artifacts import (ArtifactType, CompressionLevel, DeviceQPArtifactRemover, QPArtifactConfig, QPArtifactResult,  # noqa: E402,F401
                            create_qp_artifact_remover)
+from .frame_generation import (DeviceMissingFrameGenerator, FrameGenerationConfig, FrameGenerationResult, GapInfo,  # noqa: E402,F401
+                               GenerationModel, create_frame_generator)

@@ -220,12 +220,6 @@ __global__ __launch_bounds__(QA_NT) void band_rows_kernel(const float* __restric
     }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {                     // the splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // the column pass, then trunc(clip(float32(frame) + (noise * mask) * strength, 0, 255)): the product float32, the rest float64
 __global__ __launch_bounds__(QA_NT) void band_dither_kernel(const uint8_t* __restrict__ frame, const float* __restrict__ rows, int H, int W,
                                                             Gauss15 g, double strength, const float* __restrict__ noise,

@@ -1,5 +1,5 @@
 // Scaffolding shared by the frame-stage files (scene_cuts, dedup_hash, optical_flow, nlmeans, temporal_chain, flicker, color_lut,
-// deinterlace, vhs, hdr, qp_artifacts .hip, and frame_ops.hip for the device helpers and for the C entries of its own launchers): the status / last-error mapping of the C-ABI (fw_status.h:
+// deinterlace, vhs, hdr, qp_artifacts, frame_generation .hip, and frame_ops.hip for the device helpers and for the C entries of its own launchers): the status / last-error mapping of the C-ABI (fw_status.h:
 // fail, invalid, hip_status, guarded), the 64-lane reductions, the small integer device helpers every stage restated, and the host
 // checks of a call's frames.  A new stage includes this header and declares none of these again.
 // The translation units that include it differ in their floating-point flags, so nothing here is floating-point arithmetic whose
@@ -56,6 +56,14 @@ __device__ __forceinline__ int reflect101(int p, int len) {
     if (len == 1) return 0;
     while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - p - 2;
     return p;
+}
+
+// the splitmix64 finaliser: the counter-based noise of qp_artifacts.hip and frame_generation.hip is
+// table[mix64(key + element) >> 48], with tests/qp_artifact_ref.py's host-mixed key
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
 }
 
 // ---- host: the frames of a call --------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "stage_common.h"
+#include "add_weighted.h"
 #include "flow_accumulate.h"
 
 namespace fw {
@@ -78,11 +79,6 @@ __global__ __launch_bounds__(256) void flow_accumulate_affine_kernel(const uint8
                                                                      double* acc, double* wsum) {
     flow_accumulate_pixels(frame, fx, fy, inverse, H, W, acc, wsum,
                            [=](long i) { return conf ? w_const + w_conf * (double)conf[i] : w_const; });
-}
-
-__device__ __forceinline__ uint32_t aw_byte(uint32_t a, float alpha, uint32_t b, float beta) {
-    const float t = (float)a * alpha + (float)b * beta;       // three roundings (no contraction in this file)
-    return (uint32_t)fminf(fmaxf(rintf(t), 0.0f), 255.0f);     // round half to even, saturate
 }
 
 // words: how many leading 4-byte groups go through 32-bit loads and stores (0 unless all three pointers are 4-byte aligned)

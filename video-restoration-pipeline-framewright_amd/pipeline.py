@@ -60,12 +60,19 @@ class DeviceRestorationPipeline:
     the bar crop and in front of the denoiser, where the reference has its step 5c in front of 5d, with the quantisation parameter
     ``artifact_qp`` (None: the remover's `manual_qp`, then 28).  It works frame by frame and its dither is keyed by the frame's position
     in the clip, so the streaming forms (`DeviceQPArtifactRemover.stream`) equal `run_device`.
+
+    ``frame_generator`` (a `frame_generation.DeviceMissingFrameGenerator`; opt-in) fills the gaps in the frame numbering behind the
+    denoiser and in front of the upscale and its deduplicator, where the reference has its step 5f, when the call names the frames'
+    numbers (``frame_numbers``; ``expected_frames`` adds the gap behind the last frame).  The numbers are those of the frames that
+    reach the generator, so a stage in front that changes the frame count (BOB deinterlacing) does not go with them.  Without
+    ``frame_numbers`` nothing is filled.  The streaming forms take the numbers as a parallel iterable, hold back one frame
+    (`DeviceMissingFrameGenerator.stream`) and equal `run_device`.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
                  deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True,
                  quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0, hdr_converter=None, artifact_remover=None,
-                 artifact_qp=None):
+                 artifact_qp=None, frame_generator=None, expected_frames=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -78,11 +85,12 @@ class DeviceRestorationPipeline:
         self.last_quality_report = self.last_input_quality_report = None
         self.hdr_converter = hdr_converter
         self.artifact_remover, self.artifact_qp = artifact_remover, artifact_qp
+        self.frame_generator, self.expected_frames = frame_generator, expected_frames
 
     def _stages(self) -> tuple:
         """Every configured stage slot, in the order `_device` asks them: a new stage adds its name here."""
         return (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
-                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter, self.artifact_remover)
+                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter, self.artifact_remover, self.frame_generator)
 
     def close(self) -> None:
         """Closes every stage that can be closed (the engines free their native handles, the HDR converter its tables)."""
@@ -97,9 +105,9 @@ class DeviceRestorationPipeline:
     def for_fps(cls, denoiser, upscaler, interpolator, source_fps: float, target_fps: float) -> "DeviceRestorationPipeline":
         return cls(denoiser, upscaler, interpolator, policy.interpolation_exponent(target_fps / source_fps))
 
-    def run_device(self, frames: Sequence) -> List:
+    def run_device(self, frames: Sequence, frame_numbers: Optional[Sequence[int]] = None) -> List:
         """frames: uint8 BGR H x W x 3, numpy arrays or CUDA tensors.  Returns uint8 CUDA tensors (still on the device; the
-        work is queued on torch's current stream)."""
+        work is queued on torch's current stream).  ``frame_numbers``: the frames' numbers, for the ``frame_generator``."""
         import torch
         dev = self._device()
 
@@ -121,6 +129,8 @@ class DeviceRestorationPipeline:
                 cur = self.artifact_remover.process_device(cur, self.artifact_qp)
             if self.denoiser is not None:
                 cur = self.denoiser.denoise_clip_device(cur)
+            if self.frame_generator is not None and frame_numbers is not None:
+                cur = self.frame_generator.fill_device(cur, frame_numbers, self.expected_frames)[0]
             if self.upscaler is not None and self.deduplicator is not None and cur:
                 self.last_dedup_result = res = self.deduplicator.analyze_clip_device(cur)
                 cur = self.deduplicator.reconstruct_device([self.upscaler.upscale_device(cur[i]) for i in res.unique_indices], res)
@@ -144,9 +154,9 @@ class DeviceRestorationPipeline:
                 cur = self.hdr_converter.convert_device(cur)   # new uint16 tensors: a repeated frame may be one tensor several times
         return cur
 
-    def run(self, frames: Sequence) -> List[np.ndarray]:
+    def run(self, frames: Sequence, frame_numbers: Optional[Sequence[int]] = None) -> List[np.ndarray]:
         import torch
-        out = self.run_device(frames)
+        out = self.run_device(frames, frame_numbers)
         torch.cuda.synchronize()
         return [t.cpu().numpy() for t in out]
 
@@ -155,7 +165,7 @@ class DeviceRestorationPipeline:
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
         the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers, the HDR converter, the
-        artifact remover.
+        artifact remover, the frame generator.
         Every stage answers through `_lib.owner_device`: a new stage adds its name to `_stages`."""
         for stage in self._stages():
             dev = _lib.owner_device(stage)
@@ -203,12 +213,12 @@ class DeviceRestorationPipeline:
         if prev is not None:
             yield prev
 
-    def stream_device(self, frames: Iterable, block: int = 8):
+    def stream_device(self, frames: Iterable, block: int = 8, frame_numbers: Optional[Iterable[int]] = None):
         """Generator form of `run_device` for clips that do not fit (or have not arrived) in memory: ``frames`` is any iterator of
         uint8 BGR frames (numpy - e.g. `codec.RawVideoReader` - or CUDA tensors); yields the output frames, uint8 CUDA tensors, in
         order, as soon as their inputs allow.  Identical frames to `run_device` on the whole clip - without a ``deduplicator``:
         deduplication needs the clip's hashes in front of the upscale stage and is not part of the streaming form, which upscales
-        every frame."""
+        every frame.  ``frame_numbers``: the frames' numbers, in step with ``frames``, for the ``frame_generator``."""
         import torch
         dev = self._device()
         if block < 1:
@@ -247,6 +257,8 @@ class DeviceRestorationPipeline:
                 g = self.artifact_remover.stream(g, self.artifact_qp)
             if self.denoiser is not None:
                 g = self._gen_denoise(g, block)
+            if self.frame_generator is not None and frame_numbers is not None:
+                g = (f for _, f in self.frame_generator.stream(zip(frame_numbers, g), self.expected_frames))
             if self.upscaler is not None:
                 g = (self.upscaler.upscale_device(f) for f in g)
             if self.interpolator is not None:
@@ -262,7 +274,7 @@ class DeviceRestorationPipeline:
                 g = self.hdr_converter.stream(g)
             yield from g
 
-    def run_stream(self, frames: Iterable, writer, block: int = 8, slots: int = 3) -> int:
+    def run_stream(self, frames: Iterable, writer, block: int = 8, slots: int = 3, frame_numbers: Optional[Iterable[int]] = None) -> int:
         """``frames`` (e.g. a `codec.RawVideoReader` on the decoder's pipe) through the stages into ``writer`` (a
         `codec.RawVideoWriter` on the encoder's pipe): decode, GPU stages, download and encode overlap - the reader thread runs
         ahead of this thread, finished frames leave through a ring of ``slots`` pinned buffers on a download stream, and the writer
@@ -277,7 +289,7 @@ class DeviceRestorationPipeline:
         free: "_queue.Queue[int]" = _queue.Queue()
         n = 0
         with torch.cuda.device(dev):
-            for t in self.stream_device(frames, block):
+            for t in self.stream_device(frames, block, frame_numbers):
                 if pins is None:
                     pins = [torch.empty(tuple(t.shape), dtype=t.dtype).pin_memory() for _ in range(max(2, int(slots)))]
                     for k in range(len(pins)):
