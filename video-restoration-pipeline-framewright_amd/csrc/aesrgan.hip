@@ -36,19 +36,15 @@ struct Attn {
 
 }  // namespace
 
-struct fw_aesrgan {
-    int device = 0;
-    fw::StreamOrder order;   // device-side ordering of forwards enqueued on different streams (fw_internal.h)
+struct fw_aesrgan : fw::EngineBase {
     DType dt = DT_F16;
     int num_block = 23, scale = 2, num_attention = 4;
-    std::mutex mu;
     std::set<int> attn_after;
     std::map<std::string, size_t> want;
     std::map<std::string, std::vector<float>> host;
     std::map<std::string, Conv> convs;
     std::map<int, Attn> attn;
     bool built = false;
-    DevBuf ws;
 };
 
 namespace {
@@ -300,42 +296,17 @@ int fw_aesrgan_forward_rgb(fw_aesrgan* n, const float* x_rgb, int H, int W, floa
     int rc = fw_aesrgan_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
+        EngineCall call(n, stream);
         Arena P;
         P.plan = true;
         forward(n, P, nullptr, H, W, nullptr, nullptr);
-        ensure_workspace(n->ws, P.peak);
+        reserve_workspace(n, P.peak);
         Arena A;
         A.base = (char*)n->ws.p;
-        StreamOrder::Scope in_order(n->order, (hipStream_t)stream);
-        forward(n, A, x_rgb, H, W, out_rgb, (hipStream_t)stream);
+        forward(n, A, x_rgb, H, W, out_rgb, call.st);
     });
 }
 
-int fw_aesrgan_destroy(fw_aesrgan* n) {
-    if (!n) return FW_OK;
-    { std::lock_guard<std::mutex> lk(n->mu); }   // a call in flight on another thread finishes first
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(n->device);
-    (void)hipDeviceSynchronize();
-    for (auto& kv : n->convs) {
-        kv.second.w.release();
-        kv.second.b.release();
-    }
-    for (auto& kv : n->attn) {
-        for (int k = 0; k < 3; ++k) {
-            kv.second.w[k].release();
-            kv.second.b[k].release();
-        }
-        kv.second.gamma.release();
-    }
-    n->ws.release();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    n->order.destroy();
-    delete n;
-    return FW_OK;
-}
+int fw_aesrgan_destroy(fw_aesrgan* n) { return destroy_engine(n); }
 
 }  // extern "C"

@@ -46,20 +46,9 @@ struct Conv {
     size_t gstride = 0;      // the groups then run side by side in one launch (ConvParams::n_groups)
     DevBuf nwall;            // the same conv as 32-channel groups (one launch, ball serves both): twice the workgroups with half the
     size_t ngstride = 0;     // MFMAs each, for maps of a few tiles (build(..., narrow = true))
-    void release() {
-        for (auto& g : groups) {
-            g.w.release();
-            g.b.release();
-        }
-        groups.clear();
-        wall.release();
-        ball.release();
-        nwall.release();
-        gstride = ngstride = 0;
-    }
     // w: [cout][cin][3][3] fp32 (already transformed), zero-padded to [cout_pad][cin_pad]
     void build(DType dt, const std::vector<float>& w, const std::vector<float>& b, int cout, int cin, int cin_p, int cout_p, bool narrow = false) {
-        release();
+        *this = Conv();   // a rebuild frees what the last one uploaded
         cin_pad = cin_p;
         cout_pad = cout_p;
         cin_chunks = (cin + 31) / 32;
@@ -155,14 +144,10 @@ struct Plan {
 
 }  // namespace
 
-struct fw_ifnet {
-    int device = 0;
-    fw::StreamOrder order;   // device-side ordering of forwards enqueued on different streams (fw_internal.h)
+struct fw_ifnet : fw::EngineBase {
     DType dt = DT_F16;
-    std::mutex mu;
     Block blk[NBLK];
     bool built = false;
-    DevBuf ws;
     // hipGraph replay of a forward, keyed by everything a captured launch sequence bakes in (FW_IFNET_GRAPH=1; off by default:
     // a caller that hands over fresh buffers every frame would re-capture every frame)
     int graph_mode = 0;
@@ -180,7 +165,6 @@ struct fw_ifnet {
     long narrow_below = 128;    //   FW_IFNET_NARROW_BELOW: below that many 64-channel workgroups per launch)
     bool warmed = false;
     int last_h = 0, last_w = 0;   // frame size of the forward whose flow and mask the workspace holds (fw_ifnet_last_flow)
-    GraphCache graphs;
 };
 
 namespace {
@@ -531,12 +515,10 @@ int fw_ifnet_interp_u8(fw_ifnet* n, const uint8_t* frame0, const uint8_t* frame1
     int rc = fw_ifnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         const Plan pl = make_plan(H, W);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         char* ws = (char*)n->ws.p;
         const size_t bytes = (size_t)H * W * 3;
         const uint8_t *d0 = frame0, *d1 = frame1;
@@ -584,29 +566,6 @@ int fw_ifnet_last_flow(fw_ifnet* n, int H, int W, float* flow_out, float* mask_o
     });
 }
 
-int fw_ifnet_destroy(fw_ifnet* n) {
-    if (!n) return FW_OK;
-    { std::lock_guard<std::mutex> lk(n->mu); }   // a call in flight on another thread finishes first
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(n->device);
-    (void)hipDeviceSynchronize();
-    n->graphs.clear();
-    for (auto& b : n->blk) {
-        b.conv00.release();
-        b.conv01.release();
-        b.last.release();
-        for (int j = 0; j < NRES; ++j) {
-            b.res[j].release();
-            b.res_split[j].release();
-            b.beta[j].release();
-        }
-    }
-    n->ws.release();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    n->order.destroy();
-    delete n;
-    return FW_OK;
-}
+int fw_ifnet_destroy(fw_ifnet* n) { return destroy_engine(n); }
 
 }  // extern "C"

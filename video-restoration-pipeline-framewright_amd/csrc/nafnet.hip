@@ -43,20 +43,16 @@ struct Level {
 
 }  // namespace
 
-struct fw_nafnet {
-    int device = 0;
-    fw::StreamOrder order;   // device-side ordering of forwards enqueued on different streams (fw_internal.h)
+struct fw_nafnet : fw::EngineBase {
     DType dt = DT_BF16;
     int width = 64, middle = 12;
     int nlev = 4;
     int enc[8] = {0}, dec[8] = {0};
-    std::mutex mu;
     std::vector<std::vector<Block>> encoders, decoders;
     std::vector<Block> middle_blks;
     std::vector<Level> downs, ups;
     DevBuf intro_w, intro_b, ending_w, ending_b;
     bool have_intro_w = false, have_intro_b = false, have_end_w = false, have_end_b = false;
-    DevBuf ws;
     bool fuse_ln = true;   // LayerNorm2d inside the staging pass of the GEMM that follows it at width 64 (FW_NAF_FUSE_LN=0: A/B)
     bool gemm = true;      // 1x1 convs of the levels with >= 256 channels on pointwise_gemm.hip (FW_NAF_GEMM=0: A/B)
     bool fuse_tail = true; // conv3 .. conv5 of a width-64 block as one kernel (FW_NAF_FUSE_TAIL=0: A/B)
@@ -65,7 +61,6 @@ struct fw_nafnet {
     // sequence bakes in (FW_NAF_GRAPH=1; off by default: a caller that hands over fresh buffers every frame would re-capture every frame)
     int graph_mode = 0;
     bool warmed = false;
-    GraphCache graphs;
 };
 
 namespace {
@@ -504,12 +499,10 @@ int fw_nafnet_denoise_u8(fw_nafnet* n, const uint8_t* in_bgr, int in_loc, int H,
     int rc = fw_nafnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         const Plan pl = make_plan(n, H, W);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         const size_t bytes = (size_t)H * W * 3;
         const uint8_t* d_in = in_bgr;
         if (in_loc == FW_HOST) {
@@ -544,16 +537,14 @@ int fw_nafnet_run_block(fw_nafnet* n, const char* key_c, float* stream_f32, int 
     int rc = fw_nafnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         // the workspace of the forward in which this block sees H x W pixels: level l = log2(c / width), frame (H << l) x (W << l)
         int l = 0;
         while ((n->width << l) < bl->c) ++l;
         if (((long)H << l) > 16384 || ((long)W << l) > 16384) throw Error(FW_ERR_INVALID, "fw_nafnet_run_block: size beyond the largest frame");
         const Plan pl = make_plan(n, H << l, W << l);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         run_block(n, *bl, stream_f32, H, W, (char*)n->ws.p, pl, st);
         if (sca_out)
             FW_HIP_CHECK(hipMemcpyAsync(sca_out, (char*)n->ws.p + pl.sca, (size_t)bl->c * 4, hipMemcpyDeviceToDevice, st));
@@ -581,10 +572,8 @@ int fw_nafnet_run_resample(fw_nafnet* n, int level, int up, const float* src_f32
     int rc = fw_nafnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         launch_pointwise(n->dt, up ? up_params(n, level, src_f32, H, W, dst_f32) : down_params(n, level, src_f32, H, W, dst_f32), st);
     });
 }
@@ -614,30 +603,6 @@ double fw_nafnet_flops(const fw_nafnet* n, int H, int W) {
     return 2.0 * mac;
 }
 
-int fw_nafnet_destroy(fw_nafnet* n) {
-    if (!n) return FW_OK;
-    { std::lock_guard<std::mutex> lk(n->mu); }   // a call in flight on another thread finishes first
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(n->device);
-    (void)hipDeviceSynchronize();
-    n->graphs.clear();
-    auto free_block = [](Block& b) {
-        for (DevBuf* d : {&b.n1w, &b.n1b, &b.n2w, &b.n2b, &b.beta, &b.gamma, &b.w1, &b.b1, &b.w3, &b.b3, &b.w4, &b.b4, &b.w5, &b.w1g, &b.w3g, &b.w4g, &b.w5g,
-                          &b.b5, &b.wdw, &b.bdw, &b.wsca, &b.bsca, &b.front, &b.tail128})
-            d->release();
-    };
-    for (auto& v : n->encoders) for (auto& b : v) free_block(b);
-    for (auto& v : n->decoders) for (auto& b : v) free_block(b);
-    for (auto& b : n->middle_blks) free_block(b);
-    for (auto& l : n->downs) { l.w.release(); l.b.release(); }
-    for (auto& l : n->ups) { l.w.release(); l.b.release(); }
-    n->intro_w.release(); n->intro_b.release(); n->ending_w.release(); n->ending_b.release();
-    n->ws.release();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    n->order.destroy();
-    delete n;
-    return FW_OK;
-}
+int fw_nafnet_destroy(fw_nafnet* n) { return destroy_engine(n); }
 
 }  // extern "C"

@@ -51,14 +51,8 @@ struct Conv3 {
     std::vector<DevBuf> groups;
     DevBuf wall;            // all groups in one buffer, gstride bytes apart: they run side by side in one launch (ConvParams::n_groups)
     size_t gstride = 0;
-    void release() {
-        for (auto& g : groups) g.release();
-        groups.clear();
-        wall.release();
-        gstride = 0;
-    }
     void build(DType dt, const float* w, int cout, int cin, int cin_pad_or_0) {
-        release();
+        *this = Conv3();   // a rebuild frees what the last one uploaded
         cin_pad = cin_pad_or_0 ? cin_pad_or_0 : stream_pad(cin);
         cout_pad = pad_to(cout, 64);
         std::vector<float> wp((size_t)cout_pad * cin_pad * 9, 0.f);
@@ -87,9 +81,6 @@ struct RBlock {
     DevBuf qkv16, pin16;           // qkv / project_in in pack_pointwise_weights16's layout, rows padded to 256 (the staged levels: pointwise_gemm.hip)
     int qkv16_n = 0, pin16_n = 0;  // padded output channels
     int qkv_t = 0, proj_t = 0, pin_t = 0, pout_t = 0;
-    void release() {
-        for (DevBuf* b : {&n1w, &n1b, &n2w, &n2b, &temp, &qkv, &qkv_dw, &proj, &pin, &ffn_dw, &pout, &front_qkv, &front_ffn, &proj_f32, &qkv16, &pin16}) b->release();
-    }
 };
 
 struct Stage {
@@ -99,13 +90,10 @@ struct Stage {
 
 }  // namespace
 
-struct fw_restormer {
-    int device = 0;
-    fw::StreamOrder order;   // device-side ordering of forwards enqueued on different streams (fw_internal.h)
+struct fw_restormer : fw::EngineBase {
     DType dt = DT_F16;
     int dim = 48, nblk[4] = {4, 6, 6, 8}, nref = 4, heads[4] = {1, 2, 4, 8};
     double ffn = 2.66;
-    std::mutex mu;
     std::vector<Stage> stages;
     std::map<std::string, size_t> want;             // tensor key -> element count
     std::map<std::string, std::vector<float>> host; // as set, until finalize()
@@ -119,7 +107,6 @@ struct fw_restormer {
     bool qk_direct = true;    // the fused qkv front writes q / k in the Gram kernel's operand layout (FW_REST_QK_DIRECT=0: pixel-major + transpose pass)
     bool merge_proj = true;   // project_out folded into the attention matrix: one GEMM pass instead of two (FW_REST_MERGE_PROJ=0: A/B)
     bool fuse_front = true;   // LayerNorm + 1x1 + depthwise 3x3 (+ GDFN gate) of the 48- / 96-channel blocks as one kernel (FW_REST_FUSE_FRONT=0: A/B)
-    DevBuf ws;
 };
 
 namespace {
@@ -593,16 +580,14 @@ int fw_restormer_denoise_u8(fw_restormer* n, const uint8_t* in_bgr, int in_loc, 
     int rc = fw_restormer_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         const size_t frame = ((size_t)H * W * 3 + 255) / 256 * 256;
         Arena P;
         P.plan = true;
         forward(n, P, nullptr, H, W, nullptr, nullptr, nullptr);
         const size_t total = 2 * frame + P.peak;
-        ensure_workspace(n->ws, total);
+        reserve_workspace(n, total);
         char* base = (char*)n->ws.p;
         const uint8_t* d_in = in_bgr;
         if (in_loc == FW_HOST) {
@@ -633,10 +618,8 @@ int fw_restormer_run_block(fw_restormer* n, const char* key_c, float* stream_f32
     int rc = fw_restormer_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         int si = 0;
         const RBlock* b = find_block(n, key, &si);
         if (!b) throw Error(FW_ERR_INVALID, "fw_restormer_run_block: unknown block '" + key + "'");
@@ -645,7 +628,7 @@ int fw_restormer_run_block(fw_restormer* n, const char* key_c, float* stream_f32
         Arena P;
         P.plan = true;
         Sequencer(n, P, nullptr).block(*b, nullptr, H, W);
-        ensure_workspace(n->ws, P.peak);
+        reserve_workspace(n, P.peak);
         Arena A;
         A.base = (char*)n->ws.p;
         Sequencer(n, A, st).block(*b, stream_f32, H, W, attn_out);
@@ -679,34 +662,18 @@ int fw_restormer_run_step(fw_restormer* n, const char* step_c, const float* src_
     int rc = fw_restormer_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         Arena P;
         P.plan = true;
         Sequencer(n, P, nullptr).step(s, nullptr, nullptr, H, W, nullptr);
-        ensure_workspace(n->ws, P.peak);
+        reserve_workspace(n, P.peak);
         Arena A;
         A.base = (char*)n->ws.p;
         Sequencer(n, A, st).step(s, src_f32, skip_f32, H, W, dst_f32);
     });
 }
 
-int fw_restormer_destroy(fw_restormer* n) {
-    if (!n) return FW_OK;
-    { std::lock_guard<std::mutex> lk(n->mu); }   // a call in flight on another thread finishes first
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(n->device);
-    (void)hipDeviceSynchronize();
-    for (auto& kv : n->blocks) kv.second.release();
-    for (auto& kv : n->convs) kv.second.release();
-    for (DevBuf* b : {&n->red3, &n->red2, &n->conv_bias, &n->ones, &n->ws}) b->release();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    n->order.destroy();
-    delete n;
-    return FW_OK;
-}
+int fw_restormer_destroy(fw_restormer* n) { return destroy_engine(n); }
 
 }  // extern "C"

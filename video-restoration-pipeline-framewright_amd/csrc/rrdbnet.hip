@@ -19,11 +19,10 @@ namespace fw {
 
 struct ConvLayer {
     int cout = 0, cin = 0, ct = 0, chunks = 0;
-    void* d_w = nullptr;
-    float* d_b = nullptr;
-    void* d_wphase = nullptr;   // conv_up1 / conv_up2: the same weights as four 2x2 phase convolutions (conv_up2x_phase.hip)
-    void* d_wwino = nullptr;    // conv5 of a dense block, f16: the same weights as row-wise Winograd fragments (conv3x3_wino.hip)
-    void* d_wlast = nullptr;    // conv_last: the same weights as the pointwise fragments of the fused tail (conv3x3_hr_last.hip)
+    DevBuf d_w, d_b;            // packed weight fragments (pack_conv3x3_weights); fp32 bias, zero padded to 32 * ct
+    DevBuf d_wphase;            // conv_up1 / conv_up2: the same weights as four 2x2 phase convolutions (conv_up2x_phase.hip)
+    DevBuf d_wwino;             // conv5 of a dense block, f16: the same weights as row-wise Winograd fragments (conv3x3_wino.hip)
+    DevBuf d_wlast;             // conv_last: the same weights as the pointwise fragments of the fused tail (conv3x3_hr_last.hip)
     bool set = false;
 };
 
@@ -31,23 +30,12 @@ struct ConvLayer {
 
 using namespace fw;
 
-namespace fw {
-std::string& last_error_ref() {
-    thread_local std::string msg;
-    return msg;
-}
-}  // namespace fw
-
-struct fw_rrdbnet {
-    int device = 0;
-    fw::StreamOrder order;   // device-side ordering of forwards enqueued on different streams (fw_internal.h)
+struct fw_rrdbnet : fw::EngineBase {
     int num_block = 0;
     int scale = 4;
     DType dt = DT_BF16;
-    std::mutex mu;
     ConvLayer conv_first, conv_body, conv_up1, conv_up2, conv_hr, conv_last;
     std::vector<ConvLayer> body;  // [num_block][3][5]
-    DevBuf ws;
     int fuse_mask = 3;       // bit 0: conv1+conv2, bit 1: conv3+conv4 (FW_RRDB_FUSE_MASK, for A/B runs)
     bool fuse_pairs = true;  // conv1+conv2 / conv3+conv4 in one kernel (FW_RRDB_FUSE_PAIRS=0 disables, for A/B runs)
     // residual trunk as typed hi + typed lo planes (EPI_RESIDUAL_SPLIT): the residual adds run on the matrix cores as
@@ -79,7 +67,6 @@ struct fw_rrdbnet {
     // FW_RRDB_GRAPH_MAX_PX.
     int graph_mode = 0;
     long graph_max_px = 512L * 512L;
-    GraphCache graphs;
     bool warmed = false;
     // profiling
     bool profile = false;
@@ -87,6 +74,9 @@ struct fw_rrdbnet {
     size_t ev_used = 0;
     double prof_flops = 0;
     hipStream_t prof_stream = nullptr;
+    ~fw_rrdbnet() {   // (destroy_engine: on the handle's device)
+        for (auto e : ev_pool) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -167,18 +157,12 @@ ConvLayer* find_layer(fw_rrdbnet* n, const std::string& key, int* want_cout, int
     return nullptr;
 }
 
-void free_layer(ConvLayer& l) {
-    if (l.d_w) (void)hipFree(l.d_w);
-    if (l.d_b) (void)hipFree(l.d_b);
-    if (l.d_wphase) (void)hipFree(l.d_wphase);
-    if (l.d_wwino) (void)hipFree(l.d_wwino);
-    if (l.d_wlast) (void)hipFree(l.d_wlast);
-    l.d_wlast = nullptr;
-    l.d_wphase = nullptr;
-    l.d_wwino = nullptr;
-    l.d_w = nullptr;
-    l.d_b = nullptr;
-    l.set = false;
+// one packed form of a layer's weights on the device: sized by the packer's nullptr call, packed on the host, uploaded
+template <typename Pack>
+void upload_packed(DevBuf& b, const float* weight, Pack&& pack) {
+    std::vector<uint16_t> pk(pack(nullptr, nullptr));
+    pack(weight, pk.data());
+    upload(b, pk.data(), pk.size() * 2);
 }
 
 double conv_flops(const ConvLayer& l, size_t pixels) { return 2.0 * 9.0 * l.cin * l.cout * (double)pixels; }
@@ -204,8 +188,8 @@ void timed(fw_rrdbnet* n, hipStream_t st, double flops, F&& launch) {
 
 void run_conv(fw_rrdbnet* n, const ConvLayer& l, ConvEpilogue epi, ConvParams p, hipStream_t st) {
     p.cin_chunks = l.chunks;
-    p.wpk = l.d_w;
-    p.bias = l.d_b;
+    p.wpk = l.d_w.p;
+    p.bias = (const float*)l.d_b.p;
     timed(n, st, conv_flops(l, (size_t)p.H * p.W), [&] { launch_conv3x3(n->dt, l.ct, epi, p, st); });
 }
 
@@ -261,7 +245,7 @@ int c5_planes(const fw_rrdbnet* n, int k) { return n->rrdb_lo ? (k == 2 ? 4 : 0)
 // whether a conv5 with n_id residual planes takes the Winograd kernel: the one place that decides it, for run_rrdb and for
 // fw_rrdbnet_block_paths
 bool c5_on_wino(const fw_rrdbnet* n, int n_id, const ConvLayer& c5) {
-    return n->c5_wino && n->dt == DT_F16 && (n_id == 0 || n->c5_wino >= 2) && c5.d_wwino && !(n->abl_alias & 2) && !n->abl_rdb3;
+    return n->c5_wino && n->dt == DT_F16 && (n_id == 0 || n->c5_wino >= 2) && c5.d_wwino.p && !(n->abl_alias & 2) && !n->abl_rdb3;
 }
 
 // RRDB b of the trunk.  cur: the concat buffer whose planes 0-1 (split trunk: + 6-7) hold its input, on return the one that holds its
@@ -286,10 +270,10 @@ void run_rrdb(fw_rrdbnet* n, const Trunk& T, int b, const float* Rin, int& cur, 
                 q.na = 2 + c;
                 q.H = Ht;
                 q.W = Wt;
-                q.wpk_a = L[c].d_w;
-                q.bias_a = L[c].d_b;
-                q.wpk_b = L[c + 1].d_w;
-                q.bias_b = L[c + 1].d_b;
+                q.wpk_a = L[c].d_w.p;
+                q.bias_a = (const float*)L[c].d_b.p;
+                q.wpk_b = L[c + 1].d_w.p;
+                q.bias_b = (const float*)L[c + 1].d_b.p;
                 q.out_a = plane(cat[cur], 2 + c, PL);
                 q.out_b = plane(cat[cur], 3 + c, PL);
                 q.out_cstride = 32;
@@ -362,8 +346,8 @@ void run_rrdb(fw_rrdbnet* n, const Trunk& T, int b, const float* Rin, int& cur, 
             p.s1 = (k == 2) ? 0.2f * 0.2f : 0.2f;
             if (c5_on_wino(n, p.n_id, L[4])) {
                 p.cin_chunks = L[4].chunks;
-                p.wpk = L[4].d_wwino;
-                p.bias = L[4].d_b;
+                p.wpk = L[4].d_wwino.p;
+                p.bias = (const float*)L[4].d_b.p;
                 // algorithmic FLOPs: the nine-tap count
                 timed(n, st, conv_flops(L[4], (size_t)p.H * p.W), [&] { launch_conv3x3_wino_split(p, st); });
             } else {
@@ -401,8 +385,8 @@ Ends make_ends(const fw_rrdbnet* n, const Plan& pl) {
 
 // whether an up-conv runs as four 2x2 phase convolutions, conv_hr in the Winograd form, and conv_hr + conv_last as one launch on a
 // trunk of Ht x Wt pixels: the one place that decides each, for run_tail and for fw_rrdbnet_tail_paths
-bool up_on_phase(const fw_rrdbnet* n, const ConvLayer& l) { return n->up_phase && l.d_wphase; }
-bool hr_on_wino(const fw_rrdbnet* n) { return n->c5_wino && n->dt == DT_F16 && n->conv_hr.d_wwino && n->hr_wino; }
+bool up_on_phase(const fw_rrdbnet* n, const ConvLayer& l) { return n->up_phase && l.d_wphase.p; }
+bool hr_on_wino(const fw_rrdbnet* n) { return n->c5_wino && n->dt == DT_F16 && n->conv_hr.d_wwino.p && n->hr_wino; }
 bool tail_fused(const fw_rrdbnet* n, int Ht, int Wt) {
     return !hr_on_wino(n) && (n->hr_last < 0 ? hr_last_default(4 * Ht, 4 * Wt) : n->hr_last != 0);
 }
@@ -448,8 +432,8 @@ void run_tail(fw_rrdbnet* n, const Trunk& T, const Ends& E, int cur, int bits, i
             u.in_pstride = src_pstride;
             u.H = Hs;
             u.W = Ws;
-            u.wpk = l.d_wphase;
-            u.bias = l.d_b;
+            u.wpk = l.d_wphase.p;
+            u.bias = (const float*)l.d_b.p;
             u.act = 1;
             u.out = dst;
             u.out_cstride = 32;
@@ -497,11 +481,11 @@ void run_tail(fw_rrdbnet* n, const Trunk& T, const Ends& E, int cur, int bits, i
         p.img_H = img.img_H;
         p.img_W = img.img_W;
         p.cin_chunks = n->conv_hr.chunks;
-        p.wpk = n->conv_hr.d_w;
-        p.bias = n->conv_hr.d_b;
+        p.wpk = n->conv_hr.d_w.p;
+        p.bias = (const float*)n->conv_hr.d_b.p;
         const size_t px = (size_t)p.H * p.W;
         timed(n, st, conv_flops(n->conv_hr, px) + conv_flops(n->conv_last, px),
-              [&] { launch_conv3x3_hr_last(n->dt, p, n->conv_last.d_wlast, n->conv_last.d_b, st); });
+              [&] { launch_conv3x3_hr_last(n->dt, p, n->conv_last.d_wlast.p, (const float*)n->conv_last.d_b.p, st); });
         return;
     }
     {
@@ -511,8 +495,8 @@ void run_tail(fw_rrdbnet* n, const Trunk& T, const Ends& E, int cur, int bits, i
         p.act = 1;
         if (hr_wino) {
             p.cin_chunks = n->conv_hr.chunks;
-            p.wpk = n->conv_hr.d_wwino;
-            p.bias = n->conv_hr.d_b;
+            p.wpk = n->conv_hr.d_wwino.p;
+            p.bias = (const float*)n->conv_hr.d_b.p;
             timed(n, st, conv_flops(n->conv_hr, (size_t)p.H * p.W), [&] { launch_conv3x3_wino_store(p, st); });
         } else {
             run_conv(n, n->conv_hr, EPI_STORE, p, st);
@@ -542,20 +526,6 @@ void forward(fw_rrdbnet* n, const void* d_in, int bits, int H, int W, void* d_ou
 }  // namespace
 
 extern "C" {
-
-const char* fw_last_error(void) { return fw::last_error_ref().c_str(); }
-
-int fw_abi_version(void) { return 4; }  // 2: + upscale_u16, resize_lanczos4, grain_addback, attention (softmax rows, transposed pack, MFMA Gram)
-                                         // 3 (round 2, additive): + fw_ifnet_*, fw_restormer_*, fw_srvgg_*, fw_unsharp_mask_u8, fw_preserve_edges_*, fw_attn_proj_pack
-                                         // 4 (additive): + fw_pack_conv3x3_wino, fw_conv3x3_split_nhwc, fw_conv3x3_wino_nhwc, fw_conv3x3_wino_check_fields
-                                         // still 4 (additive entries no longer bump it): + the single-step test hooks fw_nafnet_run_block, fw_restormer_run_block /
-                                         // run_step, fw_rrdbnet_run_rrdbs / run_head / run_tail and their *_paths
-
-int fw_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
 
 int fw_rrdbnet_create(int device_id, int num_block, int scale, int dtype, fw_rrdbnet** out) {
     if (!out) return fail(FW_ERR_INVALID, "fw_rrdbnet_create: out is NULL");
@@ -601,40 +571,22 @@ int fw_rrdbnet_set_conv(fw_rrdbnet* n, const char* key, const float* weight, con
                                             std::to_string(cout) + "," + std::to_string(cin) + ",3,3], expected [" +
                                             std::to_string(wco) + "," + std::to_string(wci) + ",3,3]");
         DevGuard dg(n->device);
-        free_layer(*l);
+        *l = ConvLayer();   // a layer set again: its previous buffers go first
         l->cout = cout;
         l->cin = cin;
         l->ct = (cout + 31) / 32;
         l->chunks = (cin + 31) / 32;
-        const size_t ne = pack_conv3x3_weights(n->dt, nullptr, cout, cin, l->ct, l->chunks, nullptr);
-        std::vector<uint16_t> packed(ne);
-        pack_conv3x3_weights(n->dt, weight, cout, cin, l->ct, l->chunks, packed.data());
+        const DType dt = n->dt;
+        upload_packed(l->d_w, weight, [&](const float* w, uint16_t* dst) { return pack_conv3x3_weights(dt, w, cout, cin, l->ct, l->chunks, dst); });
         std::vector<float> b(32 * l->ct, 0.f);
         for (int i = 0; i < cout; ++i) b[i] = bias[i];
-        FW_HIP_CHECK(hipMalloc(&l->d_w, ne * 2));
-        FW_HIP_CHECK(hipMalloc((void**)&l->d_b, b.size() * 4));
-        FW_HIP_CHECK(hipMemcpy(l->d_w, packed.data(), ne * 2, hipMemcpyHostToDevice));
-        FW_HIP_CHECK(hipMemcpy(l->d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-        if (n->dt == DT_F16 && cout == 64 && (cin == 192 || l == &n->conv_hr)) {   // a dense block's conv5; conv_hr of the tail
-            const size_t nw = pack_conv3x3_wino_weights(n->dt, nullptr, cout, cin, l->chunks, nullptr);
-            std::vector<uint16_t> wn(nw);
-            pack_conv3x3_wino_weights(n->dt, weight, cout, cin, l->chunks, wn.data());
-            FW_HIP_CHECK(hipMalloc(&l->d_wwino, nw * 2));
-            FW_HIP_CHECK(hipMemcpy(l->d_wwino, wn.data(), nw * 2, hipMemcpyHostToDevice));
-        }
-        if (l == &n->conv_last) {
-            std::vector<uint16_t> pw(pack_conv_last_pointwise(n->dt, nullptr, nullptr));
-            pack_conv_last_pointwise(n->dt, weight, pw.data());
-            FW_HIP_CHECK(hipMalloc(&l->d_wlast, pw.size() * 2));
-            FW_HIP_CHECK(hipMemcpy(l->d_wlast, pw.data(), pw.size() * 2, hipMemcpyHostToDevice));
-        }
-        if (l == &n->conv_up1 || l == &n->conv_up2) {
-            const size_t np = pack_conv_up2x_phase_weights(n->dt, nullptr, nullptr);
-            std::vector<uint16_t> ph(np);
-            pack_conv_up2x_phase_weights(n->dt, weight, ph.data());
-            FW_HIP_CHECK(hipMalloc(&l->d_wphase, np * 2));
-            FW_HIP_CHECK(hipMemcpy(l->d_wphase, ph.data(), np * 2, hipMemcpyHostToDevice));
-        }
+        upload(l->d_b, b.data(), b.size() * 4);
+        if (n->dt == DT_F16 && cout == 64 && (cin == 192 || l == &n->conv_hr))   // a dense block's conv5; conv_hr of the tail
+            upload_packed(l->d_wwino, weight, [&](const float* w, uint16_t* dst) { return pack_conv3x3_wino_weights(dt, w, cout, cin, l->chunks, dst); });
+        if (l == &n->conv_last)
+            upload_packed(l->d_wlast, weight, [&](const float* w, uint16_t* dst) { return pack_conv_last_pointwise(dt, w, dst); });
+        if (l == &n->conv_up1 || l == &n->conv_up2)
+            upload_packed(l->d_wphase, weight, [&](const float* w, uint16_t* dst) { return pack_conv_up2x_phase_weights(dt, w, dst); });
         l->set = true;
     });
 }
@@ -685,12 +637,10 @@ static int upscale_any(fw_rrdbnet* n, const void* in_bgr, int in_loc, int bits, 
     int rc = fw_rrdbnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         const Plan pl = make_plan(n, H, W);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         char* ws = (char*)n->ws.p;
         const size_t in_bytes = (size_t)H * W * 3 * (bits / 8);
         const size_t out_bytes = in_bytes * n->scale * n->scale;
@@ -742,13 +692,11 @@ int fw_rrdbnet_run_rrdbs(fw_rrdbnet* n, int first_block, int count, const float*
     int rc = fw_rrdbnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         // the workspace of the forward whose trunk has Ht x Wt pixels
         const Plan pl = make_plan(n, fs * Ht, fs * Wt);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         const Trunk T = make_trunk(n, pl, Ht, Wt);
         // what a forward holds on entering first_block: three RDBs per RRDB, each moving on by one buffer
         int cur = 3 * first_block % T.ncat;
@@ -790,14 +738,12 @@ int fw_rrdbnet_run_head(fw_rrdbnet* n, const void* in_bgr, int bits, int H, int 
     int rc = fw_rrdbnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         int Ht, Wt;
         trunk_size(n, H, W, &Ht, &Wt);
         const Plan pl = make_plan(n, H, W);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         const Trunk T = make_trunk(n, pl, Ht, Wt);
         run_head(n, T, make_ends(n, pl), in_bgr, bits, H, W, st);
         // what RRDB 0 reads: the planes of concat buffer 0, or the fp32 trunk F; and F itself, which conv_body adds later
@@ -827,12 +773,10 @@ int fw_rrdbnet_run_tail(fw_rrdbnet* n, const float* feat_f32, const float* trunk
     int rc = fw_rrdbnet_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         const Plan pl = make_plan(n, H, W);
-        ensure_workspace(n->ws, pl.total, &n->graphs);
+        reserve_workspace(n, pl.total);
         const Trunk T = make_trunk(n, pl, Ht, Wt);
         // the buffer a forward holds behind its last RRDB: three RDBs per RRDB, each moving on by one buffer
         const int cur = 3 * n->num_block % T.ncat;
@@ -888,347 +832,6 @@ int fw_rrdbnet_profile_read(fw_rrdbnet* n, int* launches, double* total_ms, doub
     });
 }
 
-int fw_rrdbnet_destroy(fw_rrdbnet* n) {
-    if (!n) return FW_OK;
-    // a call in flight on another thread finishes first; calling INTO a destroyed handle remains the caller's bug (the Python
-    // engine counts its calls in flight and destroys only when there are none)
-    { std::lock_guard<std::mutex> lk(n->mu); }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(n->device);
-    (void)hipDeviceSynchronize();
-    for (auto& l : n->body) free_layer(l);
-    free_layer(n->conv_first);
-    free_layer(n->conv_body);
-    free_layer(n->conv_up1);
-    free_layer(n->conv_up2);
-    free_layer(n->conv_hr);
-    free_layer(n->conv_last);
-    n->graphs.clear();
-    n->ws.release();
-    for (auto e : n->ev_pool) (void)hipEventDestroy(e);
-    if (prev >= 0) (void)hipSetDevice(prev);
-    n->order.destroy();
-    delete n;
-    return FW_OK;
-}
-
-size_t fw_pack_conv3x3(int dtype, const float* weight, int cout, int cin, int cout_tiles, int cin_chunks,
-                       uint16_t* dst) {
-    if (cout < 1 || cin < 1 || cout_tiles < 1 || cin_chunks < 1 || cout > 32 * cout_tiles || cin > 32 * cin_chunks)
-        return 0;
-    if (dst && !weight) return 0;
-    return pack_conv3x3_weights((DType)dtype, weight, cout, cin, cout_tiles, cin_chunks, dst);
-}
-
-int fw_conv3x3_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int H, int W,
-                    const void* packed_weight, const float* bias, int cout_tiles, int act_lrelu, int upsample2x,
-                    const float* res1, float s1, const float* res2, float s2, void* out, int out_cstride,
-                    long out_plane_stride, int out_coff, float* out_f32, void* stream) {
-    return fw_conv3x3_nhwc_ex(dtype, x, in_cstride, in_plane_stride, cin_chunks, H, W, packed_weight, bias, cout_tiles,
-                              act_lrelu, upsample2x, res1, s1, res2, s2, nullptr, 0, 0, 0, out, out_cstride,
-                              out_plane_stride, out_coff, out_f32, stream);
-}
-
-int fw_conv3x3_pair_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int in_chunks, int H, int W,
-                         const void* packed_weight_a, const float* bias_a, const void* packed_weight_b, const float* bias_b,
-                         void* out_a, void* out_b, int out_cstride, void* stream) {
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_pair_nhwc: bad dtype");
-    return guarded([&] {
-        ConvPairParams q{};
-        q.in = x;
-        q.in_cstride = in_cstride;
-        q.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
-        q.na = in_chunks;
-        q.H = H;
-        q.W = W;
-        q.wpk_a = packed_weight_a;
-        q.bias_a = bias_a;
-        q.wpk_b = packed_weight_b;
-        q.bias_b = bias_b;
-        q.out_a = out_a;
-        q.out_b = out_b;
-        q.out_cstride = out_cstride;
-        // (a single pixel: the chunk-planar layout's plane stride H * W * 32 IS 32 and in_cstride addresses nothing, as in
-        // launch_conv_up2x_phase)
-        if (q.in_pstride == 32 && in_cstride < 32 * in_chunks && (long)H * W > 1)
-            throw Error(FW_ERR_INVALID, "fw_conv3x3_pair_nhwc: input too narrow");
-        launch_conv3x3_pair((DType)dtype, q, (hipStream_t)stream);
-    });
-}
-
-int fw_conv3x3_nhwc_ex(int dtype, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int H, int W,
-                       const void* packed_weight, const float* bias, int cout_tiles, int act_lrelu, int upsample2x,
-                       const float* res1, float s1, const float* res2, float s2, const float* chan_scale, int post_act,
-                       int f32_cstride, int f32_coff, void* out, int out_cstride, long out_plane_stride, int out_coff,
-                       float* out_f32, void* stream) {
-    if (!x || !packed_weight || !bias) return fail(FW_ERR_INVALID, "fw_conv3x3_nhwc: NULL argument");
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_nhwc: bad dtype");
-    if (cout_tiles != 1 && cout_tiles != 2) return fail(FW_ERR_INVALID, "fw_conv3x3_nhwc: cout_tiles must be 1 or 2");
-    if (res1 && cout_tiles != 2) return fail(FW_ERR_INVALID, "fw_conv3x3_nhwc: residual epilogue needs 64 channels");
-    if (!res1 && res2) return fail(FW_ERR_INVALID, "fw_conv3x3_nhwc: res2 without res1");
-    if (act_lrelu == 2 && (res1 || !chan_scale)) return fail(FW_ERR_INVALID, "fw_conv3x3_nhwc: PReLU needs slopes and no residual");
-    return guarded([&] {
-        ConvParams p{};
-        p.in = x;
-        p.in_cstride = in_cstride;
-        p.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
-        p.out_pstride = out_plane_stride > 0 ? out_plane_stride : 32;
-        p.cin_chunks = cin_chunks;
-        p.H = H;
-        p.W = W;
-        p.wpk = packed_weight;
-        p.bias = bias;
-        p.out = out;
-        p.out_cstride = out_cstride;
-        p.out_coff = out_coff;
-        p.out_f32 = out_f32;
-        p.res1 = res1;
-        p.res2 = res2;
-        p.s1 = s1;
-        p.s2 = s2;
-        p.act = act_lrelu;
-        p.upsample2x = upsample2x;
-        p.chan_scale = chan_scale;
-        p.post_act = post_act;
-        p.f32_cstride = f32_cstride;
-        p.f32_coff = f32_coff;
-        launch_conv3x3((DType)dtype, cout_tiles, res1 ? EPI_RESIDUAL : EPI_STORE, p, (hipStream_t)stream);
-    });
-}
-
-size_t fw_pack_conv3x3_wino(int dtype, const float* weight, int cout, int cin, int cin_chunks, uint16_t* dst) {
-    if (dtype != FW_DTYPE_F16) return 0;   // the Winograd kernel is f16 only
-    if (cout < 1 || cin < 1 || cin_chunks < 1 || cout > 64 || cin > 32 * cin_chunks) return 0;
-    if (dst && !weight) return 0;
-    return pack_conv3x3_wino_weights(DT_F16, weight, cout, cin, cin_chunks, dst);
-}
-
-int fw_conv3x3_split_nhwc(int dtype, int winograd, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int H, int W,
-                          const void* packed_weight, const float* bias, float s1, float in_id_scale, int n_id, const long* chunk_off,
-                          const float* id_scale, int post_act, void* out, void* out_lo, int out_cstride, long out_plane_stride,
-                          int out_coff, void* stream) {
-    if (!x || !packed_weight || !bias || !out) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: NULL argument");
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: bad dtype");
-    if (winograd != 0 && winograd != 1) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: winograd must be 0 or 1");
-    if (winograd && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: the Winograd form is f16 only");
-    if (n_id < 0 || n_id > 6) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: n_id must be in [0, 6]");
-    if (n_id > 0 && (!chunk_off || !id_scale)) return fail(FW_ERR_INVALID, "fw_conv3x3_split_nhwc: residual planes need chunk_off and id_scale");
-    return guarded([&] {
-        ConvParams p{};
-        p.in = x;
-        p.in_cstride = in_cstride;
-        p.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
-        p.cin_chunks = cin_chunks;
-        p.H = H;
-        p.W = W;
-        p.wpk = packed_weight;
-        p.bias = bias;
-        p.s1 = s1;
-        p.s2 = 1.f;
-        p.in_id_scale = in_id_scale;
-        p.n_id = n_id;
-        for (int i = 0; i < n_id; ++i) {
-            p.chunk_off[i] = chunk_off[i];
-            p.id_scale[i] = id_scale[i];
-        }
-        p.post_act = post_act;
-        p.out = out;
-        p.out_lo = out_lo;
-        p.out_cstride = out_cstride;
-        p.out_pstride = out_plane_stride > 0 ? out_plane_stride : 32;
-        p.out_coff = out_coff;
-        if (winograd)
-            launch_conv3x3_wino_split(p, (hipStream_t)stream);
-        else
-            launch_conv3x3((DType)dtype, 2, EPI_RESIDUAL_SPLIT, p, (hipStream_t)stream);
-    });
-}
-
-size_t fw_pack_conv_last_pointwise(int dtype, const float* weight, uint16_t* dst) {
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return 0;
-    if (dst && !weight) return 0;
-    return pack_conv_last_pointwise((DType)dtype, weight, dst);
-}
-
-int fw_conv3x3_hr_last_nhwc(int dtype, int fused, const void* x, int in_cstride, long in_plane_stride, int H, int W,
-                            const void* packed_w_hr, const float* bias_hr, const void* packed_w_last, const void* packed_w_last_pw,
-                            const float* bias_last, void* scratch_u3, int img_H, int img_W, uint8_t* out_u8, uint16_t* out_u16,
-                            float* out_rgb_f32, void* stream) {
-    if (!x || !packed_w_hr || !bias_hr || !bias_last) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: NULL argument");
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: bad dtype");
-    if (fused != 0 && fused != 1) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: fused must be 0 or 1");
-    if (fused ? !packed_w_last_pw : (!packed_w_last || !scratch_u3))
-        return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: missing conv_last weights or scratch for this form");
-    if (H < 1 || W < 1 || img_H < 1 || img_W < 1 || img_H > H || img_W > W) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: bad size");
-    if (!out_u8 && !out_u16 && !out_rgb_f32) return fail(FW_ERR_INVALID, "fw_conv3x3_hr_last_nhwc: no output");
-    return guarded([&] {
-        ConvParams hr{};
-        hr.in = x;
-        hr.in_cstride = in_cstride;
-        hr.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
-        hr.cin_chunks = 2;
-        hr.H = H;
-        hr.W = W;
-        hr.wpk = packed_w_hr;
-        hr.bias = bias_hr;
-        hr.s1 = hr.s2 = 1.f;
-        ConvParams img{};
-        img.H = H;
-        img.W = W;
-        img.s1 = img.s2 = 1.f;
-        img.out_u8 = out_u8;
-        img.out_u16 = out_u16;
-        img.out_rgb = out_rgb_f32;
-        img.img_H = img_H;
-        img.img_W = img_W;
-        if (fused) {
-            hr.out_u8 = out_u8;
-            hr.out_u16 = out_u16;
-            hr.out_rgb = out_rgb_f32;
-            hr.img_H = img_H;
-            hr.img_W = img_W;
-            launch_conv3x3_hr_last((DType)dtype, hr, packed_w_last_pw, bias_last, (hipStream_t)stream);
-            return;
-        }
-        const long plane = (long)H * W * 32;   // scratch_u3: two 32-channel planes [H][W][32]
-        hr.out = scratch_u3;
-        hr.out_cstride = 32;
-        hr.out_pstride = plane;
-        hr.act = 1;
-        launch_conv3x3((DType)dtype, 2, EPI_STORE, hr, (hipStream_t)stream);
-        img.in = scratch_u3;
-        img.in_cstride = 32;
-        img.in_pstride = plane;
-        img.cin_chunks = 2;
-        img.wpk = packed_w_last;
-        img.bias = bias_last;
-        launch_conv3x3((DType)dtype, 1, EPI_IMAGE, img, (hipStream_t)stream);
-    });
-}
-
-int fw_conv3x3_wino_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int cin_chunks, int H, int W,
-                         const void* packed_weight, const float* bias, int act_lrelu, void* out, int out_cstride, long out_plane_stride,
-                         int out_coff, void* stream) {
-    if (!x || !packed_weight || !bias || !out) return fail(FW_ERR_INVALID, "fw_conv3x3_wino_nhwc: NULL argument");
-    if (dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv3x3_wino_nhwc: the Winograd form is f16 only");
-    if (act_lrelu != 0 && act_lrelu != 1) return fail(FW_ERR_INVALID, "fw_conv3x3_wino_nhwc: act_lrelu must be 0 or 1");
-    return guarded([&] {
-        ConvParams p{};
-        p.in = x;
-        p.in_cstride = in_cstride;
-        p.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
-        p.cin_chunks = cin_chunks;
-        p.H = H;
-        p.W = W;
-        p.wpk = packed_weight;
-        p.bias = bias;
-        p.act = act_lrelu;
-        p.out = out;
-        p.out_cstride = out_cstride;
-        p.out_pstride = out_plane_stride > 0 ? out_plane_stride : 32;
-        p.out_coff = out_coff;
-        launch_conv3x3_wino_store(p, (hipStream_t)stream);
-    });
-}
-
-int fw_conv3x3_wino_check_fields(int* codes, int n) {
-    // one valid problem per form, then one field at a time set to what the Winograd kernels do not implement (no launch, no device call)
-    static const float one = 1.f;
-    static char dummy[16];
-    ConvParams ok{};
-    ok.H = ok.W = 16;
-    ok.cin_chunks = 2;
-    ok.in_cstride = 32;
-    ok.in_pstride = 16 * 16 * 32;
-    ok.out = dummy;
-    ok.out_cstride = 32;
-    ok.out_pstride = 16 * 16 * 32;
-    ok.s1 = 0.2f;
-    ok.in_id_scale = 5.f;
-    ok.n_id = 2;
-    ok.id_scale[0] = ok.id_scale[1] = 5.f;
-    ok.f32_native = 1;   // set for every conv of the engine; meaningless without fp32 side buffers, accepted
-    struct Case { bool split; void (*set)(ConvParams&); };
-    static const Case cases[] = {
-        {true, [](ConvParams& p) { p.post_act = 1; }},
-        {true, [](ConvParams& p) { p.chan_scale = &one; }},
-        {true, [](ConvParams& p) { p.res1 = &one; }},
-        {true, [](ConvParams& p) { p.res2 = &one; }},
-        {true, [](ConvParams& p) { p.out_f32 = const_cast<float*>(&one); }},
-        {true, [](ConvParams& p) { p.n_groups = 2; }},
-        {true, [](ConvParams& p) { p.act = 1; }},
-        {true, [](ConvParams& p) { p.in_id_scale = 0.1f; }},
-        {true, [](ConvParams& p) { p.id_scale[1] = 0.1f; }},
-        {false, [](ConvParams& p) { p.out_f32 = const_cast<float*>(&one); }},
-        {false, [](ConvParams& p) { p.n_groups = 2; }},
-        {false, [](ConvParams& p) { p.chan_scale = &one; }},
-        {false, [](ConvParams& p) { p.post_act = 1; }},
-        {false, [](ConvParams& p) { p.res1 = &one; }},
-        {false, [](ConvParams& p) { p.act = 2; }},
-        {false, [](ConvParams& p) { p.out_lo = dummy; }},
-    };
-    const int nc = (int)(sizeof(cases) / sizeof(cases[0]));
-    ConvParams st = ok;
-    st.n_id = 0;
-    st.in_id_scale = 0.f;
-    st.act = 1;
-    try {   // the unmodified problems pass
-        check_conv3x3_wino(ok, true);
-        check_conv3x3_wino(st, false);
-    } catch (const fw::Error& e) {
-        fail(FW_ERR_INTERNAL, std::string("fw_conv3x3_wino_check_fields: a valid problem was rejected: ") + e.what());
-        return -1;
-    }
-    for (int i = 0; i < nc && i < n; ++i) {
-        ConvParams p = cases[i].split ? ok : st;
-        cases[i].set(p);
-        codes[i] = guarded([&] { check_conv3x3_wino(p, cases[i].split); });
-    }
-    return nc;
-}
-
-size_t fw_pack_conv_up2x_phase(int dtype, const float* weight, uint16_t* dst) {
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return 0;
-    if (dst && !weight) return 0;
-    return pack_conv_up2x_phase_weights((DType)dtype, weight, dst);
-}
-
-int fw_conv_up2x_phase_nhwc(int dtype, const void* x, int in_cstride, long in_plane_stride, int H, int W, const void* packed_weight,
-                            const float* bias, int act_lrelu, void* out, int out_cstride, long out_plane_stride, void* stream) {
-    if (!x || !packed_weight || !bias || !out) return fail(FW_ERR_INVALID, "fw_conv_up2x_phase_nhwc: NULL argument");
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_conv_up2x_phase_nhwc: bad dtype");
-    if (H < 1 || W < 1) return fail(FW_ERR_INVALID, "fw_conv_up2x_phase_nhwc: bad size");
-    return guarded([&] {
-        ConvUpParams u{};
-        u.in = x;
-        u.in_cstride = in_cstride;
-        u.in_pstride = in_plane_stride > 0 ? in_plane_stride : 32;
-        u.H = H;
-        u.W = W;
-        u.wpk = packed_weight;
-        u.bias = bias;
-        u.act = act_lrelu;
-        u.out = out;
-        u.out_cstride = out_cstride;
-        u.out_pstride = out_plane_stride > 0 ? out_plane_stride : 32;
-        launch_conv_up2x_phase((DType)dtype, u, (hipStream_t)stream);
-    });
-}
-
-int fw_u8_to_nhwc(int dtype, const uint8_t* in_bgr, int H, int W, void* out, int out_cstride, void* stream) {
-    if (!in_bgr || !out || H < 1 || W < 1) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc: bad argument");
-    if (dtype != FW_DTYPE_BF16 && dtype != FW_DTYPE_F16) return fail(FW_ERR_INVALID, "fw_u8_to_nhwc: bad dtype");
-    return guarded([&] { launch_u8_to_nhwc((DType)dtype, in_bgr, H, W, out, out_cstride, 1, (hipStream_t)stream); });
-}
-
-int fw_pixel_shuffle_add_u8(const float* conv, int conv_cstride, const uint8_t* in_bgr, int H, int W, int scale,
-                            uint8_t* out_bgr, float* out_rgb_f32, void* stream) {
-    if (!conv || !in_bgr || (!out_bgr && !out_rgb_f32) || H < 1 || W < 1)
-        return fail(FW_ERR_INVALID, "fw_pixel_shuffle_add_u8: bad argument");
-    return guarded([&] {
-        launch_pixel_shuffle_add(conv, conv_cstride, in_bgr, H, W, scale, out_bgr, out_rgb_f32, (hipStream_t)stream);
-    });
-}
+int fw_rrdbnet_destroy(fw_rrdbnet* n) { return destroy_engine(n); }
 
 }  // extern "C"

@@ -31,15 +31,11 @@ struct Layer {
 
 }  // namespace
 
-struct fw_srvgg {
-    int device = 0;
-    fw::StreamOrder order;   // device-side ordering of forwards enqueued on different streams (fw_internal.h)
+struct fw_srvgg : fw::EngineBase {
     DType dt = DT_F16;
     int num_feat = 64, num_conv = 16, scale = 4;
-    std::mutex mu;
     std::vector<Layer> layers;   // num_conv + 2
     bool built = false;
-    DevBuf ws;
 };
 
 namespace {
@@ -202,12 +198,10 @@ int upscale_any(fw_srvgg* n, const void* in_bgr, int bits, int in_loc, int H, in
     int rc = fw_srvgg_finalize(n);
     if (rc != FW_OK) return rc;
     return guarded([&] {
-        std::lock_guard<std::mutex> lk(n->mu);
-        DevGuard dg(n->device);
-        hipStream_t st = (hipStream_t)stream;
-        StreamOrder::Scope in_order(n->order, st);
+        EngineCall call(n, stream);
+        hipStream_t st = call.st;
         const Plan pl = make_plan(n, H, W);
-        ensure_workspace(n->ws, pl.total);
+        reserve_workspace(n, pl.total);
         char* ws = (char*)n->ws.p;
         const size_t in_bytes = (size_t)H * W * 3 * (bits / 8), out_bytes = in_bytes * n->scale * n->scale;
         const void* d_in = in_bgr;
@@ -236,23 +230,6 @@ int fw_srvgg_upscale_u16(fw_srvgg* n, const uint16_t* in_bgr, int in_loc, int H,
     return upscale_any(n, in_bgr, 16, in_loc, H, W, out_bgr, out_loc, out_rgb_f32, stream, "fw_srvgg_upscale_u16");
 }
 
-int fw_srvgg_destroy(fw_srvgg* n) {
-    if (!n) return FW_OK;
-    { std::lock_guard<std::mutex> lk(n->mu); }   // a call in flight on another thread finishes first
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(n->device);
-    (void)hipDeviceSynchronize();
-    for (auto& L : n->layers) {
-        L.w.release();
-        L.b.release();
-        L.slopes.release();
-    }
-    n->ws.release();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    n->order.destroy();
-    delete n;
-    return FW_OK;
-}
+int fw_srvgg_destroy(fw_srvgg* n) { return destroy_engine(n); }
 
 }  // extern "C"
