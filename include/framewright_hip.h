@@ -1102,6 +1102,24 @@ int fw_framegen_finish_u8(const uint8_t* generated, uint8_t* out, int height, in
 int fw_framegen_extrapolate_u8(const uint8_t* reference, uint8_t* out, int height, int width, const float* noise, const float* noise_table,
                                uint64_t noise_key, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Cross-frame temporal consistency (csrc/temporal_consistency.hip, DESIGN K23): the classical path of the reference's
+ * processors/cross_attention_temporal.py on uint8 BGR H x W x 3 DEVICE frames; tests/temporal_consistency_ref.py is the contract,
+ * byte for byte.  Device pointers, explicit stream; nothing is allocated and nothing synchronises.
+ *   fw_tcons_gray_hist_u8: hist[256] (DEVICE uint32) = the counts of cvtColor(BGR2GRAY) of one frame, what cv2.calcHist counts in
+ *     `_detect_scene_change`; the cell is cleared and filled by integer adds, the same bits on every run.
+ *   fw_tcons_apply_u8: `_detect_flicker(prev, cur, next)` and the blend of `_apply_optical_flow_consistency` in one launch: the
+ *     binary mask min(dp, dn) * (1 - nb) > flicker_threshold of the gray absolute differences over 255, GaussianBlur((5, 5), 0) with
+ *     BORDER_REFLECT_101 as the integer k = 256 x mask, and out = trunc(cur * (1 - m3) + ((prev + next) / 2) * m3), m3 =
+ *     (k / 256) * blend_strength, every step one float32 operation.  flicker_threshold and blend_strength are the reference's Python
+ *     floats rounded to float32.  out, mask_out (float32 H x W, k / 256) and area_out (one uint64: cleared, then the sum of k over the
+ *     frame; the reference's np.mean(mask) is area / (256 H W)) may each be NULL, not all three.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL frames, a side outside 3 .. 16384 (1 .. 16384 for the
+ * histogram), a non-finite threshold, a strength outside [0, 1], misaligned mask_out / area_out / hist, an out that overlaps a frame. */
+int fw_tcons_gray_hist_u8(const uint8_t* frame, int height, int width, uint32_t* hist, void* stream);
+int fw_tcons_apply_u8(const uint8_t* prev, const uint8_t* cur, const uint8_t* next, int height, int width, float flicker_threshold,
+                      float blend_strength, uint8_t* out, float* mask_out, uint64_t* area_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,3 +18,5 @@ from .qp_artifacts import (ArtifactType, CompressionLevel, DeviceQPArtifactRemov
                            create_qp_artifact_remover)
 from .frame_generation import (DeviceMissingFrameGenerator, FrameGenerationConfig, FrameGenerationResult, GapInfo,  # noqa: E402,F401
                                GenerationModel, create_frame_generator)
+from .temporal_consistency import (CrossAttentionConfig, DeviceTemporalConsistencyProcessor, TemporalConsistencyResult,  # noqa: E402,F401
+                                   TemporalMethod, create_temporal_processor)

@@ -67,12 +67,17 @@ class DeviceRestorationPipeline:
     reach the generator, so a stage in front that changes the frame count (BOB deinterlacing) does not go with them.  Without
     ``frame_numbers`` nothing is filled.  The streaming forms take the numbers as a parallel iterable, hold back one frame
     (`DeviceMissingFrameGenerator.stream`) and equal `run_device`.
+
+    ``temporal_consistency`` (a `temporal_consistency.DeviceTemporalConsistencyProcessor`; opt-in) de-flickers the final frames behind
+    the interpolation and in front of the colour grade, where the reference has its step 7b: `apply_device` on the clip, which lists
+    the scene cuts (one wait) and passes the frames around a cut through as they are.  The streaming forms use its `stream`, which
+    is `attention_window // 2 + 1` frames behind its input and equals `run_device`.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
                  deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True,
                  quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0, hdr_converter=None, artifact_remover=None,
-                 artifact_qp=None, frame_generator=None, expected_frames=None):
+                 artifact_qp=None, frame_generator=None, expected_frames=None, temporal_consistency=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -86,11 +91,13 @@ class DeviceRestorationPipeline:
         self.hdr_converter = hdr_converter
         self.artifact_remover, self.artifact_qp = artifact_remover, artifact_qp
         self.frame_generator, self.expected_frames = frame_generator, expected_frames
+        self.temporal_consistency = temporal_consistency
 
     def _stages(self) -> tuple:
         """Every configured stage slot, in the order `_device` asks them: a new stage adds its name here."""
         return (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
-                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter, self.artifact_remover, self.frame_generator)
+                self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter, self.artifact_remover, self.frame_generator,
+                self.temporal_consistency)
 
     def close(self) -> None:
         """Closes every stage that can be closed (the engines free their native handles, the HDR converter its tables)."""
@@ -144,6 +151,8 @@ class DeviceRestorationPipeline:
                         if i + 1 < len(cur):
                             nxt.append(self.interpolator.interpolate_device(f, cur[i + 1]))
                     cur = nxt
+            if self.temporal_consistency is not None:
+                cur = self.temporal_consistency.apply_device(cur)
             if self.color_grader is not None:
                 cur = self.color_grader.apply_device(cur)      # new tensors: a repeated frame may be one tensor several times
             if self.aspect_handler is not None and self.aspect_target is not None:
@@ -165,7 +174,7 @@ class DeviceRestorationPipeline:
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
         the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers, the HDR converter, the
-        artifact remover, the frame generator.
+        artifact remover, the frame generator, the temporal-consistency processor.
         Every stage answers through `_lib.owner_device`: a new stage adds its name to `_stages`."""
         for stage in self._stages():
             dev = _lib.owner_device(stage)
@@ -264,6 +273,8 @@ class DeviceRestorationPipeline:
             if self.interpolator is not None:
                 for _ in range(self.interp_passes):
                     g = self._gen_interp(g)
+            if self.temporal_consistency is not None:
+                g = self.temporal_consistency.stream(g)
             if self.color_grader is not None:
                 g = (self.color_grader.apply_device([f])[0] for f in g)
             if self.aspect_handler is not None and self.aspect_target is not None:
