@@ -1120,6 +1120,45 @@ int fw_tcons_gray_hist_u8(const uint8_t* frame, int height, int width, uint32_t*
 int fw_tcons_apply_u8(const uint8_t* prev, const uint8_t* cur, const uint8_t* next, int height, int width, float flicker_threshold,
                       float blend_strength, uint8_t* out, float* mask_out, uint64_t* area_out, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Perceptual tuning of final frames (csrc/perceptual.hip, DESIGN K24): the frame path of the reference's
+ * processors/perceptual_tuning.py (`PerceptualTuner.apply_to_frame`) on uint8 BGR H x W x 3 DEVICE frames; tests/perceptual_ref.py is
+ * the contract, byte for byte.  Device pointers, explicit stream; nothing synchronises (the Lab tables are made on a device's first
+ * call with detail recovery).  Every weight is the reference's Python double rounded to float32 by the caller.
+ *   fw_ptune_unsharp_u8: addWeighted(src, w_src, GaussianBlur(src, (0, 0), 3), w_blur, 0) in one launch: 19 taps in 8-bit fixed point,
+ *     rows into 16 bits, columns into 32, (v + 2^15) >> 16, BORDER_REFLECT_101 as often as it takes.
+ *   fw_ptune_gauss19_table: HOST function (no GPU needed): the 19 integer taps of that blur (sum 256) into out19.
+ *   fw_ptune_clahe_u8: cv2.createCLAHE(clip, (8, 8)).apply on a uint8 H x W plane; limit = max(int(clip * tile area / 256), 1), the
+ *     caller's, computed in double.  fw_ptune_detail_u8: BGR -> Lab, that CLAHE in place of L, Lab -> BGR.
+ *   fw_ptune_grain_u8: g = gray(original); addWeighted(result, 1.0, max(g - GaussianBlur(g, (5, 5), 0), 0) on all channels, amount, 0).
+ *   fw_ptune_apply_u8: the steps that params switches on, in the reference's order: fastNlMeansDenoisingColored(h, h, 7, 21) where
+ *     denoise_h > 0 (a launch of fw_nlmeans_colored_u8), then sharpen, colour (fw_hdr_saturation_u8's pixel step; hsv_div is its
+ *     DEVICE table), detail and grain (of src, the original).  Without detail: one launch behind the denoise (nothing on: a copy).  With
+ *     it: one pass that stores the sharpened and coloured bytes, the tile histograms of their L, the 64 maps, one pass that writes.
+ *   scratch: DEVICE memory, 4-byte aligned.  fw_ptune_scratch_bytes(height, width, params) is what fw_ptune_apply_u8 needs with those
+ *     params: 0 without denoise and detail (scratch may be NULL), 81920 bytes (the histograms and the maps) with detail alone or with
+ *     grain, one frame more where sharpen or colour run in front of detail, and two frames and the non-local means' own planes with
+ *     denoise.  params = NULL: the 81920 bytes of fw_ptune_clahe_u8 and fw_ptune_detail_u8.  0 on bad sizes.
+ * Refused with FW_ERR_INVALID and a message, nothing launched: NULL pointers, a side outside 3 .. 16384 (8 .. 16384 with detail
+ * recovery or CLAHE), weights that are not finite, a limit below 1, a dst that overlaps src (or result / original): every output
+ * reads a neighbourhood. */
+typedef struct fw_ptune_params {
+    int32_t denoise_h;          /* 0: no denoise */
+    int32_t sharpen, colour, detail, grain;
+    int32_t clahe_limit;
+    float w_src, w_blur;        /* sharpen */
+    float boost, hue_scale;     /* colour: hue_scale = float32(6 / 180) */
+    float grain_amount;
+    const int32_t* hsv_div;     /* colour: DEVICE [512], as fw_hdr_saturation_u8 takes it */
+} fw_ptune_params;
+size_t fw_ptune_scratch_bytes(int height, int width, const fw_ptune_params* params);
+int fw_ptune_gauss19_table(int32_t* out19);
+int fw_ptune_unsharp_u8(const uint8_t* src, uint8_t* dst, int height, int width, float w_src, float w_blur, void* stream);
+int fw_ptune_clahe_u8(const uint8_t* plane, uint8_t* dst, int height, int width, int limit, void* scratch, void* stream);
+int fw_ptune_detail_u8(const uint8_t* src, uint8_t* dst, int height, int width, int limit, void* scratch, void* stream);
+int fw_ptune_grain_u8(const uint8_t* result, const uint8_t* original, uint8_t* dst, int height, int width, float amount, void* stream);
+int fw_ptune_apply_u8(const uint8_t* src, uint8_t* dst, int height, int width, const fw_ptune_params* params, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,3 +20,5 @@ from .frame_generation import (DeviceMissingFrameGenerator, FrameGenerationConfi
                                GenerationModel, create_frame_generator)
 from .temporal_consistency import (CrossAttentionConfig, DeviceTemporalConsistencyProcessor, TemporalConsistencyResult,  # noqa: E402,F401
                                    TemporalMethod, create_temporal_processor)
+from .perceptual import (DevicePerceptualTuner, PerceptualConfig, PerceptualMode, PerceptualProfile,  # noqa: E402,F401
+                         create_perceptual_tuner, get_perceptual_profile)

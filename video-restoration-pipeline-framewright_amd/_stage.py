@@ -1,7 +1,7 @@
-"""What the Python drivers of the seventeen frame stages share (DeviceFlowEstimator, DeviceSpatialDenoiser, DeviceTemporalAccumulator,
+"""What the Python drivers of the eighteen frame stages share (DeviceFlowEstimator, DeviceSpatialDenoiser, DeviceTemporalAccumulator,
 DeviceClipAnalyzer, DeviceFlickerReducer, DeviceTemporalConsistencyFilter, DeviceSceneCutDetector, DeviceFrameDeduplicator,
 DeviceColorGrader, DeviceDeinterlacer, DeviceVHSProcessor, DeviceAspectHandler, DeviceFrameQualityScorer, DeviceHDRConverter,
-DeviceQPArtifactRemover, DeviceMissingFrameGenerator, DeviceTemporalConsistencyProcessor): the owner of a device and a scratch buffer, the frame checks, the overlap
+DeviceQPArtifactRemover, DeviceMissingFrameGenerator, DeviceTemporalConsistencyProcessor, DevicePerceptualTuner): the owner of a device and a scratch buffer, the frame checks, the overlap
 check and the transfers between numpy and the device.  The C++ counterpart is csrc/stage_common.h.  Every check takes the refusing
 stage's own message: what a stage says when it refuses is the stage's, that it is said is written here.
 """

@@ -36,13 +36,15 @@ ARCH = "gfx950"
 # qp_artifacts.hip: the bilateral's b * w + sum, the 15-tap Gaussian and the float64 blends round after every operation, as tests/qp_artifact_ref.py does
 # frame_generation.hip: map = grid + flow * t, the 17-tap blur and the float64 grain sum round after every operation, as tests/frame_generation_ref.py does
 # temporal_consistency.hip: cur * (1 - m3) + blend * m3 is numpy's float32 arithmetic, two products and a sum; one FMA in it changes output bytes
+# perceptual.hip: addWeighted(x, 1.0, grain, amount) is float(grain) * amount, then the sum: one FMA rounds once where cv2 rounds twice
 # aspect.hip (picked up by `sources()` like every csrc/*.hip) is integer arithmetic throughout: no flag
 PER_FILE_FLAGS = {"frame_ops.hip": ["-ffp-contract=off"], "optical_flow.hip": ["-ffp-contract=off"], "nlmeans.hip": ["-ffp-contract=off"],
                   "temporal_chain.hip": ["-ffp-contract=off"], "flicker.hip": ["-ffp-contract=off"], "scene_cuts.hip": ["-ffp-contract=off"],
                   "dedup_hash.hip": ["-ffp-contract=off"], "color_lut.hip": ["-ffp-contract=off"],
                   "deinterlace.hip": ["-ffp-contract=off"], "vhs.hip": ["-ffp-contract=off"], "quality.hip": ["-ffp-contract=off"],
                   "hdr.hip": ["-ffp-contract=off"], "qp_artifacts.hip": ["-ffp-contract=off"],
-                  "frame_generation.hip": ["-ffp-contract=off"], "temporal_consistency.hip": ["-ffp-contract=off"]}
+                  "frame_generation.hip": ["-ffp-contract=off"], "temporal_consistency.hip": ["-ffp-contract=off"],
+                  "perceptual.hip": ["-ffp-contract=off"]}
 EXTRA = os.environ.get("FW_EXTRA_CXXFLAGS", "").split()
 CXXFLAGS = [*EXTRA, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -1,6 +1,6 @@
 // The per-pixel bodies of the 8-bit sRGB BGR <-> Lab transforms (cv2.COLOR_BGR2LAB / COLOR_LAB2BGR as tests/flicker_ref.py states them:
 // integers over the tables of lab_tables.h plus a 256-entry sRGB decode in front and an sRGB encode, 255 thresholds, behind), shared by
-// flicker.hip, where they were written, and hdr.hip (the local-contrast step of the HDR conversion).  Integer arithmetic throughout,
+// flicker.hip, where they were written, hdr.hip (the local-contrast step of the HDR conversion) and perceptual.hip (detail recovery).  Integer arithmetic throughout,
 // so the floating-point flags of the including file play no part.  device_gamma_small() is defined in flicker.hip.
 #pragma once
 #include "lab_tables.h"

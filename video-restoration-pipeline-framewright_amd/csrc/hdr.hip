@@ -25,6 +25,8 @@
 // so two runs give the same bytes.
 #include "stage_common.h"
 #include "gamma_lab.h"
+#include "clahe.h"
+#include "hsv_sat.h"
 
 #include <cmath>
 
@@ -36,8 +38,7 @@ namespace {
 constexpr int HD_NT = 256;
 constexpr int HD_MAX_FRAMES = 32;
 constexpr int HD_MIN_SIDE = 8;
-constexpr int HD_GRID = 8;                                       // CLAHE tiles a side
-constexpr int HD_HIST = HD_GRID * HD_GRID * 256;                 // bins a frame
+constexpr int HD_GRID = CL_GRID, HD_HIST = CL_HIST;              // clahe.h: tiles a side, bins a frame
 constexpr int HD_BLOCKS = 2048;
 
 struct Frames {
@@ -45,30 +46,9 @@ struct Frames {
     void* dst[HD_MAX_FRAMES];
 };
 
-struct Geo {
-    int H, W, Hp, Wp, th, tw, limit;
-    float inv_th, inv_tw, lut_scale;
-};
+using Geo = ClaheGeo;
 
-Geo geometry(int H, int W) {
-    Geo g;
-    g.H = H, g.W = W;
-    const bool whole = H % HD_GRID == 0 && W % HD_GRID == 0;
-    g.Hp = whole ? H : H + HD_GRID - H % HD_GRID;
-    g.Wp = whole ? W : W + HD_GRID - W % HD_GRID;
-    g.th = g.Hp / HD_GRID, g.tw = g.Wp / HD_GRID;
-    const int area = g.th * g.tw;
-    g.limit = std::max((int)(2.0 * area / 256), 1);
-    g.inv_th = (float)(1.0 / g.th), g.inv_tw = (float)(1.0 / g.tw);
-    g.lut_scale = (float)(255.0 / area);
-    return g;
-}
-
-// numpy's clip: the bound where the value is not beyond it, so -0.0 becomes the bound's +0.0
-__device__ __forceinline__ float clipf(float x, float lo, float hi) {
-    const float t = x > lo ? x : lo;
-    return t < hi ? t : hi;
-}
+Geo geometry(int H, int W) { return clahe_geometry(H, W, clahe_limit(2.0, H, W)); }
 
 __device__ __forceinline__ float curve_lum(const fw_hdr_params& P, float lum) {
     const float* k = P.curve_k;
@@ -218,80 +198,20 @@ __global__ __launch_bounds__(HD_NT) void hist_kernel(Frames fr, Geo G, int rows_
     if (SRC == 0) s_gamma[tid] = gamma_g[tid], gm = s_gamma;
     if (SRC != 2) s_dec[tid] = (uint16_t)small_g[tid];
     __syncthreads();
-    const int ty = blockIdx.y, f = blockIdx.z;
-    const int r0 = ty * G.th + blockIdx.x * rows_per_block;
-    const int r1 = min(r0 + rows_per_block, (ty + 1) * G.th);
-    const long count = (long)max(r1 - r0, 0) * G.Wp;
-    for (long i = tid; i < count; i += HD_NT) {
-        const int yp = r0 + (int)(i / G.Wp), xp = (int)(i % G.Wp);
-        const long p = (long)reflect101(yp, G.H) * G.W + reflect101(xp, G.W);          // the padding is the frame mirrored
-        uint32_t L;
-        if (SRC == 2) {
-            L = static_cast<const uint8_t*>(fr.src[f])[p];
-        } else {
-            uint32_t c[3];
+    const int f = blockIdx.z;
+    clahe_count_rows(s_hist, G, rows_per_block, hist_g + (size_t)f * HD_HIST, [&](long p) -> uint32_t {
+        if (SRC == 2) return static_cast<const uint8_t*>(fr.src[f])[p];
+        uint32_t c[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-                c[k] = SRC == 0 ? static_cast<const uint8_t*>(fr.src[f])[3 * p + k] : static_cast<const uint16_t*>(fr.src[f])[3 * p + k];
-            float o[3];
-            tone_px(P, gm[c[0]], gm[c[1]], gm[c[2]], o);
-            L = l_of_px(quantise_px(o), s_dec, kf, cbrt_tab);
-        }
-        atomicAdd(&s_hist[(xp / G.tw) * 256 + L], 1u);
-    }
-    __syncthreads();
-    uint32_t* out = hist_g + ((size_t)f * HD_GRID + ty) * HD_GRID * 256;
-#pragma unroll
-    for (int k = 0; k < HD_GRID; ++k) {
-        const uint32_t v = s_hist[k * 256 + tid];
-        if (v) atomicAdd(&out[k * 256 + tid], v);
-    }
+        for (int k = 0; k < 3; ++k)
+            c[k] = SRC == 0 ? static_cast<const uint8_t*>(fr.src[f])[3 * p + k] : static_cast<const uint16_t*>(fr.src[f])[3 * p + k];
+        float o[3];
+        tone_px(P, gm[c[0]], gm[c[1]], gm[c[2]], o);
+        return l_of_px(quantise_px(o), s_dec, kf, cbrt_tab);
+    });
 }
 
-// one workgroup per tile: grid (64, n).  lane i holds bin i
-__global__ __launch_bounds__(256) void lut_kernel(const uint32_t* __restrict__ hist_g, uint8_t* __restrict__ luts, int limit, float lut_scale) {
-    __shared__ int s_scan[256];
-    __shared__ int s_wave[4];
-    const int tid = threadIdx.x;
-    const size_t base = ((size_t)blockIdx.y * HD_GRID * HD_GRID + blockIdx.x) * 256;
-    int h = (int)hist_g[base + tid];
-    const int over = wave_sum(max(h - limit, 0));
-    if ((tid & 63) == 0) s_wave[tid >> 6] = over;
-    __syncthreads();
-    const int excess = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    h = min(h, limit) + excess / 256;
-    const int residual = excess % 256;
-    if (residual) {
-        const int step = max(256 / residual, 1);
-        if (tid % step == 0 && tid / step < residual) ++h;
-    }
-    s_scan[tid] = h;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {                              // inclusive scan: integers, any order gives the same sums
-        const int add = tid >= d ? s_scan[tid - d] : 0;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
-    const int v = __float2int_rn((float)s_scan[tid] * lut_scale);
-    luts[base + tid] = (uint8_t)min(max(v, 0), 255);
-}
-
-// cv2's CLAHE interpolation of value v at (x, y) between the four nearest tile LUTs of frame `luts`; then the half-and-half blend
-__device__ __forceinline__ uint32_t clahe_px(const uint8_t* __restrict__ luts, const Geo& G, int x, int y, uint32_t v) {
-    const float txf = (float)x * G.inv_tw - 0.5f, tyf = (float)y * G.inv_th - 0.5f;
-    const float fx = floorf(txf), fy = floorf(tyf);
-    const float xa = txf - fx, ya = tyf - fy;
-    const int tx1 = min(max((int)fx, 0), HD_GRID - 1), tx2 = min(max((int)fx + 1, 0), HD_GRID - 1);
-    const int ty1 = min(max((int)fy, 0), HD_GRID - 1), ty2 = min(max((int)fy + 1, 0), HD_GRID - 1);
-    const float xb = 1.0f - xa, yb = 1.0f - ya;
-    const float l11 = luts[(ty1 * HD_GRID + tx1) * 256 + v], l12 = luts[(ty1 * HD_GRID + tx2) * 256 + v];
-    const float l21 = luts[(ty2 * HD_GRID + tx1) * 256 + v], l22 = luts[(ty2 * HD_GRID + tx2) * 256 + v];
-    const float top = l11 * xb + l12 * xa, bottom = l21 * xb + l22 * xa;
-    const float res = top * yb + bottom * ya;
-    return (uint32_t)min(max(__float2int_rn(res), 0), 255);
-}
-
+// the half-and-half blend of L with its CLAHE (clahe.h)
 __device__ __forceinline__ uint32_t blend_half(uint32_t a, uint32_t b) {      // cv2.addWeighted(a, 0.5, b, 0.5, 0)
     return (uint32_t)__float2int_rn((float)a * 0.5f + (float)b * 0.5f);       // exact products and sum; at most 255
 }
@@ -305,38 +225,7 @@ __global__ __launch_bounds__(HD_NT) void clahe_apply_kernel(const uint8_t* __res
     }
 }
 
-// ---- HSV -----------------------------------------------------------------------------------------------------------------------------
-// cv2's sector table {1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}: two bits per (sector, channel)
-constexpr uint64_t sector_bits() {
-    const int t[18] = {1, 3, 0, 1, 0, 2, 3, 0, 1, 0, 2, 1, 0, 1, 3, 2, 1, 0};
-    uint64_t v = 0;
-    for (int i = 0; i < 18; ++i) v |= (uint64_t)t[i] << (2 * i);
-    return v;
-}
-
-// 8-bit BGR -> integer HSV (hue 0 .. 179) -> s = trunc(clip(s * boost, 0, 255)) -> float32 HSV -> BGR.  div: sdiv[256], hdiv[256]
-__device__ __forceinline__ uint32_t saturate_px(uint32_t q, const int* div, float boost, float hue_scale) {
-    const int b = q & 255u, g = (q >> 8) & 255u, r = (q >> 16) & 255u;
-    const int v = max(max(b, g), r), diff = v - min(min(b, g), r);
-    const int s = (diff * div[v] + 2048) >> 12;
-    int h = v == r ? g - b : v == g ? b - r + 2 * diff : r - g + 4 * diff;
-    h = (h * div[256 + diff] + 2048) >> 12;
-    if (h < 0) h += 180;
-    const int s2 = (int)clipf((float)s * boost, 0.0f, 255.0f);
-    const float hh = (float)(h & 255) * hue_scale, ss = __fdiv_rn((float)s2, 255.0f), vv = __fdiv_rn((float)v, 255.0f);
-    const float sec = floorf(hh), fr = hh - sec;
-    const int sector = ((int)sec) % 6;
-    const float t0 = vv, t1 = vv * (1.0f - ss), t2 = vv * (1.0f - ss * fr), t3 = vv * (1.0f - ss * (1.0f - fr));
-    uint32_t out = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int pick = (int)((sector_bits() >> (2 * (3 * sector + c))) & 3u);
-        const float x = pick == 0 ? t0 : pick == 1 ? t1 : pick == 2 ? t2 : t3;
-        out |= (uint32_t)min(max(__float2int_rn(x * 255.0f), 0), 255) << (8 * c);
-    }
-    return out;
-}
-
+// ---- HSV (the pixel body is hsv_sat.h's) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(HD_NT) void saturation_kernel(const uint8_t* src, uint8_t* dst, long npx, const int* __restrict__ div_g,
                                                            float boost, float hue_scale) {
     __shared__ int s_div[512];
@@ -434,14 +323,14 @@ void launch_hist(const Frames& fr, int n, const Geo& G, const fw_hdr_params& P, 
     const LabTables& t = lab_tables();
     const DeviceLab lab = device_lab();
     const int* small = device_gamma_small();
-    const int rows = std::max(1, 16384 / G.Wp);
-    const dim3 grid((unsigned)((G.th + rows - 1) / rows), HD_GRID, (unsigned)n);
+    const int rows = clahe_hist_rows_per_block(G);
+    const dim3 grid(clahe_hist_chunks(G), HD_GRID, (unsigned)n);
     hipLaunchKernelGGL((hist_kernel<SRC>), grid, dim3(HD_NT), 0, st, fr, G, rows, P, gamma, t.fwd, lab.cbrt_tab, small, hist);
     FW_HIP_CHECK(hipGetLastError());
 }
 
 void launch_luts(int n, const Geo& G, const uint32_t* hist, uint8_t* luts, hipStream_t st) {
-    hipLaunchKernelGGL(lut_kernel, dim3(HD_GRID * HD_GRID, (unsigned)n), dim3(256), 0, st, hist, luts, G.limit, G.lut_scale);
+    hipLaunchKernelGGL(clahe_lut_kernel, dim3(HD_GRID * HD_GRID, (unsigned)n), dim3(CL_NT), 0, st, hist, luts, G.limit, G.lut_scale);
     FW_HIP_CHECK(hipGetLastError());
 }
 

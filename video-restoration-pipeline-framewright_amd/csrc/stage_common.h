@@ -1,5 +1,5 @@
 // Scaffolding shared by the frame-stage files (scene_cuts, dedup_hash, optical_flow, nlmeans, temporal_chain, flicker, color_lut,
-// deinterlace, vhs, hdr, qp_artifacts, frame_generation, temporal_consistency .hip, and frame_ops.hip for the device helpers and for the C entries of its own launchers): the status / last-error mapping of the C-ABI (fw_status.h:
+// deinterlace, vhs, hdr, qp_artifacts, frame_generation, temporal_consistency, perceptual .hip, and frame_ops.hip for the device helpers and for the C entries of its own launchers): the status / last-error mapping of the C-ABI (fw_status.h:
 // fail, invalid, hip_status, guarded), the 64-lane reductions, the small integer device helpers every stage restated, and the host
 // checks of a call's frames.  A new stage includes this header and declares none of these again.
 // The translation units that include it differ in their floating-point flags, so nothing here is floating-point arithmetic whose

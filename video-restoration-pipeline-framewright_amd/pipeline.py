@@ -72,12 +72,16 @@ class DeviceRestorationPipeline:
     the interpolation and in front of the colour grade, where the reference has its step 7b: `apply_device` on the clip, which lists
     the scene cuts (one wait) and passes the frames around a cut through as they are.  The streaming forms use its `stream`, which
     is `attention_window // 2 + 1` frames behind its input and equals `run_device`.
+
+    ``perceptual_tuner`` (a `perceptual.DevicePerceptualTuner`; opt-in) applies the perceptual look (denoise, unsharp mask,
+    saturation, CLAHE detail, grain) to the final frames behind the temporal-consistency pass and in front of the colour grade, into
+    new tensors.  Every step reads one frame, so the streaming forms have it too and hold nothing back.
     """
 
     def __init__(self, denoiser=None, upscaler=None, interpolator=None, interp_passes: int = 1, deduplicator=None, color_grader=None,
                  deinterlacer=None, vhs_processor=None, aspect_handler=None, aspect_target=None, crop_bars: bool = True,
                  quality_scorer=None, input_quality_scorer=None, quality_fps: float = 0.0, hdr_converter=None, artifact_remover=None,
-                 artifact_qp=None, frame_generator=None, expected_frames=None, temporal_consistency=None):
+                 artifact_qp=None, frame_generator=None, expected_frames=None, temporal_consistency=None, perceptual_tuner=None):
         self.denoiser, self.upscaler, self.interpolator = denoiser, upscaler, interpolator
         self.interp_passes = int(interp_passes)
         self.deduplicator = deduplicator
@@ -92,12 +96,13 @@ class DeviceRestorationPipeline:
         self.artifact_remover, self.artifact_qp = artifact_remover, artifact_qp
         self.frame_generator, self.expected_frames = frame_generator, expected_frames
         self.temporal_consistency = temporal_consistency
+        self.perceptual_tuner = perceptual_tuner
 
     def _stages(self) -> tuple:
         """Every configured stage slot, in the order `_device` asks them: a new stage adds its name here."""
         return (self.interpolator, self.upscaler, self.denoiser, self.color_grader, self.deinterlacer, self.vhs_processor,
                 self.aspect_handler, self.quality_scorer, self.input_quality_scorer, self.hdr_converter, self.artifact_remover, self.frame_generator,
-                self.temporal_consistency)
+                self.temporal_consistency, self.perceptual_tuner)
 
     def close(self) -> None:
         """Closes every stage that can be closed (the engines free their native handles, the HDR converter its tables)."""
@@ -153,6 +158,8 @@ class DeviceRestorationPipeline:
                     cur = nxt
             if self.temporal_consistency is not None:
                 cur = self.temporal_consistency.apply_device(cur)
+            if self.perceptual_tuner is not None:
+                cur = self.perceptual_tuner.apply_device(cur)  # new tensors: a repeated frame may be one tensor several times
             if self.color_grader is not None:
                 cur = self.color_grader.apply_device(cur)      # new tensors: a repeated frame may be one tensor several times
             if self.aspect_handler is not None and self.aspect_target is not None:
@@ -174,7 +181,7 @@ class DeviceRestorationPipeline:
         """The device the stages live on, for `run_device` and the streaming path alike: the interpolator's, else the upscaler's
         (the two never sit on different devices; where both are set the later stage names it, as `run_device` always had it), else
         the first of denoiser, colour grader, deinterlacer, VHS processor, aspect handler, the two quality scorers, the HDR converter, the
-        artifact remover, the frame generator, the temporal-consistency processor.
+        artifact remover, the frame generator, the temporal-consistency processor, the perceptual tuner.
         Every stage answers through `_lib.owner_device`: a new stage adds its name to `_stages`."""
         for stage in self._stages():
             dev = _lib.owner_device(stage)
@@ -275,6 +282,8 @@ class DeviceRestorationPipeline:
                     g = self._gen_interp(g)
             if self.temporal_consistency is not None:
                 g = self.temporal_consistency.stream(g)
+            if self.perceptual_tuner is not None:
+                g = self.perceptual_tuner.stream(g)
             if self.color_grader is not None:
                 g = (self.color_grader.apply_device([f])[0] for f in g)
             if self.aspect_handler is not None and self.aspect_target is not None:
